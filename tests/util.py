@@ -41,3 +41,28 @@ def pair(seed: int, b: int, n: int, m: int | None = None, kind: str = 'recon'):
         return uniform_cloud(rng, b, n), uniform_cloud(rng, b, m)
     ref = ref_cloud(rng, b, m)
     return recon_cloud(rng, ref, n), ref
+
+
+class host_independent_math:
+    """Context manager: ``torch.sqrt`` / ``torch.exp`` of float32 tensors rounded from float64 while it is active.  Torch
+    hands float32 sqrt / exp on the CPU to a vector-math library whose code path, and last bit, depends on the CPU
+    vendor; rounded from float64 (sqrt exactly, exp to far below half a float32 ulp) the bits are the same on every
+    host, so a golden vector made with it can be compared bit for bit anywhere."""
+
+    def __enter__(self):
+        import torch
+
+        self._orig = torch.sqrt, torch.exp
+        sqrt, exp = self._orig
+
+        def wrap(fn):
+            return lambda t, *a, **k: fn(t.double(), *a, **k).float() if t.dtype == torch.float32 else fn(t, *a, **k)
+
+        torch.sqrt, torch.exp = wrap(sqrt), wrap(exp)
+        return self
+
+    def __exit__(self, *exc):
+        import torch
+
+        torch.sqrt, torch.exp = self._orig
+        return False

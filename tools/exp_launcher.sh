@@ -2,7 +2,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out/exp_launcher.log
 : > $O
-A="--steps 30 --warmup 5 --no-extras --no-cpu-baseline"
+A="--full --steps 30 --warmup 5 --no-extras --no-cpu-baseline"
 pick() { python3 -c "import json,sys; r=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(sys.argv[2], r['value'], r['ms_per_step'], r.get('value_stress'))" $1 "$2" >> $O 2>&1; }
 python3 bench.py $A > gpurun_out/l0.json 2>/dev/null; pick gpurun_out/l0.json "standalone"
 OMP_NUM_THREADS=1 python3 bench.py $A > gpurun_out/l1.json 2>/dev/null; pick gpurun_out/l1.json "standalone OMP_NUM_THREADS=1"
