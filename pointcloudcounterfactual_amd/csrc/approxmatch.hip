@@ -27,7 +27,7 @@
 //                                                | fine levels (64-owner group, 16-candidate block) pairs whose box
 //                                                | distance makes every exp2(level*d2) underflow are skipped
 //                                                | (V_CULL), and points whose capacity is used up drop out as
-//                                                | candidates (V_CCAND / V_CLIST) and as owners (V_COWN)
+//                                                | candidates (V_CLIST) and as owners (V_COWN)
 //   one stream, one block per sample             | a large batch runs as two half-batch lanes on two streams so
 //                                                | that the dependent launch chains fill each other's bubbles
 //
@@ -77,7 +77,23 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // ---------------------------------------------------------------------------------------------------
 enum Phase { PH_A = 0, PH_B = 1, PH_CA = 2, PH_C = 3 };
 
-constexpr int kDbgInts = 64 + 24 * 19;  // counters + per-phase stamps
+// The per-owner recurrence of the passes (approxmatch.cu:37,61 / 106-109 / 154-162), shared by every pass kernel; each
+// caller keeps its own stores.  Same operation order as the reference, nothing contracted (-ffp-contract=off).
+//   pass A: ratioL = remainL / (1e-9 + sum_l e * remainR[l])
+__device__ __forceinline__ float pass_a_ratio(float remL, float sum) { return remL / (1e-9f + sum); }
+//   pass B: sumr = sum_k e * ratioL[k] * remainR ; ratioR = min(remainR / (sumr + 1e-9), 1) * remainR ;
+//           remainR = max(0, remainR - sumr)
+struct PassB {
+    float ratio, remain;
+};
+__device__ __forceinline__ PassB pass_b(float remR, float sum) {
+    const float sumr = sum * remR;
+    const float consumption = __builtin_fminf(remR / (sumr + 1e-9f), 1.0f);
+    return {consumption * remR, __builtin_fmaxf(0.0f, remR - sumr)};
+}
+//   pass C: remainL = max(0, remainL - sum_l e * ratioL[k] * ratioR[l])
+__device__ __forceinline__ float pass_c_left(float remL, float ratioL, float sum) { return __builtin_fmaxf(0.0f, remL - ratioL * sum); }
+
 constexpr int kBox = 16;          // points per bounding-box block (sorted order)
 constexpr int kLiveRow = 16;      // ints per sample in the live-owner counters (one per level, padded)
 constexpr int kInfSlot = 13;      // live-counter row, slots 13 / 14: set1 / set2 of the sample holds an infinite coordinate
@@ -114,8 +130,6 @@ struct PhaseArgs {
     int mask_words;
     const int *live_in;                // [b] live owners (remain != 0) of this pass B, counted by the previous pass B (V_COWN)
     int *live_out;                     // [b] pass B: live owners of the next level's pass B (integer atomics: order-free)
-    int *dbg;                          // optional [2] counters: blocks visited / skipped (debug builds of the host)
-    int *stamp;                        // optional [3][8] s_memrealtime stamps of the first / middle / last workgroup (PCC_AM_DEBUG=2)
 };
 
 // Work-skipping variants of a pass launch.  All of them only drop terms that are EXACTLY zero:
@@ -146,8 +160,6 @@ struct Sched {
     unsigned *live_mask;           // [b][kLevels][ceil(m4 / 32)] live bits of set2 per level (rows 4.. preset to ones by the sort)
     int skip;                      // work-skipping variants enabled
     LevelConsts lc;
-    int *dbg;
-    int dbg_counts;                // 1: count visited / skipped blocks (slow: one atomic per block)
 };
 
 __host__ __device__ inline int sched_phases() { return 2 * kLevels + 1; }
@@ -176,7 +188,6 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
         a.w0 = nullptr; a.w0c = sc.multiR; a.c0 = sc.lc.c[0]; a.first = 1;
         a.cut2 = kZeroExp / -sc.lc.c[0];
         a.ratio_out = sc.lv; a.ratio_stride = kLevels * nm4;
-        a.dbg = sc.dbg_counts ? sc.dbg : nullptr;
     } else {
         const int i = (p - 1) / 2;
         float *ratioL = sc.lv + (size_t)i * nm4, *ratioR = ratioL + sc.n4;
@@ -209,7 +220,6 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
                 a.live_in = (var == V_COWN && i >= 1) ? sc.live_cnt + i : nullptr;
                 a.live_out = i + 1 < kLevels ? sc.live_cnt + i + 1 : nullptr;
             }
-            a.dbg = sc.dbg_counts ? sc.dbg + 2 + 4 * i : nullptr;
         } else {           // pass C of level i (+ pass A of level i+1)
             mode = i + 1 < kLevels ? PH_CA : PH_C;
             // (the cull radius is the one of level i+1); from level 3 on pass B has left the dense candidate list
@@ -228,10 +238,8 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
                 a.c1 = sc.lc.c[i + 1];
                 a.ratio_out = sc.lv + (size_t)(i + 1) * nm4;
             }
-            a.dbg = sc.dbg_counts ? sc.dbg + 4 + 4 * i : nullptr;
         }
     }
-    a.stamp = (sc.dbg && !sc.dbg_counts) ? sc.dbg + 64 + 24 * p : nullptr;
     *mode_out = mode;
     *var_out = var;
     return a;
@@ -277,20 +285,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
     const float *W0 = W0_CONST ? nullptr : a.w0 + (size_t)smp * a.w0_stride;
     const float *W1 = (NW == 2) ? a.w1 + (size_t)smp * a.w1_stride : nullptr;
 
-    // debug stamps (100 MHz s_memrealtime) of the first, middle and last workgroup of the launch; a.stamp is null in
-    // normal runs (one predicated-off scalar branch per stamp)
-    unsigned long long tst0 = 0;
-    int *stamp = nullptr;
-    if (a.stamp && threadIdx.x == 0) {
-        const unsigned bx = blockIdx.x, gx = gridDim.x;
-        const int which = bx == 0 ? 0 : bx == gx / 2 ? 1 : bx == gx - 1 ? 2 : -1;
-        if (which >= 0) {
-            stamp = a.stamp + 8 * which;
-            tst0 = __builtin_amdgcn_s_memrealtime();
-            stamp[0] = (int)(tst0 & 0x7fffffff);
-        }
-    }
-#define PCC_ST(k) do { if (stamp) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); stamp[(k)] = (int)(__builtin_amdgcn_s_memrealtime() - tst0); } } while (0)
     // ---- which owners does this workgroup hold? ----
     if (!COWN && tile * TQ >= a.n_own) return;
     // Candidate staging, split in two: the loads of a chunk (one float4 group per thread and row: CH / 4 <= T) and its
@@ -316,7 +310,7 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
         // the owners exhausted since cleared): a thread takes one 32-owner word -- one count, ONE block scan, and the set
         // bits of the word dealt to the tile's slots.  (Until round 3 every workgroup scanned the 2048 remainR floats, 16
         // per thread, and carried the zeros of the exhausted owners into the second remainR buffer: 3-4 us at the head of
-        // each of the six passes, PCC_AM_DEBUG=2 stamps.)
+        // each of the six passes, timed inside the kernel.)
         const int lo = tile * TQ, hi = lo + TQ;
         const unsigned *mk = a.mask_in + (size_t)smp * kLevels * a.mask_words;
         unsigned *mnext = (tile == 0 && a.mask_out) ? a.mask_out + (size_t)smp * kLevels * a.mask_words : nullptr;
@@ -347,7 +341,7 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
         int before = 0, total = 0;
 #pragma unroll
         for (int i = 0; i < S; i++) {
-            const int c = wave_cnt[i];
+            const int c = __builtin_amdgcn_readfirstlane(wave_cnt[i]);  // (uniform: the S counts stay in scalar registers)
             before += i < w ? c : 0;
             total += c;
         }
@@ -364,10 +358,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
             deal(word, tid * 32);
         } else {
             for (int j = tid * wpt; j < min(tid * wpt + wpt, a.mask_words); j++) deal(mk[j], j * 32);
-        }
-        if (a.dbg && tile == 0 && tid == 0) {
-            atomicAdd(&a.dbg[0], a.n_own);
-            atomicAdd(&a.dbg[1], a.n_own - total);
         }
         if (a.clist_cnt && tile == 0 && tid == 0) a.clist_cnt[smp] = total;  // pass C/A stages exactly the live owners
         n_valid = min(TQ, total - lo);
@@ -399,7 +389,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
         if (MODE != PH_A && !a.first) pre_rem = a.remain[(size_t)smp * a.remain_stride + oe];
         if (MODE == PH_CA || MODE == PH_C) pre_ratio = a.ratio_in[(size_t)smp * a.ratio_stride + oe];
     }
-    PCC_ST(1);
     const float4 *X4 = reinterpret_cast<const float4 *>(lds_c);
     const float4 *Y4 = X4 + CH / 4;
     const float4 *Z4 = Y4 + CH / 4;
@@ -453,7 +442,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
         }
         const int nblk = (ngroups + 3) / 4;  // blocks of 16 candidates (4 groups)
         __syncthreads();
-        PCC_ST(3);
         // the S waves take the 16-candidate blocks round-robin
         for (int blk = w; blk < nblk; blk += S) {
             const int g_end = min(blk * 4 + 4, ngroups);
@@ -497,7 +485,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
             }
         }
     }
-    PCC_ST(4);
     if (R == 1) {
         s0[0] += t0x;
         s1[0] += t1x;
@@ -512,7 +499,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
         if (NW == 2) red[(1 * S + w) * PQ + r * 64 + lane] = s1[r];
     }
     __syncthreads();
-    PCC_ST(5);
     if (own_e < 0) return;
     {
         const int e = tid;
@@ -525,14 +511,10 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
             if (NW == 2) t1 += red[(1 * S + s) * PQ + e];
         }
         if (MODE == PH_A) {
-            // ratioL[k] = remainL[k] / (1e-9 + sum)            approxmatch.cu:37,61 (remainL == multiL)
-            a.ratio_out[(size_t)smp * a.ratio_stride + o] = a.multiL / (1e-9f + t0);
+            a.ratio_out[(size_t)smp * a.ratio_stride + o] = pass_a_ratio(a.multiL, t0);  // (remainL == multiL)
         } else if (MODE == PH_B) {
-            // approxmatch.cu:106-109
-            const float rR = a.first ? a.multiR : pre_rem;
-            const float sumr = t0 * rR;
-            const float consumption = __builtin_fminf(rR / (sumr + 1e-9f), 1.0f);
-            const float ratio_new = consumption * rR, remain_new = __builtin_fmaxf(0.0f, rR - sumr);
+            const PassB pb = pass_b(a.first ? a.multiR : pre_rem, t0);
+            const float ratio_new = pb.ratio, remain_new = pb.remain;
             a.ratio_out[(size_t)smp * a.ratio_stride + o] = ratio_new;
             a.remain_out[(size_t)smp * a.remain_stride + o] = remain_new;
             if (a.live_out) {  // owners still live after this level = the owner count of the next pass B
@@ -558,18 +540,11 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
                 cl[(size_t)4 * a.cl_n4] = remain_new;
             }
         } else {
-            // pass C: suml = sum_l e*ratioL[k]*ratioR[l] ; remainL = max(0, remainL - suml)   :154-162
-            float *rem = a.remain + (size_t)smp * a.remain_stride + o;
-            const float rl = pre_ratio;
-            const float rL = a.first ? a.multiL : pre_rem;
-            const float left = __builtin_fmaxf(0.0f, rL - rl * t0);
-            *rem = left;
-            // pass A of the next level: ratioL' = remainL / (1e-9 + sum_l e'*remainR[l])       :37,61
-            if (MODE == PH_CA) a.ratio_out[(size_t)smp * a.ratio_stride + o] = left / (1e-9f + t1);
+            const float left = pass_c_left(a.first ? a.multiL : pre_rem, pre_ratio, t0);
+            a.remain[(size_t)smp * a.remain_stride + o] = left;
+            if (MODE == PH_CA) a.ratio_out[(size_t)smp * a.ratio_stride + o] = pass_a_ratio(left, t1);  // pass A of the next level
         }
     }
-    PCC_ST(6);
-#undef PCC_ST
 }
 
 
@@ -631,6 +606,103 @@ __device__ __forceinline__ float row_sum16(float v) {
     return v;
 }
 
+// The steps of a fine-level pass, one copy for am_fine_kernel (one launch per pass) and am_fine_persist_kernel (levels
+// 0-2 in one launch).  The two kernels keep their own LDS layouts and hand in the row base pointers.  Thread
+// (tg, tb) = (tid / NBLK, tid % NBLK) holds the test of owner group tg of the tile against candidate block tb; wave w
+// walks the block list of group og = w % kFineGroups, share cs = w / kFineGroups of it; lane = (candidate cl of a block,
+// owner quad).
+struct FineOwners {  // the kFineQ owners of a lane: group-local 4 quad .. 4 quad + 3
+    float x[kFineQ], y[kFineQ], z[kFineQ];
+};
+struct FineRows {  // LDS rows of the staged candidates: coordinates, weights of the first / second exponential
+    const float *x, *y, *z, *w0, *w1;
+};
+
+// bounding box of 16-owner group g16 of sample smp (an empty box beyond the cloud: it is near no block)
+__device__ __forceinline__ void fine_group_box(const float *own_box, int own_nb, int smp, int g16, float4 &lo, float4 &hi) {
+    lo = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
+    hi = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), 0.f);
+    if (g16 < own_nb) {
+        const float4 *ob = reinterpret_cast<const float4 *>(own_box + ((size_t)smp * own_nb + g16) * 8);
+        lo = ob[0];
+        hi = ob[1];
+    }
+}
+
+// squared distance between a group's box and the box of a candidate block (cand_box points at its 8 floats)
+__device__ __forceinline__ float fine_box_d2(const float4 &glo, const float4 &ghi, const float *cand_box) {
+    const float4 *cb = reinterpret_cast<const float4 *>(cand_box);
+    const float4 lo = cb[0], hi = cb[1];
+    const float dx = fmaxf(fmaxf(glo.x - hi.x, lo.x - ghi.x), 0.f);
+    const float dy = fmaxf(fmaxf(glo.y - hi.y, lo.y - ghi.y), 0.f);
+    const float dz = fmaxf(fmaxf(glo.z - hi.z, lo.z - ghi.z), 0.f);
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// The surviving blocks of every group, compacted in block order into items[group][] (bit 7: outer_only, the finer level
+// of pass C/A is exactly 0 for the whole pair of boxes) and flagged in need[]: the two waves 2 tg and 2 tg + 1 hold the
+// tests of group tg, wave_cnt[] their counts.  need[] must be free (the previous chunk / pass has staged); ends with a
+// barrier behind which the lists are complete.
+template <int NBLK>
+__device__ __forceinline__ void fine_block_list(bool keep, bool outer_only, int tid, int tg, int tb, int w, int lane,
+                                                int *wave_cnt, unsigned char (*items)[NBLK], unsigned char *need) {
+    if (tid < NBLK) need[tid] = 0;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wave_cnt[w] = __popcll(bal);
+    __syncthreads();
+    const int before = (w & 1) ? wave_cnt[w - 1] : 0;
+    if (keep) {
+        items[tg][before + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned char)(tb | (outer_only ? 128 : 0));  // (tb < 128)
+        need[tb] = 1;  // (same value from every writer)
+    }
+    __syncthreads();
+}
+
+// A wave walks its half (cs) of its group's block list (nitems entries): a lane holds ONE candidate of the block (five
+// scalar LDS reads, 16 distinct addresses per wave) against its four owners in registers -- four independent fma chains.
+template <int NW>
+__device__ __forceinline__ void fine_walk(const FineRows &rows, const unsigned char *list, int nitems, int cs, int cl, float c0,
+                                          float c1, const FineOwners &own, float (&s0)[kFineQ], float (&s1)[kFineQ]) {
+    for (int it = cs; it < nitems; it += 2) {
+        const int item = __builtin_amdgcn_readfirstlane((int)list[it]);
+        const int ci = (item & 127) * kBox + cl;
+        const float x = rows.x[ci], y = rows.y[ci], z = rows.z[ci];
+        if (NW == 2 && (item & 128)) {  // (wave-uniform) beyond the finer level's radius: its terms are exact zeros
+            const float wb = rows.w1[ci];
+#pragma unroll
+            for (int j = 0; j < kFineQ; j++) s1[j] = __builtin_fmaf(fast_exp2(c1 * sq3(x - own.x[j], y - own.y[j], z - own.z[j])), wb, s1[j]);
+            continue;
+        }
+        const float wa = rows.w0[ci];
+        float wb = 0.f;
+        if (NW == 2) wb = rows.w1[ci];
+#pragma unroll
+        for (int j = 0; j < kFineQ; j++) {
+            const float d = sq3(x - own.x[j], y - own.y[j], z - own.z[j]);
+            s0[j] = __builtin_fmaf(fast_exp2(c0 * d), wa, s0[j]);
+            if (NW == 2) s1[j] = __builtin_fmaf(fast_exp2(c1 * d), wb, s1[j]);
+        }
+    }
+}
+
+// the 16 candidate lanes of an owner meet through four butterfly steps (a + b is the same float on both sides, so every
+// lane ends with the same sum); lane cl == 0 of each quad hands the four sums to red[exponential][cs][group-local owner]
+template <int NW>
+__device__ __forceinline__ void fine_reduce(float (&s0)[kFineQ], float (&s1)[kFineQ], float (*red)[2][64], int cs, int cl, int og, int quad) {
+#pragma unroll
+    for (int j = 0; j < kFineQ; j++) {
+        s0[j] = row_sum16(s0[j]);
+        if (NW == 2) s1[j] = row_sum16(s1[j]);
+    }
+    if (cl == 0) {
+#pragma unroll
+        for (int j = 0; j < kFineQ; j++) {
+            red[0][cs][og * kFineOG + quad * kFineQ + j] = s0[j];
+            if (NW == 2) red[1][cs][og * kFineOG + quad * kFineQ + j] = s1[j];
+        }
+    }
+}
+
 template <int MODE, int CH>
 // (<= 64 VGPRs for passes A and B: with their 34 KB of LDS four workgroups -- the 2 x 512 of the two half-batch lanes --
 // then fit a CU together; at 70 VGPRs three fitted, a quarter of every launch's workgroups waited for a slot, and these
@@ -664,28 +736,15 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
     const float *W0 = W0_CONST ? nullptr : a.w0 + (size_t)smp * a.w0_stride;
     const float *W1 = (NW == 2) ? a.w1 + (size_t)smp * a.w1_stride : nullptr;
 
-    // debug stamps as in am_phase_body (PCC_AM_DEBUG=2): [1] owners + boxes loaded, [2] lists built, [3] candidates staged,
-    // [4] walk done, [5] reduced, [6] end
-    unsigned long long tst0 = 0;
-    int *stamp = nullptr;
-    if (a.stamp && threadIdx.x == 0) {
-        const unsigned bx = blockIdx.x, gx = gridDim.x;
-        const int which = bx == 0 ? 0 : bx == gx / 2 ? 1 : bx == gx - 1 ? 2 : -1;
-        if (which >= 0) {
-            stamp = a.stamp + 8 * which;
-            tst0 = __builtin_amdgcn_s_memrealtime();
-            stamp[0] = (int)(tst0 & 0x7fffffff);
-        }
-    }
-#define PCC_STF(k) do { if (stamp) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); stamp[(k)] = (int)(__builtin_amdgcn_s_memrealtime() - tst0); } } while (0)
-    float ox[kFineQ], oy[kFineQ], oz[kFineQ], s0[kFineQ], s1[kFineQ];
+    FineOwners own;
+    float s0[kFineQ], s1[kFineQ];
 #pragma unroll
     for (int j = 0; j < kFineQ; j++) {
         int o = tile * 64 + og * kFineOG + quad * kFineQ + j;
         o = o < a.n_own ? o : a.n_own - 1;
-        ox[j] = O[o];
-        oy[j] = O[a.own_n4 + o];
-        oz[j] = O[2 * a.own_n4 + o];
+        own.x[j] = O[o];
+        own.y[j] = O[a.own_n4 + o];
+        own.z[j] = O[2 * a.own_n4 + o];
         s0[j] = 0.f;
         s1[j] = 0.f;
     }
@@ -698,54 +757,27 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
         if (MODE != PH_A && !a.first) pre_rem = a.remain[(size_t)smp * a.remain_stride + oe];
         if (MODE == PH_CA || MODE == PH_C) pre_ratio = a.ratio_in[(size_t)smp * a.ratio_stride + oe];
     }
-    // box of the owner group this THREAD tests (thread = (group tg, candidate block tb))
+    // box of the owner group this THREAD tests
     const int tg = tid / NBLK, tb = tid - tg * NBLK;
-    float4 glo = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
-    float4 ghi = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), 0.f);
-    {
-        const int g16 = tile * kFineGroups + tg;
-        if (g16 < a.own_nb) {
-            const float4 *ob = reinterpret_cast<const float4 *>(a.own_box16 + ((size_t)smp * a.own_nb + g16) * 8);
-            glo = ob[0];
-            ghi = ob[1];
-        }
-    }
+    float4 glo, ghi;
+    fine_group_box(a.own_box16, a.own_nb, smp, tile * kFineGroups + tg, glo, ghi);
     const float c0 = a.c0, c1 = a.c1, cut2 = a.cut2;
-    PCC_STF(1);
+    const FineRows rows = {lds_c, lds_c + CH, lds_c + 2 * CH, lds_c + 3 * CH, lds_c + 4 * CH};
 
     for (int q0 = 0; q0 < a.n_cand; q0 += CH) {
         const int cnt = min(CH, a.n_cand - q0);
         const int ngroups = (cnt + 3) / 4;
         const int nblk = (ngroups + 3) / 4;
         if (q0) __syncthreads();
-        if (tid < NBLK) need[tid] = 0;
-        // one box test per thread; the surviving blocks of a group are compacted, in order, into its list (the two
-        // waves that hold the flags of a group: 2 tg and 2 tg + 1)
         bool keep = false, outer_only = false;
         if (tb < nblk) {
-            const float4 *cb = reinterpret_cast<const float4 *>(a.cand_box + ((size_t)smp * a.cand_nb + q0 / kBox + tb) * 8);
-            const float4 lo = cb[0], hi = cb[1];
-            const float dx = fmaxf(fmaxf(glo.x - hi.x, lo.x - ghi.x), 0.f);
-            const float dy = fmaxf(fmaxf(glo.y - hi.y, lo.y - ghi.y), 0.f);
-            const float dz = fmaxf(fmaxf(glo.z - hi.z, lo.z - ghi.z), 0.f);
-            const float bd2 = dx * dx + dy * dy + dz * dz;
+            const float bd2 = fine_box_d2(glo, ghi, a.cand_box + ((size_t)smp * a.cand_nb + q0 / kBox + tb) * 8);
             keep = !(bd2 > cut2);  // farther: every exponential of the pair of boxes is exactly 0
             // pass C/A walks the radius of the COARSER level; between the two radii the finer level's exponential is
             // exactly 0 for the whole pair of boxes: such a block is marked and costs one exponential, not two
             outer_only = NW == 2 && bd2 > a.cut2_fine;
         }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[w] = __popcll(bal);
-        __syncthreads();
-        {
-            const int before = (w & 1) ? wave_cnt[w - 1] : 0;
-            if (keep) {
-                items[tg][before + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned char)(tb | (outer_only ? 128 : 0));  // (tb < 128)
-                need[tb] = 1;  // (same value from every writer)
-            }
-        }
-        __syncthreads();
-        PCC_STF(2);
+        fine_block_list<NBLK>(keep, outer_only, tid, tg, tb, w, lane, wave_cnt, items, need);
         {   // stage the blocks some group of this workgroup needs (on the fine levels a fraction of the cloud): the sorted
             // SoA rows and weight rows are padded to a multiple of 4 (zeros), so these are straight float4 copies
             float4 *dst4 = reinterpret_cast<float4 *>(lds_c);
@@ -777,64 +809,21 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
             }
         }
         __syncthreads();
-        PCC_STF(3);
-        // a wave walks its half of the group's block list: a lane holds ONE candidate of the block (five scalar LDS
-        // reads, 16 distinct addresses per wave) against its four owners in registers -- four independent fma chains
-        const int nitems = wave_cnt[2 * og] + wave_cnt[2 * og + 1];
-        for (int it = cs; it < nitems; it += 2) {
-            const int item = __builtin_amdgcn_readfirstlane((int)items[og][it]);
-            const int ci = (item & 127) * kBox + cl;
-            const float x = lds_c[ci], y = lds_c[CH + ci], z = lds_c[2 * CH + ci];
-            if (NW == 2 && (item & 128)) {  // (wave-uniform) beyond the finer level's radius: its terms are exact zeros
-                const float wb = lds_c[4 * CH + ci];
-#pragma unroll
-                for (int j = 0; j < kFineQ; j++) s1[j] = __builtin_fmaf(fast_exp2(c1 * sq3(x - ox[j], y - oy[j], z - oz[j])), wb, s1[j]);
-                continue;
-            }
-            const float wa = lds_c[3 * CH + ci];
-            float wb = 0.f;
-            if (NW == 2) wb = lds_c[4 * CH + ci];
-#pragma unroll
-            for (int j = 0; j < kFineQ; j++) {
-                const float d = sq3(x - ox[j], y - oy[j], z - oz[j]);
-                s0[j] = __builtin_fmaf(fast_exp2(c0 * d), wa, s0[j]);
-                if (NW == 2) s1[j] = __builtin_fmaf(fast_exp2(c1 * d), wb, s1[j]);
-            }
-        }
+        fine_walk<NW>(rows, items[og], wave_cnt[2 * og] + wave_cnt[2 * og + 1], cs, cl, c0, c1, own, s0, s1);
     }
-    PCC_STF(4);
-    // the 16 candidate lanes of an owner meet through four butterfly steps (a + b is the same float on both sides, so
-    // every lane ends with the same sum); lane cl == 0 of each quad hands the four sums to the epilogue
-#pragma unroll
-    for (int j = 0; j < kFineQ; j++) {
-        s0[j] = row_sum16(s0[j]);
-        if (NW == 2) s1[j] = row_sum16(s1[j]);
-    }
-    if (cl == 0) {
-#pragma unroll
-        for (int j = 0; j < kFineQ; j++) {
-            red[0][cs][og * kFineOG + quad * kFineQ + j] = s0[j];
-            if (NW == 2) red[NW - 1][cs][og * kFineOG + quad * kFineQ + j] = s1[j];
-        }
-    }
+    fine_reduce<NW>(s0, s1, red, cs, cl, og, quad);
     __syncthreads();
-    PCC_STF(5);
     if (own_e < 0) return;
     const float sum0 = red[0][0][tid] + red[0][1][tid];
     const float sum1 = NW == 2 ? red[NW - 1][0][tid] + red[NW - 1][1][tid] : 0.f;
     if (MODE == PH_A) {
-        // ratioL[k] = remainL[k] / (1e-9 + sum)            approxmatch.cu:37,61 (remainL == multiL)
-        a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = a.multiL / (1e-9f + sum0);
+        a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = pass_a_ratio(a.multiL, sum0);  // (remainL == multiL)
     } else if (MODE == PH_B) {
-        // approxmatch.cu:106-109
-        const float rR = a.first ? a.multiR : pre_rem;
-        const float sumr = sum0 * rR;
-        const float consumption = __builtin_fminf(rR / (sumr + 1e-9f), 1.0f);
-        const float ratio_new = consumption * rR, remain_new = __builtin_fmaxf(0.0f, rR - sumr);
-        a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = ratio_new;
-        a.remain_out[(size_t)smp * a.remain_stride + own_e] = remain_new;
+        const PassB pb = pass_b(a.first ? a.multiR : pre_rem, sum0);
+        a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = pb.ratio;
+        a.remain_out[(size_t)smp * a.remain_stride + own_e] = pb.remain;
         if (a.live_out) {  // owners still live after this level = the owner count of the next pass B
-            const unsigned long long alive = __ballot(remain_new != 0.f);
+            const unsigned long long alive = __ballot(pb.remain != 0.f);
             if (lane == 0) atomicAdd(&a.live_out[(size_t)smp * kLiveRow], (int)__popcll(alive));
             if (a.mask_out && lane == 0) {  // ... and their bits: this tile's 64 owners are two whole words of the next row
                 unsigned *mo = a.mask_out + (size_t)smp * kLevels * a.mask_words;
@@ -843,15 +832,10 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
             }
         }
     } else {
-        // pass C: suml = sum_l e*ratioL[k]*ratioR[l] ; remainL = max(0, remainL - suml)   :154-162
-        const float rL = a.first ? a.multiL : pre_rem;
-        const float left = __builtin_fmaxf(0.0f, rL - pre_ratio * sum0);
+        const float left = pass_c_left(a.first ? a.multiL : pre_rem, pre_ratio, sum0);
         a.remain[(size_t)smp * a.remain_stride + own_e] = left;
-        // pass A of the next level: ratioL' = remainL / (1e-9 + sum_l e'*remainR[l])       :37,61
-        if (MODE == PH_CA) a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = left / (1e-9f + sum1);
+        if (MODE == PH_CA) a.ratio_out[(size_t)smp * a.ratio_stride + own_e] = pass_a_ratio(left, sum1);  // pass A of the next level
     }
-    PCC_STF(6);
-#undef PCC_STF
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -867,8 +851,8 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
 //     workgroups during this launch) and one or two values per owner are written (agent-scope stores);
 //   * a pass boundary is a per-SAMPLE barrier (one counter per sample in the live-counter row; tiles of a sample get
 //     consecutive block ids of one XCD): no launch, no cache-wide fence.
-// The pair walk, the reductions and the epilogue formulas are am_fine_kernel's, in the same order: the level rows carry
-// the same bits as with one launch per pass (tests/test_gpu_structural.py::test_resident_fine_levels_equal_one_launch_per_pass).
+// The box test, block lists, pair walk, reductions and epilogue formulas are am_fine_kernel's (the same helpers): the
+// level rows carry the same bits as with one launch per pass (tests/test_gpu_structural.py::test_resident_fine_levels_equal_one_launch_per_pass).
 // Residency: a sample's barrier needs its `tiles` workgroups resident together, and the hardware does NOT dispatch
 // workgroups strictly in block-id order (measured: a launch of more workgroups than the chip holds leaves samples
 // half-resident for milliseconds -- B=32 as two 512-workgroup lanes ran 4 ms per call, with barrier time-outs).  So, like
@@ -945,31 +929,20 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
         }
     }
     // ---- once: this lane's owners of both roles, and the box distance of its (group, block) test per direction ----
-    float ox1[kFineQ], oy1[kFineQ], oz1[kFineQ], ox2[kFineQ], oy2[kFineQ], oz2[kFineQ];
+    FineOwners set1, set2;
 #pragma unroll
     for (int j = 0; j < kFineQ; j++) {
         const int o = tile * 64 + og * kFineOG + quad * kFineQ + j;
         const int o1 = min(o, a.n - 1), o2 = min(o, a.m - 1);
-        ox1[j] = S1[o1]; oy1[j] = S1[a.n4 + o1]; oz1[j] = S1[2 * a.n4 + o1];
-        ox2[j] = S2[o2]; oy2[j] = S2[a.m4 + o2]; oz2[j] = S2[2 * a.m4 + o2];
+        set1.x[j] = S1[o1]; set1.y[j] = S1[a.n4 + o1]; set1.z[j] = S1[2 * a.n4 + o1];
+        set2.x[j] = S2[o2]; set2.y[j] = S2[a.m4 + o2]; set2.z[j] = S2[2 * a.m4 + o2];
     }
     const int tg = tid / NBLK, tb = tid - tg * NBLK;
     auto box_d2 = [&](const float *own_box, int own_nb, const float *cand_box, int cand_nb) -> float {
-        float4 glo = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
-        float4 ghi = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), 0.f);
-        const int g16 = tile * kFineGroups + tg;
-        if (g16 < own_nb) {
-            const float4 *ob = reinterpret_cast<const float4 *>(own_box + ((size_t)smp * own_nb + g16) * 8);
-            glo = ob[0];
-            ghi = ob[1];
-        }
+        float4 glo, ghi;
+        fine_group_box(own_box, own_nb, smp, tile * kFineGroups + tg, glo, ghi);
         if (tb >= cand_nb) return __builtin_inff();
-        const float4 *cb = reinterpret_cast<const float4 *>(cand_box + ((size_t)smp * cand_nb + tb) * 8);
-        const float4 lo = cb[0], hi = cb[1];
-        const float dx = fmaxf(fmaxf(glo.x - hi.x, lo.x - ghi.x), 0.f);
-        const float dy = fmaxf(fmaxf(glo.y - hi.y, lo.y - ghi.y), 0.f);
-        const float dz = fmaxf(fmaxf(glo.z - hi.z, lo.z - ghi.z), 0.f);
-        return dx * dx + dy * dy + dz * dz;
+        return fine_box_d2(glo, ghi, cand_box + ((size_t)smp * cand_nb + tb) * 8);
     };
     const float d2_role0 = box_d2(a.box1, a.nb1, a.box2, a.nb2);  // set1 owners against set2 candidate blocks
     const float d2_role1 = box_d2(a.box2, a.nb2, a.box1, a.nb1);  // set2 owners against set1 candidate blocks
@@ -991,21 +964,10 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
         const float c0 = a.c[i], c1 = a.c[MODE == PH_CA ? i + 1 : i];
         const float cut2 = a.cut2[MODE == PH_CA ? i + 1 : i];  // the coarser of the two levels decides what is 0
         const float *P = lds_p[ROLE ? 0 : 1];
-        if (tid < NBLK) need[tid] = 0;
         const float bd2 = ROLE ? d2_role1 : d2_role0;
         const bool keep = tb < nblk && !(bd2 > cut2);
         const bool outer_only = NW == 2 && bd2 > a.cut2[i];  // beyond the finer level's radius (see am_fine_kernel)
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[w] = __popcll(bal);
-        __syncthreads();
-        {
-            const int before = (w & 1) ? wave_cnt[w - 1] : 0;
-            if (keep) {
-                items[tg][before + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned char)(tb | (outer_only ? 128 : 0));
-                need[tb] = 1;
-            }
-        }
-        __syncthreads();
+        fine_block_list<NBLK>(keep, outer_only, tid, tg, tb, w, lane, wave_cnt, items, need);
         // weights of the blocks some group needs
         {
             const float *W0 = MODE == PH_A ? nullptr : MODE == PH_B ? LV + (size_t)i * nm4 : LV + (size_t)i * nm4 + a.n4;
@@ -1024,57 +986,24 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
         float s0[kFineQ], s1[kFineQ];
 #pragma unroll
         for (int j = 0; j < kFineQ; j++) s0[j] = s1[j] = 0.f;
-        const int nitems = wave_cnt[2 * og] + wave_cnt[2 * og + 1];
-        for (int it = cs; it < nitems; it += 2) {
-            const int item = __builtin_amdgcn_readfirstlane((int)items[og][it]);
-            const int ci = (item & 127) * kBox + cl;
-            const float x = P[ci], y = P[CH + ci], z = P[2 * CH + ci];
-            if (NW == 2 && (item & 128)) {  // (wave-uniform; pass C/A only, whose owners are set1)
-                const float wb = lds_w[1][ci];
-#pragma unroll
-                for (int j = 0; j < kFineQ; j++) s1[j] = __builtin_fmaf(fast_exp2(c1 * sq3(x - ox1[j], y - oy1[j], z - oz1[j])), wb, s1[j]);
-                continue;
-            }
-            const float wa = lds_w[0][ci];
-            float wb = 0.f;
-            if (NW == 2) wb = lds_w[1][ci];
-#pragma unroll
-            for (int j = 0; j < kFineQ; j++) {
-                const float d = ROLE ? sq3(x - ox2[j], y - oy2[j], z - oz2[j]) : sq3(x - ox1[j], y - oy1[j], z - oz1[j]);
-                s0[j] = __builtin_fmaf(fast_exp2(c0 * d), wa, s0[j]);
-                if (NW == 2) s1[j] = __builtin_fmaf(fast_exp2(c1 * d), wb, s1[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kFineQ; j++) {
-            s0[j] = row_sum16(s0[j]);
-            if (NW == 2) s1[j] = row_sum16(s1[j]);
-        }
-        if (cl == 0) {
-#pragma unroll
-            for (int j = 0; j < kFineQ; j++) {
-                red[0][cs][og * kFineOG + quad * kFineQ + j] = s0[j];
-                if (NW == 2) red[1][cs][og * kFineOG + quad * kFineQ + j] = s1[j];
-            }
-        }
+        const FineRows rows = {P, P + CH, P + 2 * CH, lds_w[0], lds_w[1]};
+        fine_walk<NW>(rows, items[og], wave_cnt[2 * og] + wave_cnt[2 * og + 1], cs, cl, c0, c1, ROLE ? set2 : set1, s0, s1);
+        fine_reduce<NW>(s0, s1, red, cs, cl, og, quad);
         __syncthreads();
         const int own_e = ROLE ? own2 : own1;
         if (own_e >= 0) {
             const float sum0 = red[0][0][tid] + red[0][1][tid];
             const float sum1 = NW == 2 ? red[1][0][tid] + red[1][1][tid] : 0.f;
             if (MODE == PH_A) {
-                ratL = a.multiL / (1e-9f + sum0);                                       // approxmatch.cu:37,61
+                ratL = pass_a_ratio(a.multiL, sum0);
                 fp_st(LV + own_e, ratL);
             } else if (MODE == PH_B) {
-                const float rR = i == 0 ? a.multiR : remR;                               // approxmatch.cu:106-109
-                const float sumr = sum0 * rR;
-                const float consumption = __builtin_fminf(rR / (sumr + 1e-9f), 1.0f);
-                const float ratio_new = consumption * rR, remain_new = __builtin_fmaxf(0.0f, rR - sumr);
-                fp_st(LV + (size_t)i * nm4 + a.n4 + own_e, ratio_new);
-                fp_st(REM + a.n4 + (size_t)((i + 1) & 1) * a.m4 + own_e, remain_new);
-                remR = remain_new;
+                const PassB pb = pass_b(i == 0 ? a.multiR : remR, sum0);
+                fp_st(LV + (size_t)i * nm4 + a.n4 + own_e, pb.ratio);
+                fp_st(REM + a.n4 + (size_t)((i + 1) & 1) * a.m4 + own_e, pb.remain);
+                remR = pb.remain;
                 if (i == 2) {  // owners still live after level 2 = the owner count of pass B of level 3 (V_COWN)
-                    const unsigned long long alive = __ballot(remain_new != 0.f);
+                    const unsigned long long alive = __ballot(pb.remain != 0.f);
                     if (lane == 0) {
                         atomicAdd(&row[3], (int)__popcll(alive));
                         unsigned *mo = a.live_mask + ((size_t)smp * kLevels + 3) * a.mask_words;  // ... and their bits
@@ -1083,11 +1012,9 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
                     }
                 }
             } else {
-                const float rL = i == 0 ? a.multiL : remL;                               // approxmatch.cu:154-162
-                const float left = __builtin_fmaxf(0.0f, rL - ratL * sum0);
-                fp_st(REM + own_e, left);
-                remL = left;
-                ratL = left / (1e-9f + sum1);                                            // :37,61 of the next level
+                remL = pass_c_left(i == 0 ? a.multiL : remL, ratL, sum0);
+                fp_st(REM + own_e, remL);
+                ratL = pass_a_ratio(remL, sum1);  // pass A of the next level
                 fp_st(LV + (size_t)(i + 1) * nm4 + own_e, ratL);
             }
         }
@@ -1419,7 +1346,7 @@ __device__ __forceinline__ void bitonic_sort(unsigned (&key)[SLOTS], unsigned *l
     // element tid * SLOTS + s sits in slot s of thread tid (a thread's keys are neighbours): the SHORT strides -- the ones
     // every merge repeats -- are exchanges between registers, the middle ones between lanes, and only the three longest
     // strides (6 stages of the 66 at 2048 keys) cross waves through LDS.  (With element tid + 512 s the three strides 64 /
-    // 128 / 256 went through LDS, 12 stages with two barriers each: half of the sort's time by in-kernel stamps.)
+    // 128 / 256 went through LDS, 12 stages with two barriers each: half of the sort's time, timed inside the kernel.)
     constexpr int NPAD = kSortT * SLOTS;
 #pragma unroll
     for (int kk = 2; kk <= NPAD; kk <<= 1) {
@@ -1832,19 +1759,17 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(int parts, const float
 }
 
 // ---------------------------------------------------------------------------------------------------
-// matchcost / matchcostgrad2: "row" kernels.  A workgroup takes RT rows (query points l of set2) of
-// one sample; set1 is staged SoA in LDS chunk by chunk; each wave streams whole rows of match with
-// coalesced float4 loads (1 KiB per wave-instruction).
-//   MODE 0: cost partial  = sum match * sqrt(d2)                         (approxmatch.cu:200-209)
-//   MODE 1: grad2[k,:]    = sum_j match[k,j] (p2_k - p1_j) rsqrt(max(d2,1e-20))   (:239-246)
+// matchcost: "row" kernel.  A workgroup takes RT rows (query points l of set2) of one sample; set1 is
+// staged SoA in LDS chunk by chunk; each wave streams whole rows of match with coalesced float4 loads
+// (1 KiB per wave-instruction).  Cost partial = sum match * sqrt(d2)   (approxmatch.cu:200-209)
 // ---------------------------------------------------------------------------------------------------
 constexpr int kRowRT = 32;  // rows per workgroup -> 8 per wave
 
-template <int MODE, bool VEC, int CH>
+template <bool VEC>
 __global__ __launch_bounds__(256) void am_row_kernel(int n, int m, const float *__restrict__ xyz1,
                                                       const float *__restrict__ xyz2,
                                                       const float *__restrict__ match, float *__restrict__ out) {
-    constexpr int RPW = kRowRT / 4;
+    constexpr int RPW = kRowRT / 4, CH = 2048;  // (set1 points staged per chunk)
     __shared__ __attribute__((aligned(16))) float lds_p[3 * CH];
     __shared__ float lds_red[4];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1857,9 +1782,6 @@ __global__ __launch_bounds__(256) void am_row_kernel(int n, int m, const float *
     const float4 *Y4 = X4 + CH / 4;
     const float4 *Z4 = Y4 + CH / 4;
 
-    float acc[RPW][3];
-#pragma unroll
-    for (int i = 0; i < RPW; i++) acc[i][0] = acc[i][1] = acc[i][2] = 0.f;
     float csum = 0.f;
 
     for (int q0 = 0; q0 < n; q0 += CH) {
@@ -1896,108 +1818,16 @@ __global__ __launch_bounds__(256) void am_row_kernel(int n, int m, const float *
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const float dx = x2 - px[q], dy = y2 - py[q], dz = z2 - pz[q];
-                    const float d = sq3(dx, dy, dz);
-                    if (MODE == 0) {
-                        csum = __builtin_fmaf(mv[q], __builtin_amdgcn_sqrtf(d), csum);
-                    } else {
-                        const float f = mv[q] * __builtin_amdgcn_rsqf(__builtin_fmaxf(d, 1e-20f));
-                        acc[i][0] = __builtin_fmaf(dx, f, acc[i][0]);
-                        acc[i][1] = __builtin_fmaf(dy, f, acc[i][1]);
-                        acc[i][2] = __builtin_fmaf(dz, f, acc[i][2]);
-                    }
+                    csum = __builtin_fmaf(mv[q], __builtin_amdgcn_sqrtf(sq3(dx, dy, dz)), csum);
                 }
             }
         }
     }
-    if (MODE == 0) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) csum += __shfl_down(csum, off, 64);
-        if (lane == 0) lds_red[w] = csum;
-        __syncthreads();
-        if (tid == 0) out[(size_t)smp * gridDim.x + blockIdx.x] = ((lds_red[0] + lds_red[1]) + lds_red[2]) + lds_red[3];
-    } else {
-#pragma unroll
-        for (int i = 0; i < RPW; i++) {
-            const int row = r0 + w + 4 * i;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                float v = acc[i][c];
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-                if (lane == 0 && row < m) out[((size_t)smp * m + row) * 3 + c] = v;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// matchcostgrad1: "column" kernel.  grad1[l,:] = sum_k match[k,l] (p1_l - p2_k) rsqrt(max(d2,1e-20))
-// (approxmatch.cu:277-285).  A lane owns 4 consecutive columns l; the rows k are split RS ways over
-// workgroups and 4 ways over waves; partial sums go to a workspace and are added in a fixed order.
-// ---------------------------------------------------------------------------------------------------
-template <bool VEC>
-__global__ __launch_bounds__(256) void am_col_kernel(int n, int m, int rs, const float *__restrict__ xyz1,
-                                                      const float *__restrict__ xyz2,
-                                                      const float *__restrict__ match, float *__restrict__ part) {
-    __shared__ float red[3][4][64 * 3];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int smp = blockIdx.z;
-    const int split = blockIdx.y;
-    const int k0 = blockIdx.x * 256 + lane * 4;
-    const float *p1 = xyz1 + (size_t)smp * n * 3;
-    const float *p2 = xyz2 + (size_t)smp * m * 3;
-    const int rbeg = (int)((long long)m * split / rs), rend = (int)((long long)m * (split + 1) / rs);
-    float x1[4], y1[4], z1[4], g[4][3];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        int k = k0 + q;
-        k = k < n ? k : n - 1;
-        x1[q] = p1[k * 3 + 0];
-        y1[q] = p1[k * 3 + 1];
-        z1[q] = p1[k * 3 + 2];
-        g[q][0] = g[q][1] = g[q][2] = 0.f;
-    }
-    for (int row = rbeg + w; row < rend; row += 4) {
-        const float x2 = p2[row * 3 + 0], y2 = p2[row * 3 + 1], z2 = p2[row * 3 + 2];
-        const float *mrow = match + ((size_t)smp * m + row) * n;
-        float mv[4];
-        if (VEC && k0 + 3 < n) {
-            const float4 t = *reinterpret_cast<const float4 *>(mrow + k0);
-            mv[0] = t.x; mv[1] = t.y; mv[2] = t.z; mv[3] = t.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) mv[q] = (k0 + q < n) ? mrow[k0 + q] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float dx = x1[q] - x2, dy = y1[q] - y2, dz = z1[q] - z2;
-            const float f = mv[q] * __builtin_amdgcn_rsqf(__builtin_fmaxf(sq3(dx, dy, dz), 1e-20f));
-            g[q][0] = __builtin_fmaf(dx, f, g[q][0]);
-            g[q][1] = __builtin_fmaf(dy, f, g[q][1]);
-            g[q][2] = __builtin_fmaf(dz, f, g[q][2]);
-        }
-    }
-    // merge the 4 waves (fixed order), then store this split's partial [b][split][n][3]
-    if (w > 0) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) red[w - 1][q][lane * 3 + c] = g[q][c];
-    }
+    for (int off = 32; off > 0; off >>= 1) csum += __shfl_down(csum, off, 64);
+    if (lane == 0) lds_red[w] = csum;
     __syncthreads();
-    if (w == 0) {
-        float *dst = part + (((size_t)smp * rs + split) * n) * 3;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (k0 + q >= n) continue;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const float v = ((g[q][c] + red[0][q][lane * 3 + c]) + red[1][q][lane * 3 + c]) + red[2][q][lane * 3 + c];
-                dst[(size_t)(k0 + q) * 3 + c] = v;
-            }
-        }
-    }
+    if (tid == 0) out[(size_t)smp * gridDim.x + blockIdx.x] = ((lds_red[0] + lds_red[1]) + lds_red[2]) + lds_red[3];
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2186,7 +2016,6 @@ struct PairArgs {
     float *part1;               // [b][row_tiles][n4][3]   column sums (grad1, sorted space)
     float *part2;               // [b][col_blocks][m4][3]  row sums    (grad2, sorted space)
     int col_blocks, row_tiles, bc;  // 1-D grid of col_blocks * row_tiles * bc workgroups (see the kernel)
-    int plain_order;
 };
 
 template <int Q, bool GRAD>
@@ -2208,8 +2037,7 @@ __global__ __launch_bounds__(256) void am_pair_kernel(PairArgs a) {
     const int shift_k = item / cbn, cblk = item - shift_k * cbn;
     const int base_r = (int)(((long long)(2 * cblk + 1) * rtn) / (2 * cbn));
     const int shift = ((shift_k + 1) >> 1) * ((shift_k & 1) ? 1 : -1);  // 0, +1, -1, +2, ... : a complete residue system mod rtn
-    int rtile = ((base_r + shift) % rtn + rtn) % rtn;
-    if (a.plain_order) rtile = shift_k;  // (A/B switch 1: row tiles in index order)
+    const int rtile = ((base_r + shift) % rtn + rtn) % rtn;
     const int l0 = rtile * kPairRT;
     const int kb = cblk * 64 * Q;
     const int k0 = kb + lane * Q;
@@ -2685,14 +2513,14 @@ int sort_clouds(int b, const WsLayout &L, int n, int m, const float *xyz1, const
 // while the first half runs on the caller's stream, so that one half's kernels fill the launch / drain bubbles of
 // the other's (each launch is a chain link of ~20 us with 4-8 us of fixed cost).  Fork and join are events on the
 // caller's stream: for the caller the call still is "enqueue on `stream`, no host synchronisation".
-constexpr int kMaxLanes = 4;
-hipStream_t side_stream(int which) {  // which = 0 .. kMaxLanes - 2
+constexpr int kMaxLanes = 2;
+hipStream_t side_stream() {
     static std::mutex mu;
-    static hipStream_t streams[64][kMaxLanes - 1] = {};
+    static hipStream_t streams[64] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || which < 0 || which >= kMaxLanes - 1) return nullptr;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
-    if (!streams[dev][which]) {
+    if (!streams[dev]) {
         // HIP multiplexes the streams of a process onto a few hardware queues per PRIORITY class, in creation order: a
         // plain side stream created after an application has made many streams of its own (RCCL does, at
         // init_process_group) can land on the hardware queue of the caller's stream, and the two lanes then serialise
@@ -2703,46 +2531,39 @@ hipStream_t side_stream(int which) {  // which = 0 .. kMaxLanes - 2
             (void)hipGetLastError();
             least = greatest = 0;
         }
-        if (hipStreamCreateWithPriority(&streams[dev][which], hipStreamNonBlocking, greatest) != hipSuccess) {
+        if (hipStreamCreateWithPriority(&streams[dev], hipStreamNonBlocking, greatest) != hipSuccess) {
             (void)hipGetLastError();
-            if (hipStreamCreateWithFlags(&streams[dev][which], hipStreamNonBlocking) != hipSuccess) {
-                streams[dev][which] = nullptr;
+            if (hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking) != hipSuccess) {
+                streams[dev] = nullptr;
                 (void)hipGetLastError();
             }
         }
     }
-    return streams[dev][which];
+    return streams[dev];
 }
 
-struct ForkJoin {  // the side streams wait for everything enqueued on main so far; at scope exit main waits for them
-    hipStream_t main, side[kMaxLanes - 1] = {};
-    int nside = 0;
-    bool ok = false;
-    ForkJoin(hipStream_t m, int want) : main(m) {
-        if (want <= 0) return;
+struct ForkJoin {  // the side stream waits for everything enqueued on main so far; at scope exit main waits for it
+    hipStream_t main, side = nullptr;
+    ForkJoin(hipStream_t m, bool fork) : main(m) {
+        if (!fork) return;
         hipEvent_t ev;
         if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return;
         if (hipEventRecord(ev, main) == hipSuccess) {
-            for (int i = 0; i < want && i < kMaxLanes - 1; i++) {
-                hipStream_t s = side_stream(i);
-                if (!s || hipStreamWaitEvent(s, ev, 0) != hipSuccess) break;
-                side[nside++] = s;
-            }
+            hipStream_t s = side_stream();
+            if (s && hipStreamWaitEvent(s, ev, 0) == hipSuccess) side = s;
         }
         (void)hipEventDestroy(ev);  // released once the recorded work has completed
-        ok = nside > 0;
     }
     ~ForkJoin() {
-        for (int i = 0; i < nside; i++) {
-            hipEvent_t ev;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-                (void)hipStreamSynchronize(side[i]);  // cannot order the streams any other way
-                continue;
-            }
-            (void)hipEventRecord(ev, side[i]);
-            (void)hipStreamWaitEvent(main, ev, 0);
-            (void)hipEventDestroy(ev);
+        if (!side) return;
+        hipEvent_t ev;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipStreamSynchronize(side);  // cannot order the streams any other way
+            return;
         }
+        (void)hipEventRecord(ev, side);
+        (void)hipStreamWaitEvent(main, ev, 0);
+        (void)hipEventDestroy(ev);
     }
 };
 
@@ -2793,7 +2614,7 @@ static bool resident_enabled() {  // measurement switch (pcc_test_hooks.h): one 
 // the seven fine-level passes of the samples of `sc` as one resident launch; returns -1 when the device / the sizes do
 // not qualify (the caller then runs one launch per pass)
 int launch_fine_resident(const Sched &sc, int bc, hipStream_t st) {
-    if (!sc.skip || !sc.live_cnt || !sc.live_mask || sc.dbg || !resident_enabled()) return -1;
+    if (!sc.skip || !sc.live_cnt || !sc.live_mask || !resident_enabled()) return -1;
     if (sc.n > kFpCH || sc.m > kFpCH || sc.n < 1 || sc.m < 1) return -1;
     const int tiles = pcc::ceil_div(std::max(sc.n, sc.m), 64);
     FinePersistArgs a{};
@@ -2842,18 +2663,6 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
     const long long nm4 = (long long)L.n4 + L.m4;  // sorted-space level row: ratioL (n4) | ratioR (m4)
     const long long rs = (long long)L.n4 + 2LL * L.m4;  // remain row: remainL (n4) | remainR ping (m4) | pong (m4)
 
-    static int *dbg_counters = [] {
-        int *p = nullptr;
-        const char *e = std::getenv("PCC_AM_DEBUG");
-        if (e && (e[0] == '1' || e[0] == '2') && hipMalloc(reinterpret_cast<void **>(&p), kDbgInts * sizeof(int)) == hipSuccess)
-            (void)hipMemset(p, 0, kDbgInts * sizeof(int));
-        return p;
-    }();
-    static const int dbg_counts = [] {
-        const char *e = std::getenv("PCC_AM_DEBUG");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
-
     const bool split_enabled = pcc::tuning(PCC_TUNE_AM_NOSPLIT) == 0;  // (measurement switch: everything on the caller's stream)
 
     // Lanes: disjoint sample ranges that run the same schedule on different streams.  Two lanes when each half still
@@ -2865,27 +2674,24 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
         Sched sc;
     };
     Lane lanes[kMaxLanes];
-    int nlanes = 1, want_side = 0;
-    if (split_enabled && !dbg_counters && b >= 8 && (long long)b * std::max(n, m) >= 32768) {
+    int nlanes = 1;
+    bool fork = false;
+    if (split_enabled && b >= 8 && (long long)b * std::max(n, m) >= 32768) {
         // not while the caller's stream is being captured into a graph: the capture stays a single-stream chain
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
             (void)hipGetLastError();
             cap = hipStreamCaptureStatusNone;
         }
-        if (cap == hipStreamCaptureStatusNone) {
-            want_side = 1;
-            const int t = pcc::tuning(PCC_TUNE_AM_LANES);  // (measurement switch: lane count)
-            if (t >= 1 && t <= kMaxLanes) want_side = t - 1;
-        }
+        fork = cap == hipStreamCaptureStatusNone;
     }
-    ForkJoin fj(st, want_side);
-    if (fj.ok) nlanes = 1 + fj.nside;
+    ForkJoin fj(st, fork);
+    if (fj.side) nlanes = 2;
     for (int l = 0; l < nlanes; l++) {
         Lane &ln = lanes[l];
         ln.s0 = (int)((long long)b * l / nlanes);
         ln.bc = (int)((long long)b * (l + 1) / nlanes) - ln.s0;
-        ln.st = l == 0 ? st : fj.side[l - 1];
+        ln.st = l == 0 ? st : fj.side;
         const size_t s0 = (size_t)ln.s0;
         Sched &sc = ln.sc;
         sc = Sched{};
@@ -2899,8 +2705,6 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
         sc.multiL = multiL; sc.multiR = multiR;
         sc.skip = cull_enabled() ? 1 : 0;
         sc.lc = lc;
-        sc.dbg = l == 0 ? dbg_counters : nullptr;
-        sc.dbg_counts = dbg_counts;
         {
             sc.clist = reinterpret_cast<float *>(base + L.clist) + s0 * 5 * L.m4;
             sc.clist_cnt = reinterpret_cast<int *>(base + L.clist_cnt) + s0;
@@ -2909,7 +2713,6 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
         if (sc.skip) sc.live_mask = reinterpret_cast<unsigned *>(base + L.live_mask) + s0 * kLevels * mask_words(L.m4);
     }
     int rc = PCC_OK;
-    const bool nn_all_at_head = pcc::tuning(PCC_TUNE_NN_HEAD) != 0;  // (measurement switch)
     auto enqueue_head = [&](int l) -> int {
         const Lane &ln = lanes[l];
         const size_t s0 = (size_t)ln.s0;
@@ -2925,9 +2728,9 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
         // work that only needs the sorted clouds of this lane's samples (pcc_chamfer_emd: the nearest-neighbour search).
         // Even lanes run it here, odd lanes behind their passes: two searches at the same moment halve each other (each
         // wants every SIMD); against the other lane's pass chain a search costs less (chamfer_emd 447.7 -> 440.4 us, step
-        // 470 -> 462.6 us, tools/ab_nn.py; before passes 3 / 7 / 11 / 15 of the odd lane: 451 / 445 / 445 / 445 us; on a
+        // 470 -> 462.6 us; before passes 3 / 7 / 11 / 15 of the odd lane: 451 / 445 / 445 / 445 us; on a
         // stream of its own: 522 us).
-        if (!r && after_sort && (l % 2 == 0 || nn_all_at_head)) r = after_sort(ln.s0, ln.bc, ln.st);
+        if (!r && after_sort && l % 2 == 0) r = after_sort(ln.s0, ln.bc, ln.st);
         return r;
     };
     auto enqueue_pass = [&](int l, int p) -> int {
@@ -2962,33 +2765,13 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
         }
         // what follows the passes for one lane's samples (the implicit path's pair + finish kernels) goes on that lane's
         // stream: the lane that finishes its passes first starts at once instead of waiting for the join
-        if (after_sort && !nn_all_at_head)
+        if (after_sort)
             for (int l = 1; l < nlanes; l += 2)
                 if (int rc2 = after_sort(lanes[l].s0, lanes[l].bc, lanes[l].st)) return rc2;
         if (lane_tail) {
             for (int l = 0; l < nlanes; l++)
                 if (int rc2 = lane_tail(lanes[l].s0, lanes[l].bc, lanes[l].st)) return rc2;
         }
-    }
-    if (dbg_counters) {
-        static int h[kDbgInts];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbg_counters, sizeof h, hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "[pcc dbg] A: %d/%d skipped;", h[1], h[0]);
-        for (int i = 0; i < kLevels; i++) std::fprintf(stderr, " B%d %d/%d CA%d %d/%d;", i, h[3 + 4 * i], h[2 + 4 * i], i, h[5 + 4 * i], h[4 + 4 * i]);
-        if (!dbg_counts) {
-            std::fprintf(stderr, "\n[pcc dbg] phase stamps x10ns (first | middle | last workgroup): start-after-first [prologue loads staged loop reduced end]");
-            for (int q = 0; q < sched_phases(); q++) {
-                const int *s = h + 64 + 24 * q;
-                std::fprintf(stderr, "\n[pcc dbg]  p%02d", q);
-                for (int k = 0; k < 3; k++) {
-                    const int *t = s + 8 * k;
-                    std::fprintf(stderr, " | +%d [%d %d %d %d %d %d]", (t[0] - s[0]) & 0x7fffffff, t[1], t[2], t[3], t[4], t[5], t[6]);
-                }
-            }
-        }
-        std::fprintf(stderr, "\n");
-        (void)hipMemset(dbg_counters, 0, sizeof h);
     }
     return PCC_OK;
 }
@@ -3071,7 +2854,6 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
         pa.part1 = grad ? reinterpret_cast<float *>(base + part1_off) + o * row_tiles * L.n4 * 3 : nullptr;
         pa.part2 = grad ? reinterpret_cast<float *>(base + part2_off) + o * col_blocks * L.m4 * 3 : nullptr;
         pa.col_blocks = col_blocks; pa.row_tiles = row_tiles; pa.bc = bc;
-        pa.plain_order = pcc::tuning(PCC_TUNE_PAIR_PLAIN_ORDER);
         if ((long long)col_blocks * row_tiles * bc > 0x7fffffffLL) return pcc::invalid("match_cost: grid too large");
         const dim3 grid((unsigned)(col_blocks * row_tiles * bc));
         if (int rc = launch_pair<q_cols>(pa, grid, grad, lst)) return rc;
@@ -3249,8 +3031,8 @@ int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, con
     const bool vec = (n % 4 == 0) && aligned16(match);
     {
         pcc::ProfScope prof("am_row_kernel<cost>", st);
-        if (vec) hipLaunchKernelGGL((am_row_kernel<0, true, 2048>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
-        else hipLaunchKernelGGL((am_row_kernel<0, false, 2048>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
+        if (vec) hipLaunchKernelGGL((am_row_kernel<true>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
+        else hipLaunchKernelGGL((am_row_kernel<false>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
     }
     if (int rc = pcc::check_launch("matchcost")) return rc;
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(b), dim3(256), 0, st, tiles, part, out);
