@@ -32,9 +32,11 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
  * barrier times out -- a workgroup of the sample was never scheduled -- the kernel poisons its outputs (dist = NaN,
  * unassigned points keep assignment -1) and raises a sticky per-device word.  The NEXT pcc_auction_forward /
  * pcc_auction_backward on that device returns PCC_EINVAL with a message instead of starting, and
- * pcc_auction_status() returns 1 (each of them clears the word).  Launches are asynchronous: synchronise the stream
- * before asking.  Cluster launches issued on different streams are ordered one after the other by an event, so two of
- * them never compete for residency.  (The reporting path is exercised through include/pcc_test_hooks.h.) */
+ * pcc_auction_status() returns 1 (each of them clears the word); the call after that runs normally.  Launches are
+ * asynchronous: synchronise the stream before asking.  A co-resident launch -- of this kind or the approximate EMD's
+ * (pcc_structural.h) -- issued on another stream waits for the previous one, so two of them never compete for
+ * residency.  While the stream is being captured into a graph the one-workgroup schedule runs instead (same bits).
+ * (The reporting path is exercised through include/pcc_test_hooks.h.) */
 int pcc_auction_status(void);
 
 /* emd_cuda_backward (emd_cuda.cu:283-315): grad_xyz1[b,n,3] = 2 grad_dist (xyz1 - xyz2[assignment]); overwritten.

@@ -113,7 +113,9 @@ int pcc_chamfer_emd_grad(int b, int n, const float *xyz1, int m, const float *xy
  *   [remainL(n) | remainR(m) | ratioL(n) | ratioR(m)] after the last level.
  * The reference-named form allocates its per-level workspace with hipMallocAsync on `stream`;
  * pcc_approxmatch_ws takes a caller-provided workspace of pcc_approxmatch_workspace_bytes(b,n,m)
- * bytes instead (graph-capture friendly, no allocation in the call). */
+ * bytes instead (graph-capture friendly, no allocation in the call).
+ * Failure: if a sample barrier of the resident launch of levels 0-2 times out, that sample's match and temp are NaN and
+ * the next approximate-EMD call on the device (any entry point here) returns PCC_EINVAL ("did not complete"). */
 void approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                  pcc_stream_t stream);
 int pcc_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
@@ -125,7 +127,7 @@ int pcc_approxmatch_ws(int b, int n, int m, const float *xyz1, const float *xyz2
 /* approxmatch + matchcost in one call (what the Python-level match_cost forward needs,
  * reference structural_losses/match_cost.py:25-27): the pass that materialises `match` also
  * accumulates cost[b], so `match` is not re-read.  Same results as pcc_approxmatch + pcc_matchcost up to
- * float summation order. */
+ * float summation order.  Failure as for pcc_approxmatch: NaN match, temp and cost for the sample. */
 int pcc_approxmatch_cost(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                          float *cost, pcc_stream_t stream);
 
@@ -160,7 +162,7 @@ int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float
  *   grad_cost[b] or NULL (= 1).
  * Non-finite coordinates: a NaN propagates through the distances as in the reference; a sample with an infinite
  * coordinate returns NaN cost and NaN gradients (the reference's 0 * sqrt(inf), approxmatch.cu:207,247-248), the other
- * samples of the batch are unaffected. */
+ * samples of the batch are unaffected.  Failure as for pcc_approxmatch: NaN cost and gradients for the sample. */
 int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost, float *cost,
                    float *grad1, float *grad2, pcc_stream_t stream);
 

@@ -11,9 +11,14 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default)
 
-/* Makes the next cluster launch of pcc_auction_forward on the current device start with its error word raised, as if
- * a sample barrier had timed out: exercises the failure-reporting path of pcc_emd.h.  Returns 1 when armed. */
+/* Make the next co-resident launch on the current device -- the cluster launch of pcc_auction_forward, resp. the
+ * approximate EMD's resident launch of levels 0-2 (batch x tiles <= CUs) -- fail as if a sample barrier had timed out.
+ * They exercise the one failure contract of pcc_emd.h and pcc_structural.h: the launch's outputs come out NaN for the
+ * failed samples, and the next call of that kind on the device returns PCC_EINVAL ("did not complete") instead of
+ * starting.  A call that runs no such launch (the batch, the sizes or a stream capture rule it out) leaves the request
+ * pending.  Return 1 when armed. */
 int pcc_test_inject_auction_failure(void);
+int pcc_test_inject_approxmatch_failure(void);
 
 /* A/B switches of the measurement scripts under tools/ and of the bit-identity tests (value 0 = the product's
  * behaviour).  They replace the PCC_* environment variables earlier rounds read inside the product library: nothing

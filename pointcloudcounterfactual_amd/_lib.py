@@ -73,6 +73,7 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_auction_backward': (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/pcc_test_hooks.h (inert without PCC_TEST_HOOKS=1)
     'pcc_test_inject_auction_failure': (_int, []),
+    'pcc_test_inject_approxmatch_failure': (_int, []),
     'pcc_test_set_tuning': (_int, [_int, _int]),
 }
 

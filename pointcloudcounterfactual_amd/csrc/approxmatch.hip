@@ -858,9 +858,9 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
 // half-resident for milliseconds -- B=32 as two 512-workgroup lanes ran 4 ms per call, with barrier time-outs).  So, like
 // the auction's cluster kernel, the host uses this form only when the WHOLE launch fits the device with room to spare
 // (batch x tiles <= compute units while two workgroups fit a CU: b <= 8 at N = 2048, the reference's default
-// per-device batch, default_train.yaml:6) and never lets two of these launches run at the same time (an event orders
-// them across streams).  Spins are bounded all the same: a barrier that times out raises the sample's error slot (the
-// finish kernel then reports NaN for the sample) and a sticky host word (the next call on the device fails) instead
+// per-device batch, default_train.yaml:6), and a pcc::CoresidentGate keeps every other co-resident launch off the device
+// meanwhile.  Spins are bounded all the same: a barrier that times out raises the sample's error slot (the
+// finish and unpermute kernels then report NaN for the sample) and a sticky host word (the next call on the device fails) instead
 // of hanging.  Measured (N=2048, b=8): 68 us against 91 us for the seven launches -- the passes are bound by the
 // latency of one workgroup's own work (list, weights, walk, reduction: ~10 us), not by the launch boundary.
 // ---------------------------------------------------------------------------------------------------
@@ -878,11 +878,9 @@ struct FinePersistArgs {
     int *live_cnt;                 // [b][kLiveRow]
     unsigned *live_mask;           // [b][kLevels][mask_words] (row 3 is written here: PhaseArgs::mask_out)
     int mask_words;
-    unsigned *host_err;            // sticky word in mapped host memory (or null)
+    unsigned *host_err;            // sticky word in mapped host memory (pcc::CoresidentGate)
+    int inject;                    // test hook: every sample fails at its first barrier
 };
-
-__device__ __forceinline__ float fp_ld(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void fp_st(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersistArgs a) {
     constexpr int T = 64 * kFineS, CH = kFpCH, NBLK = CH / kBox;
@@ -893,7 +891,6 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
     __shared__ unsigned char items[kFineGroups][NBLK];
     __shared__ unsigned char need[NBLK];
     __shared__ int wave_cnt[kFineS];
-    __shared__ int bar_failed;
 
     const int lid = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     const int smp = lid / a.tiles;
@@ -950,7 +947,6 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
     const int own1 = (tid < 64 && tile * 64 + tid < a.n) ? tile * 64 + tid : -1;
     const int own2 = (tid < 64 && tile * 64 + tid < a.m) ? tile * 64 + tid : -1;
     float remL = 0.f, ratL = 0.f, remR = 0.f;
-    if (tid == 0) bar_failed = 0;
     unsigned arrivals = 0;
     bool ok = true;
 
@@ -976,8 +972,8 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
                 if (!need[idx >> 4]) continue;
                 float v0, v1 = 0.f;
                 if (MODE == PH_A) v0 = idx < n_cand ? a.multiR : 0.f;
-                else v0 = idx < cand_n4 ? fp_ld(W0 + idx) : 0.f;
-                if (NW == 2) v1 = idx < cand_n4 ? fp_ld(W1 + idx) : 0.f;
+                else v0 = idx < cand_n4 ? pcc::agent_ld(W0 + idx) : 0.f;
+                if (NW == 2) v1 = idx < cand_n4 ? pcc::agent_ld(W1 + idx) : 0.f;
                 lds_w[0][idx] = v0;
                 if (NW == 2) lds_w[1][idx] = v1;
             }
@@ -996,11 +992,11 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
             const float sum1 = NW == 2 ? red[1][0][tid] + red[1][1][tid] : 0.f;
             if (MODE == PH_A) {
                 ratL = pass_a_ratio(a.multiL, sum0);
-                fp_st(LV + own_e, ratL);
+                pcc::agent_st(LV + own_e, ratL);
             } else if (MODE == PH_B) {
                 const PassB pb = pass_b(i == 0 ? a.multiR : remR, sum0);
-                fp_st(LV + (size_t)i * nm4 + a.n4 + own_e, pb.ratio);
-                fp_st(REM + a.n4 + (size_t)((i + 1) & 1) * a.m4 + own_e, pb.remain);
+                pcc::agent_st(LV + (size_t)i * nm4 + a.n4 + own_e, pb.ratio);
+                pcc::agent_st(REM + a.n4 + (size_t)((i + 1) & 1) * a.m4 + own_e, pb.remain);
                 remR = pb.remain;
                 if (i == 2) {  // owners still live after level 2 = the owner count of pass B of level 3 (V_COWN)
                     const unsigned long long alive = __ballot(pb.remain != 0.f);
@@ -1013,46 +1009,28 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
                 }
             } else {
                 remL = pass_c_left(i == 0 ? a.multiL : remL, ratL, sum0);
-                fp_st(REM + own_e, remL);
+                pcc::agent_st(REM + own_e, remL);
                 ratL = pass_a_ratio(remL, sum1);  // pass A of the next level
-                fp_st(LV + (size_t)(i + 1) * nm4 + own_e, ratL);
+                pcc::agent_st(LV + (size_t)(i + 1) * nm4 + own_e, ratL);
             }
         }
     };
-    // sample barrier: every wave's agent-scope stores have left the CU, then one arrival per workgroup
-    auto sample_barrier = [&]() -> bool {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+    // pcc::coresident_barrier; the failure code for the host: 1 | barrier << 4 | arrivals seen << 8 | sample << 20
+    auto barrier = [&]() -> bool {
         arrivals += (unsigned)a.tiles;
-        if (tid == 0) {
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned spins = 0;
-            while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < arrivals) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 22) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    const unsigned seen = __hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned was = __hip_atomic_exchange(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    // diagnosis for the host: 1 | barrier << 4 | arrivals seen << 8 | sample << 20 (first reporter wins)
-                    if (a.host_err && !was) {
-                        unsigned expected = 0;
-                        __hip_atomic_compare_exchange_strong(a.host_err, &expected, 1u | ((arrivals / (unsigned)a.tiles) << 4) | ((seen & 0xfffu) << 8) | ((unsigned)smp << 20),
-                                                             __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    bar_failed = 1;
-                    break;
-                }
-            }
-        }
-        __syncthreads();
-        return bar_failed == 0;
+        return pcc::coresident_barrier<1, (1u << 22)>(bar, arrivals, err, a.host_err, [&] {
+            const unsigned seen = pcc::agent_ld(bar);
+            return 1u | ((arrivals / (unsigned)a.tiles) << 4) | ((seen & 0xfffu) << 8) | ((unsigned)smp << 20);
+        });
     };
-    __syncthreads();  // clouds staged, bar_failed initialised
+    if (a.inject && tile == 0 && tid == 0) pcc::coresident_fail(err, a.host_err, 1u | ((unsigned)smp << 20));
+    __syncthreads();  // clouds staged
     pass(std::integral_constant<int, PH_A>{}, 0);
     for (int i = 0; i < 3 && ok; i++) {
-        ok = sample_barrier();
+        ok = barrier();
         if (!ok) break;
         pass(std::integral_constant<int, PH_B>{}, i);
-        ok = sample_barrier();
+        ok = barrier();
         if (!ok) break;
         pass(std::integral_constant<int, PH_CA>{}, i);
     }
@@ -1608,12 +1586,15 @@ __global__ __launch_bounds__(kSortT) void am_sort_kernel(SortArgs a) {
 
 // The phases run in Hilbert-sorted index space; this puts the nine (ratioL | ratioR) level vectors back into
 // the caller's point order for the materialise pass (contiguous loads there) and fills
-// temp = remainL | remainR | ratioL | ratioR of the last level (approxmatch.cu:4).
+// temp = remainL | remainR | ratioL | ratioR of the last level (approxmatch.cu:4).  A sample whose resident fine-level
+// passes did not complete (kErrSlot of its live-counter row, am_fine_persist_kernel) gets NaN rows, hence NaN match and
+// cost, as on the implicit path.
 __global__ __launch_bounds__(256) void am_unpermute_kernel(int n, int m, int n4, int m4,
                                                             const float *__restrict__ lv_sorted,
                                                             const float *__restrict__ rem_sorted,
                                                             const int *__restrict__ rank1,
                                                             const int *__restrict__ rank2,
+                                                            const int *__restrict__ flags,
                                                             float *__restrict__ lv, float *__restrict__ temp) {
     // sorted-space rows are [ratioL (n4) | ratioR (m4)] (16-byte aligned halves); outputs are dense [n | m]
     const int smp = blockIdx.y;
@@ -1623,15 +1604,16 @@ __global__ __launch_bounds__(256) void am_unpermute_kernel(int n, int m, int n4,
     const size_t nm = (size_t)n + m, nm4 = (size_t)n4 + m4;
     const float *src = lv_sorted + (size_t)smp * kLevels * nm4;
     float *dst = lv + (size_t)smp * kLevels * nm;
+    const bool failed = flags[(size_t)smp * kLiveRow + kErrSlot] != 0;
     float last = 0.f;
 #pragma unroll
     for (int l = 0; l < kLevels; l++) {
-        last = src[(size_t)l * nm4 + s];
+        last = failed ? __builtin_nanf("") : src[(size_t)l * nm4 + s];
         dst[(size_t)l * nm + i] = last;
     }
     // remain row: remainL (n4) | remainR ping (m4) | pong (m4); the nine passes B leave the final remainR in pong
     float *tb = temp + (size_t)smp * 2 * nm;
-    tb[i] = rem_sorted[(size_t)smp * (nm4 + m4) + (i < n ? s : s + m4)];
+    tb[i] = failed ? __builtin_nanf("") : rem_sorted[(size_t)smp * (nm4 + m4) + (i < n ? s : s + m4)];
     tb[nm + i] = last;
 }
 
@@ -2567,47 +2549,6 @@ struct ForkJoin {  // the side stream waits for everything enqueued on main so f
     }
 };
 
-// Per-device state of the resident fine-level launch (am_fine_persist_kernel): a sticky failure word in mapped host
-// memory, the event of the last such launch (two of them never run at the same time: a launch on another stream first
-// waits for the previous one) and whether the device holds enough workgroups of the kernel at once.
-struct ResidentState {
-    unsigned *host_word = nullptr, *dev_word = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    int wg_per_cu = -1, cus = 0;  // resident workgroups of am_fine_persist_kernel per CU (-1: not asked yet), compute units
-};
-std::mutex g_resident_mu;
-ResidentState *resident_state() {  // (call with g_resident_mu held)
-    static ResidentState st[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    ResidentState &r = st[dev];
-    if (r.wg_per_cu < 0) {
-        r.wg_per_cu = 0;
-        void *h = nullptr, *d = nullptr;
-        int per_cu = 0, cus = 0;
-        if (hipHostMalloc(&h, sizeof(unsigned), hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess &&
-            hipEventCreateWithFlags(&r.last, hipEventDisableTiming) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(am_fine_persist_kernel), 64 * kFineS, 0) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
-            r.host_word = static_cast<unsigned *>(h);
-            r.dev_word = static_cast<unsigned *>(d);
-            *r.host_word = 0;
-            r.wg_per_cu = per_cu;
-            r.cus = cus;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    return &r;
-}
-// nonzero if an earlier resident launch on this device timed out (and clears the word)
-unsigned take_resident_failure() {
-    std::lock_guard<std::mutex> lk(g_resident_mu);
-    ResidentState *r = resident_state();
-    if (!r || !r->host_word) return 0;
-    return __atomic_exchange_n(r->host_word, 0u, __ATOMIC_RELAXED);
-}
 static bool resident_enabled() {  // measurement switch (pcc_test_hooks.h): one launch per pass at the fine levels too
     return pcc::tuning(PCC_TUNE_AM_NORESIDENT) == 0;
 }
@@ -2628,18 +2569,21 @@ int launch_fine_resident(const Sched &sc, int bc, hipStream_t st) {
     a.live_cnt = sc.live_cnt;
     a.live_mask = sc.live_mask;
     a.mask_words = mask_words(sc.m4);
+    static const int per_cu = [] {  // resident workgroups per CU (0 if the query fails)
+        int r = 0;
+        const void *k = reinterpret_cast<const void *>(am_fine_persist_kernel);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k, 64 * kFineS, 0) != hipSuccess) (void)hipGetLastError();
+        return r;
+    }();
+    // the whole launch resident at once on half of the device's workgroup slots
+    if (per_cu < 2 || (long long)bc * tiles > pcc::device_cus()) return -1;
+    pcc::CoresidentGate gate(pcc::kFineResident, st);  // declines while `st` is being captured
+    if (!gate.ok) return -1;
+    a.host_err = gate.sticky;
+    a.inject = gate.inject;
     {
-        std::lock_guard<std::mutex> lk(g_resident_mu);
-        ResidentState *r = resident_state();
-        // the whole launch resident at once on half of the device's workgroup slots
-        if (!r || r->wg_per_cu < 2 || (long long)bc * tiles > r->cus) return -1;
-        a.host_err = r->dev_word;
-        if (r->last_stream && r->last_stream != st) (void)hipStreamWaitEvent(st, r->last, 0);
-        {
-            pcc::ProfScope prof("am_fine_persist_kernel", st);
-            hipLaunchKernelGGL(am_fine_persist_kernel, dim3((unsigned)(bc * tiles)), dim3(64 * kFineS), 0, st, a);
-        }
-        if (hipEventRecord(r->last, st) == hipSuccess) r->last_stream = st;
+        pcc::ProfScope prof("am_fine_persist_kernel", st);
+        hipLaunchKernelGGL(am_fine_persist_kernel, dim3((unsigned)(bc * tiles)), dim3(64 * kFineS), 0, st, a);
     }
     return pcc::check_launch("approxmatch(resident fine levels)");
 }
@@ -2649,7 +2593,7 @@ int launch_fine_resident(const Sched &sc, int bc, hipStream_t st) {
 int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const WsLayout &L, char *base, hipStream_t st,
                const std::function<int(int, int, hipStream_t)> &lane_tail = nullptr,
                const std::function<int(int, int, hipStream_t)> &after_sort = nullptr) {
-    if (const unsigned fw = take_resident_failure()) {
+    if (const unsigned fw = pcc::take_coresident_failure(pcc::kFineResident)) {
         char buf[320];
         std::snprintf(buf, sizeof buf, "approxmatch: an earlier call on this device did not complete (a sample barrier of the resident "
                       "fine-level launch timed out: barrier %u of sample %u saw %u arrivals; the implicit path reported NaN for those "
@@ -2677,13 +2621,7 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
     int nlanes = 1;
     bool fork = false;
     if (split_enabled && b >= 8 && (long long)b * std::max(n, m) >= 32768) {
-        // not while the caller's stream is being captured into a graph: the capture stays a single-stream chain
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
-            (void)hipGetLastError();
-            cap = hipStreamCaptureStatusNone;
-        }
-        fork = cap == hipStreamCaptureStatusNone;
+        fork = !pcc::capturing(st);  // a capture stays a single-stream chain
     }
     ForkJoin fj(st, fork);
     if (fj.side) nlanes = 2;
@@ -2790,8 +2728,9 @@ int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, 
     float *lv_orig = reinterpret_cast<float *>(base + L.lv_orig);
     float *cpart = reinterpret_cast<float *>(base + L.cpart);
     const LevelConsts lc = make_levels();
+    const int *flags = reinterpret_cast<const int *>(base + L.live_cnt);  // (written by this call's sort and passes)
     hipLaunchKernelGGL(am_unpermute_kernel, dim3(pcc::ceil_div(n + m, 256), b), dim3(256), 0, st, n, m, L.n4, L.m4, lv, rem,
-                       rank1, rank2, lv_orig, temp);
+                       rank1, rank2, flags, lv_orig, temp);
     rc = pcc::check_launch("approxmatch(unpermute)");
     if (rc) return rc;
     const dim3 grid(pcc::ceil_div(n, kMatKT), pcc::ceil_div(m, kMatLT), b);

@@ -8,14 +8,10 @@
 // Bid values follow emd_cuda.cu:145 literally: `3.0 - sqrtf(d2) - price` is DOUBLE arithmetic rounded once
 // to float; sqrtf is correctly rounded (-fno-fast-math).
 #include "pcc_common.hpp"
-#include <atomic>
-
-#include <mutex>
 #include "pcc_emd.h"
 #include "pcc_test_hooks.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
 
@@ -149,38 +145,14 @@ __global__ __launch_bounds__(1024) void auction_kernel(int n, const float *__res
 // A workgroup owns a contiguous slice of the BIDDERS (set1 points) and keeps the whole target cloud plus a copy of
 // the prices in LDS; the state the workgroups of a sample share -- prices, assignment, inverse assignment, highest
 // increment and winner per target -- lives in global memory and is touched only with agent-scope (sc1) accesses /
-// atomics, so no cache-wide fence is needed (cdna_hip_programming.md Guideline 16).  Three sample-local barriers per
+// atomics (the rule of pcc::coresident_barrier, pcc_common.hpp).  Three sample-local barriers per
 // iteration replace the kernel boundaries of the reference (Bid | GetMax | Assign).  Same deterministic rules as the
 // one-workgroup kernel, hence the same bits: the best / second-best scan of a bidder does not depend on who runs
 // it, atomicMax / atomicMin are order-free, and every target has at most one winner per iteration.
-// All workgroups of a launch must be co-resident (the host sizes C and the launch for that); spins are bounded and
-// raise an error word that poisons the outputs instead of hanging.
+// All workgroups of a launch must be co-resident (the host sizes C and the launch for that, behind a
+// pcc::CoresidentGate); spins are bounded and raise an error word that poisons the outputs instead of hanging.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int gld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float gldf(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void gst(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void gstf(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ bool cluster_barrier(unsigned *ctr, unsigned target, unsigned *err, int tid) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sc1 stores / atomics have left the CU
-    __syncthreads();
-    __shared__ int failed;
-    if (tid == 0) {
-        failed = 0;
-        __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > (1u << 24) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a partner never arrived
-                failed = 1;
-                break;
-            }
-        }
-    }
-    __syncthreads();
-    return failed == 0;
-}
+using pcc::agent_ld, pcc::agent_st;
 
 __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, const float *__restrict__ xyz1,
                                                                 const float *__restrict__ xyz2, float eps, int iters,
@@ -210,6 +182,9 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
     unsigned *err = sync;                                  // one error word, then the per-sample records:
     unsigned *sy_ctr = sync + 1 + (size_t)smp * (2 + iters);  // [0] barrier counter, [1] unused, [2 + it] bidders of iteration it
     unsigned barriers = 0;
+    auto barrier = [&] {  // the error word is launch-wide; the sticky host word is raised once, at the end of the kernel
+        return pcc::coresident_barrier<2, (1u << 24)>(sy_ctr, C * ++barriers, err, nullptr, [] { return 1u; });
+    };
 
     for (int k = tid; k < n; k += T) {
         sx[k] = p2[k * 3 + 0];
@@ -217,20 +192,20 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
         sz[k] = p2[k * 3 + 2];
     }
     for (int k = j0 + tid; k < j1; k += T) {  // this workgroup initialises its share of the shared state
-        gstf(&price[k], 0.f);
-        gst(&inv[k], -1);
-        gst(&max_inc[k], 0);  // emd_module.py:41 zeros
-        gst(&ass[k], -1);
+        agent_st(&price[k], 0.f);
+        agent_st(&inv[k], -1);
+        agent_st(&max_inc[k], 0);  // emd_module.py:41 zeros
+        agent_st(&ass[k], -1);
     }
-    bool ok = cluster_barrier(sy_ctr, (unsigned)C * ++barriers, err, tid);
+    bool ok = barrier();
 
     for (int it = 0; ok && it < iters; it++) {
         const bool last = it == iters - 1;
         if (tid == 0) cnt[0] = 0;
-        for (int k = tid; k < n; k += T) pr[k] = gldf(&price[k]);
+        for (int k = tid; k < n; k += T) pr[k] = agent_ld(&price[k]);
         __syncthreads();
         for (int j = j0 + tid; j < j1; j += T)
-            if (gld(&ass[j]) == -1) unass[atomicAdd(&cnt[0], 1)] = j;  // order irrelevant to the result
+            if (agent_ld(&ass[j]) == -1) unass[atomicAdd(&cnt[0], 1)] = j;  // order irrelevant to the result
         __syncthreads();
         const int nu = cnt[0];
         if (tid == 0 && nu) __hip_atomic_fetch_add(&sy_ctr[2 + it], (unsigned)nu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -269,43 +244,43 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
                 incl[u] = bi;
                 // :175 (bi > 0: int order == float order)
                 __hip_atomic_fetch_max(&max_inc[cd.best_i], __float_as_int(bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                gst(&win[cd.best_i], 0x7fffffff);
+                agent_st(&win[cd.best_i], 0x7fffffff);
             }
         }
-        ok = cluster_barrier(sy_ctr, (unsigned)C * ++barriers, err, tid);
+        ok = barrier();
         if (!ok) break;
         // everything assigned: the remaining iterations (and the forced one) are no-ops; every workgroup of the
         // sample reads the same total, so the exit is uniform
-        if (__hip_atomic_load(&sy_ctr[2 + it], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) break;
+        if (agent_ld(&sy_ctr[2 + it]) == 0) break;
         // ---- GetMax (:180-193): lowest qualifying bidder wins ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bidl[u];
-            const double bi = incl[u], mi = __int_as_float(gld(&max_inc[t]));
+            const double bi = incl[u], mi = __int_as_float(agent_ld(&max_inc[t]));
             if (bi - 1e-6 <= mi && mi <= bi + 1e-6) __hip_atomic_fetch_min(&win[t], j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        ok = cluster_barrier(sy_ctr, (unsigned)C * ++barriers, err, tid);
+        ok = barrier();
         if (!ok) break;
         // ---- Assign (:195-214) ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bidl[u];
-            if (last || gld(&win[t]) == j) {
-                const int owner = gld(&inv[t]);
-                if (!last && owner != -1) gst(&ass[owner], -1);
-                gst(&inv[t], j);
-                gst(&ass[j], t);
+            if (last || agent_ld(&win[t]) == j) {
+                const int owner = agent_ld(&inv[t]);
+                if (!last && owner != -1) agent_st(&ass[owner], -1);
+                agent_st(&inv[t], j);
+                agent_st(&ass[j], t);
                 if (last) __hip_atomic_fetch_add(&price[t], incl[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else gstf(&price[t], pr[t] + incl[u]);  // the only writer of price[t] in this iteration
-                gst(&max_inc[t], __float_as_int(-1e9f));
+                else agent_st(&price[t], pr[t] + incl[u]);  // the only writer of price[t] in this iteration
+                agent_st(&max_inc[t], __float_as_int(-1e9f));
             }
         }
-        ok = cluster_barrier(sy_ctr, (unsigned)C * ++barriers, err, tid);
+        ok = barrier();
     }
     __syncthreads();
-    const bool bad = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const bool bad = agent_ld(err) != 0;
     // the failure also goes to a sticky word in host memory: the next pcc_auction_* call on this device reports it
     if (bad && tid == 0 && host_err) __hip_atomic_store(host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (int j = j0 + tid; j < j1; j += T) {  // CalcDist :216-225
-        const int k = gld(&ass[j]);
+        const int k = agent_ld(&ass[j]);
         const bool valid = !bad && k >= 0 && k < n;
         const int kk = valid ? k : 0;
         const float d = sq3(p1[j * 3 + 0] - sx[kk], p1[j * 3 + 1] - sy[kk], p1[j * 3 + 2] - sz[kk]);
@@ -330,45 +305,6 @@ __global__ __launch_bounds__(256) void auction_bwd_kernel(size_t total, int n, c
     for (int c = 0; c < 3; c++) grad1[t * 3 + c] = valid ? g * (xyz1[t * 3 + c] - xyz2[q * 3 + c]) : 0.f;
 }
 
-// Per-device state of the cluster schedule: a sticky failure word in mapped host memory (set by a kernel whose sample
-// barrier timed out) and the event of the last cluster launch -- two cluster launches must never run at the same time
-// (each needs all of its workgroups resident; two of them on different streams could wait for each other forever),
-// so a launch on another stream first waits for the previous one.
-struct ClusterState {
-    unsigned *host_word = nullptr, *dev_word = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool inject = false;
-};
-std::mutex g_cluster_mu;
-ClusterState *cluster_state() {
-    static ClusterState st[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    ClusterState &c = st[dev];
-    if (!c.host_word) {
-        void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        c.host_word = static_cast<unsigned *>(h);
-        c.dev_word = static_cast<unsigned *>(d);
-        *c.host_word = 0;
-        if (hipEventCreateWithFlags(&c.last, hipEventDisableTiming) != hipSuccess) c.last = nullptr;
-    }
-    return &c;
-}
-// nonzero if an earlier cluster launch on this device timed out (and clears the word)
-int take_cluster_failure() {
-    std::lock_guard<std::mutex> lk(g_cluster_mu);
-    ClusterState *c = cluster_state();
-    if (!c || !c->host_word) return 0;
-    const unsigned v = __atomic_exchange_n(c->host_word, 0u, __ATOMIC_RELAXED);
-    return v != 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -380,7 +316,7 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
     if (n > 8192) return pcc::invalid("auction: n > 8192 does not fit the LDS-resident state");
     if (b == 0) return PCC_OK;
     if (!xyz1 || !xyz2 || !dist || !assignment) return pcc::invalid("auction: null pointer");
-    if (take_cluster_failure())
+    if (pcc::take_coresident_failure(pcc::kAuctionCluster))
         return pcc::invalid("auction: an earlier launch on this device did not complete (a sample barrier timed out: its "
                             "outputs were poisoned with NaN / -1); this call was not started");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -398,52 +334,37 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
         const int njmax = (n + C - 1) / C + 1;
         const size_t lds = (size_t)4 * n * 4 + (size_t)3 * njmax * 4 + 16;
         if (C > 1 && lds <= 160 * 1024 - 256) {
-            static bool attr2 = [] {  // the kernel also has a few bytes of static LDS (barrier flag)
-                const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(auction_cluster_kernel),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
-                if (!ok) (void)hipGetLastError();
-                return ok;
-            }();
-            (void)attr2;
-            const int group = std::max(1, cus / C);          // samples per launch
-            const size_t sync_words = 1 + (size_t)b * (2 + iters);
-            const size_t bytes = (size_t)b * 4 * n * 4 + sync_words * 4;
-            char *ws = nullptr;
-            if (pcc::ws_malloc(reinterpret_cast<void **>(&ws), bytes, st) != hipSuccess) {
-                (void)hipGetLastError();
-                pcc::set_error(PCC_ENOMEM, "auction: workspace allocation failed");
-                return PCC_ENOMEM;
-            }
-            int *scratch = reinterpret_cast<int *>(ws);
-            unsigned *sync = reinterpret_cast<unsigned *>(ws + (size_t)b * 4 * n * 4);
-            (void)hipMemsetAsync(sync, 0, sync_words * 4, st);
-            unsigned *host_err = nullptr;
-            {
-                std::lock_guard<std::mutex> lk(g_cluster_mu);
-                ClusterState *cs = cluster_state();
-                if (cs) {
-                    host_err = cs->dev_word;
-                    // never two cluster launches at once: a launch on another stream waits for the previous one
-                    if (cs->last && cs->last_stream && cs->last_stream != st) (void)hipStreamWaitEvent(st, cs->last, 0);
-                    if (cs->inject) {  // test hook: start with the error word raised
-                        (void)hipMemsetAsync(sync, 1, 1, st);
-                        cs->inject = false;
-                    }
+            pcc::CoresidentGate gate(pcc::kAuctionCluster, st);  // declines while capturing: auction_kernel below, same bits
+            if (gate.ok) {
+                static bool attr2 = [] {  // the kernel also has a few bytes of static LDS (barrier flag)
+                    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(auction_cluster_kernel),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
+                    if (!ok) (void)hipGetLastError();
+                    return ok;
+                }();
+                (void)attr2;
+                const int group = std::max(1, cus / C);          // samples per launch
+                const size_t sync_words = 1 + (size_t)b * (2 + iters);
+                const size_t bytes = (size_t)b * 4 * n * 4 + sync_words * 4;
+                char *ws = nullptr;
+                if (pcc::ws_malloc(reinterpret_cast<void **>(&ws), bytes, st) != hipSuccess) {
+                    (void)hipGetLastError();
+                    pcc::set_error(PCC_ENOMEM, "auction: workspace allocation failed");
+                    return PCC_ENOMEM;
                 }
+                int *scratch = reinterpret_cast<int *>(ws);
+                unsigned *sync = reinterpret_cast<unsigned *>(ws + (size_t)b * 4 * n * 4);
+                (void)hipMemsetAsync(sync, 0, sync_words * 4, st);
+                if (gate.inject) (void)hipMemsetAsync(sync, 1, 1, st);  // test hook: start with the error word raised
+                for (int s0 = 0; s0 < b; s0 += group) {
+                    const int gb = std::min(group, b - s0);
+                    pcc::ProfScope prof("auction_cluster_kernel", st);
+                    hipLaunchKernelGGL(auction_cluster_kernel, dim3((unsigned)(gb * C)), dim3(1024), lds, st, n, C, xyz1, xyz2, eps,
+                                       iters, dist, assignment, scratch, sync, s0, gate.sticky);
+                }
+                (void)pcc::ws_free(ws, st);
+                return pcc::check_launch("auction_forward(cluster)");
             }
-            for (int s0 = 0; s0 < b; s0 += group) {
-                const int gb = std::min(group, b - s0);
-                pcc::ProfScope prof("auction_cluster_kernel", st);
-                hipLaunchKernelGGL(auction_cluster_kernel, dim3((unsigned)(gb * C)), dim3(1024), lds, st, n, C, xyz1, xyz2, eps,
-                                   iters, dist, assignment, scratch, sync, s0, host_err);
-            }
-            {
-                std::lock_guard<std::mutex> lk(g_cluster_mu);
-                ClusterState *cs = cluster_state();
-                if (cs && cs->last && hipEventRecord(cs->last, st) == hipSuccess) cs->last_stream = st;
-            }
-            (void)pcc::ws_free(ws, st);
-            return pcc::check_launch("auction_forward(cluster)");
         }
     }
     const size_t hot = (size_t)5 * n * 4 + 16, state = (size_t)5 * n * 4;
@@ -470,26 +391,13 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
 }
 
 int pcc_auction_status(void) {
-    return take_cluster_failure() ? 1 : 0;
-}
-
-// include/pcc_test_hooks.h -- NOT part of the product ABI: inert unless PCC_TEST_HOOKS=1 was in the environment when the
-// library first looked (the test-suite sets it; tests/conftest.py)
-int pcc_test_inject_auction_failure(void) {
-    static const bool armed = [] {
-        const char *e = std::getenv("PCC_TEST_HOOKS");
-        return e && e[0] == '1';
-    }();
-    if (!armed) return 0;
-    std::lock_guard<std::mutex> lk(g_cluster_mu);
-    if (ClusterState *cs = cluster_state()) cs->inject = true;
-    return 1;
+    return pcc::take_coresident_failure(pcc::kAuctionCluster) ? 1 : 0;
 }
 
 int pcc_auction_backward(int b, int n, const float *xyz1, const float *xyz2, const float *grad_dist,
                          const int *assignment, float *grad_xyz1, pcc_stream_t stream) {
     pcc::clear_error();
-    if (take_cluster_failure())
+    if (pcc::take_coresident_failure(pcc::kAuctionCluster))
         return pcc::invalid("auction_backward: the forward launch on this device did not complete (a sample barrier timed "
                             "out: dist was poisoned with NaN, unassigned points are -1)");
     if (b < 0 || n < 0) return pcc::invalid("auction_backward: bad size");

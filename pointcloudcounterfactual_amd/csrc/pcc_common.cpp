@@ -2,9 +2,10 @@
 #include "pcc_common.hpp"
 
 #include <atomic>
-
+#include <cstdlib>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -163,14 +164,87 @@ const char *pcc_last_error(void) { return t_msg; }
 int pcc_last_status(void) { return t_status; }
 }
 
-#include <cstdlib>
+namespace pcc {
+bool capturing(hipStream_t st) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) (void)hipGetLastError();
+    return cap != hipStreamCaptureStatusNone;
+}
+
+// per device: the sticky failure words [kind] (mapped host memory), the event of the last co-resident launch and its
+// stream, pending test injections [kind]; guarded by g_coresident_mu
+struct CoresidentDevice {
+    unsigned *host = nullptr, *mapped = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool inject[kCoresidentKinds] = {}, tried = false;
+};
+namespace {
+std::mutex g_coresident_mu;
+CoresidentDevice *coresident_device() {  // null if the state cannot be set up
+    static CoresidentDevice devs[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    CoresidentDevice &d = devs[dev];
+    if (!std::exchange(d.tried, true)) {
+        void *h = nullptr, *p = nullptr;
+        if (hipHostMalloc(&h, kCoresidentKinds * sizeof(unsigned), hipHostMallocMapped) == hipSuccess &&
+            hipHostGetDevicePointer(&p, h, 0) == hipSuccess && hipEventCreateWithFlags(&d.last, hipEventDisableTiming) == hipSuccess) {
+            d.host = static_cast<unsigned *>(std::memset(h, 0, kCoresidentKinds * sizeof(unsigned)));
+            d.mapped = static_cast<unsigned *>(p);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    return d.host ? &d : nullptr;
+}
+}  // namespace
+
+CoresidentGate::CoresidentGate(CoresidentKind kind, hipStream_t s) : st(s) {
+    if (capturing(st)) return;  // (first: nothing is set up, waited on or recorded inside a capture)
+    g_coresident_mu.lock();
+    if (!(dev = coresident_device())) {
+        g_coresident_mu.unlock();
+        return;
+    }
+    if (dev->last_stream && dev->last_stream != st) (void)hipStreamWaitEvent(st, dev->last, 0);
+    ok = true;
+    sticky = dev->mapped + kind;
+    inject = std::exchange(dev->inject[kind], false);
+}
+CoresidentGate::~CoresidentGate() {
+    if (!dev) return;
+    if (hipEventRecord(dev->last, st) == hipSuccess) dev->last_stream = st;
+    g_coresident_mu.unlock();
+}
+
+unsigned take_coresident_failure(CoresidentKind kind) {
+    std::lock_guard<std::mutex> lk(g_coresident_mu);
+    CoresidentDevice *d = coresident_device();
+    return d ? __atomic_exchange_n(&d->host[kind], 0u, __ATOMIC_RELAXED) : 0;
+}
+}  // namespace pcc
+
+// include/pcc_test_hooks.h: inert unless PCC_TEST_HOOKS=1 was in the environment when the library first looked
 #include "pcc_test_hooks.h"
-extern "C" int pcc_test_set_tuning(int key, int value) {
+static bool hooks_armed() {
     static const bool armed = [] {
         const char *e = std::getenv("PCC_TEST_HOOKS");
         return e && e[0] == '1';
     }();
-    if (!armed || key < 0 || key >= 16) return 0;
+    return armed;
+}
+extern "C" int pcc_test_set_tuning(int key, int value) {
+    if (!hooks_armed() || key < 0 || key >= 16) return 0;
     __atomic_store_n(&g_tuning[key], value, __ATOMIC_RELAXED);
     return 1;
 }
+static int inject_failure(pcc::CoresidentKind kind) {
+    if (!hooks_armed()) return 0;
+    std::lock_guard<std::mutex> lk(pcc::g_coresident_mu);
+    pcc::CoresidentDevice *d = pcc::coresident_device();
+    if (d) d->inject[kind] = true;
+    return d ? 1 : 0;
+}
+extern "C" int pcc_test_inject_auction_failure(void) { return inject_failure(pcc::kAuctionCluster); }
+extern "C" int pcc_test_inject_approxmatch_failure(void) { return inject_failure(pcc::kFineResident); }

@@ -7,6 +7,11 @@
 
 #include "pcc_structural.h"
 
+// The device code assumes gfx950: wave64, the co-resident barrier's `s_waitcnt vmcnt(0)` and its memory model.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "libpcc_structural is written for gfx950 (MI355X) only"
+#endif
+
 namespace pcc {
 
 constexpr int kWave = 64;  // CDNA wavefront
@@ -88,5 +93,78 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
 // (x, y, z, original index as bits), box16 [b][ceil(n/16)][8] (lo xyz, pad, hi xyz, pad), perm [b][n] sorted -> original.
 constexpr int kSortBox = 16;
 int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st);
+
+// true while `st` is being captured into a graph (a failed query counts as not capturing)
+bool capturing(hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------
+// Co-resident launches (auction_cluster_kernel, am_fine_persist_kernel): every workgroup of the grid is on the device at
+// once, because the workgroups of a sample meet at barriers in global memory instead of at kernel boundaries.  The
+// caller sizes the grid to fit the device; CoresidentGate keeps other co-resident launches off it meanwhile.
+// The barrier issues no cache-wide fence (cdna_hip_programming.md Guideline 16).  It is correct under this rule:
+//   * every access to state the workgroups of a sample share is agent_ld / agent_st or an agent-scope atomic (served by
+//     the L2 every CU sees);
+//   * every wave waits for its own vector memory operations (s_waitcnt vmcnt(0)), then the workgroup barrier;
+//   * one relaxed agent-scope fetch_add per workgroup arrives; one thread spins with relaxed agent-scope loads, SLEEP
+//     s_sleep units between polls, until the count reaches `target` (the counter is never reset: barrier k of a sample of
+//     W workgroups waits for k W);
+//   * the spin gives up after BOUND polls or when the sample's error word is raised, reporting through coresident_fail;
+//   * a second workgroup barrier hands the outcome to every thread.
+// ---------------------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ T agent_ld(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T>
+__device__ __forceinline__ void agent_st(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Raises the sample's error word; its first reporter also sets the sticky host word (if given, and still clear) to `code`.
+__device__ __forceinline__ void coresident_fail(unsigned *err, unsigned *host_err, unsigned code) {
+    const unsigned was = __hip_atomic_exchange(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned expected = 0;
+    if (host_err && !was)
+        __hip_atomic_compare_exchange_strong(host_err, &expected, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// false in every thread if the barrier failed; `code()` (the failure code for the host) runs only then
+template <int SLEEP, unsigned BOUND, class Code>
+__device__ __forceinline__ bool coresident_barrier(unsigned *ctr, unsigned target, unsigned *err, unsigned *host_err, Code code) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's agent-scope stores / atomics have left the CU
+    __syncthreads();
+    __shared__ int failed;
+    if (threadIdx.x == 0) {
+        failed = 0;
+        __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned spins = 0;
+        while (agent_ld(ctr) < target) {
+            __builtin_amdgcn_s_sleep(SLEEP);
+            if (++spins > BOUND || agent_ld(err)) {  // a partner never arrived, or one reported a failure
+                coresident_fail(err, host_err, code());
+                failed = 1;
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    return failed == 0;
+}
+
+// kinds of co-resident launch; each has its own sticky failure word and test hook (include/pcc_test_hooks.h)
+enum CoresidentKind { kAuctionCluster = 0, kFineResident = 1, kCoresidentKinds = 2 };
+
+// Per-device gate taken around the co-resident launch(es) of one call on stream `st`.  `ok` is false while `st` is being
+// captured into a graph (a replay would escape the order kept here) or if the device state could not be set up: the
+// caller then runs its other schedule.  Otherwise the gate holds the lock, makes `st` wait for the last co-resident launch
+// of EITHER kind when that went to another stream, and records the device's event on `st` when it ends.  `sticky`: the
+// kind's word in mapped host memory, for coresident_fail; `inject`: the test hook asks this launch to fail.
+struct CoresidentGate {
+    CoresidentGate(CoresidentKind kind, hipStream_t st);
+    ~CoresidentGate();
+    bool ok = false, inject = false;
+    unsigned *sticky = nullptr;
+    struct CoresidentDevice *dev = nullptr;
+    hipStream_t st;
+};
+
+// The failure code an earlier launch of `kind` left on the current device (0: none); clears it.
+unsigned take_coresident_failure(CoresidentKind kind);
 
 }  // namespace pcc

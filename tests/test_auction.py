@@ -199,8 +199,10 @@ def test_auction_failure_is_reported_not_silent(cuda):
 @pytest.mark.gpu
 def test_auction_cluster_launches_on_two_streams(cuda):
     """Two cluster launches enqueued on different streams are ordered by the library (each needs all its workgroups
-    resident): both finish with the bits of a launch on its own."""
+    resident): both finish with the bits of a launch on its own.  The same holds when they alternate with the approximate
+    EMD's resident launches (the other co-resident kind, b x tiles <= CUs): one per-device event orders both kinds."""
     from emd import emdModule
+    from structural_losses import match_cost
 
     a, c = _clouds(9, 8, 2048)
     t1, t2 = torch.from_numpy(a).to(cuda), torch.from_numpy(c).to(cuda)
@@ -214,3 +216,54 @@ def test_auction_cluster_launches_on_two_streams(cuda):
     torch.cuda.synchronize()
     for d, asg in outs:
         assert torch.equal(d, ref_d) and torch.equal(asg, ref_a)
+    # mixed kinds: auction cluster launches and resident match_cost launches alternate over the two streams
+    ref_c = match_cost(t1, t2)
+    torch.cuda.synchronize()
+    outs, costs = [], []
+    for st in (s1, s2, s1, s2):
+        with torch.cuda.stream(st):
+            outs.append(emdModule()(t1, t2, 0.005, 30))
+        with torch.cuda.stream(s2 if st is s1 else s1):
+            costs.append(match_cost(t1, t2))
+    torch.cuda.synchronize()
+    for d, asg in outs:
+        assert torch.equal(d, ref_d) and torch.equal(asg, ref_a)
+    for cst in costs:
+        assert torch.equal(cst, ref_c)
+
+
+@pytest.mark.gpu
+def test_coresident_launches_decline_under_graph_capture(cuda):
+    """While a stream is being captured into a graph, neither co-resident launch is recorded (a replay would run outside
+    the order the library keeps between them): the capture holds the approximate EMD's launch per pass and the auction's
+    one-workgroup schedule, which give the bits of the eager resident / cluster launches.  The eager calls after the
+    replays still give them too."""
+    from emd import emdModule
+    from pointcloudcounterfactual_amd import backend
+
+    a, c = _clouds(11, 8, 2048)
+    t1, t2 = torch.from_numpy(a).to(cuda), torch.from_numpy(c).to(cuda)
+
+    def run():
+        cost, g1, g2 = backend.MatchCostImplicit(t1, t2, True)
+        d, asg = emdModule()(t1, t2, 0.005, 30)
+        return [cost, g1, g2, d, asg]
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        ref = run()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = run()
+    for _ in range(2):
+        for x in captured:
+            x.fill_(0)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, y) for x, y in zip(captured, ref))
+    after = run()
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(after, ref))

@@ -465,6 +465,36 @@ def test_resident_fine_levels_equal_one_launch_per_pass(cuda):
         assert torch.isfinite(resident['cost']).all()
 
 
+def test_resident_failure_is_reported_not_silent(cuda):
+    """A resident launch of levels 0-2 whose sample barriers fail (here: injected through the test hook, which makes every
+    sample fail at its first barrier) gives NaN for its samples on both paths -- cost and gradients of the implicit path,
+    match / temp / cost of the materialising one -- AND surfaces as an error: the next call on the device raises
+    instead of starting, and the call after it is finite again."""
+    from pointcloudcounterfactual_amd import _lib, backend
+
+    a, c = pair(61, 4, 2048, 2048, 'recon')
+    t1, t2 = _dev(a, cuda), _dev(c, cuda)
+    assert _lib.lib.pcc_test_inject_approxmatch_failure() == 1  # armed: tests/conftest.py sets PCC_TEST_HOOKS=1
+    cost, g1, g2 = backend.MatchCostImplicit(t1, t2, True)
+    torch.cuda.synchronize()
+    assert torch.isnan(cost).all() and torch.isnan(g1).all() and torch.isnan(g2).all()
+    with pytest.raises(RuntimeError, match='did not complete'):
+        backend.MatchCostImplicit(t1, t2, True)
+    cost, g1, g2 = backend.MatchCostImplicit(t1, t2, True)
+    torch.cuda.synchronize()
+    assert torch.isfinite(cost).all() and torch.isfinite(g1).all() and torch.isfinite(g2).all()
+
+    assert _lib.lib.pcc_test_inject_approxmatch_failure() == 1
+    match, temp, mc = backend.ApproxMatchCost(t1, t2)
+    torch.cuda.synchronize()
+    assert torch.isnan(match).all() and torch.isnan(temp).all() and torch.isnan(mc).all()
+    with pytest.raises(RuntimeError, match='did not complete'):
+        backend.ApproxMatchCost(t1, t2)
+    match, temp, mc = backend.ApproxMatchCost(t1, t2)
+    torch.cuda.synchronize()
+    assert torch.isfinite(match).all() and torch.isfinite(temp).all() and torch.isfinite(mc).all()
+
+
 def test_stale_workspace_does_not_leak_into_results(cuda):
     """The library's scratch comes from a stream-ordered pool and is not cleared; the suite runs with PCC_WS_POISON=1
     (conftest.py), which fills every workspace with NaN patterns first.  Results must not depend on it: a call repeated
