@@ -26,8 +26,10 @@ extern "C" {
  * feature space, ascending distance (the point itself first), ties by ascending index.
  *   c <= 3 : exact difference form sum_c (x_j - x_i)^2 on the f32 VALU (the GPU reference's formula, :35-40)
  *   c >= 4 : expanded form |x_i|^2 + |x_j|^2 - 2 x_i.x_j with the inner product on the f32 MFMA pipe
- *            (the reference CPU path's formula, self_square_distance :53-60)
- * Requires 1 <= k <= min(n, 32). */
+ *            (the reference CPU path's formula, self_square_distance :53-60): (-2*dot + |x_j|^2) + |x_i|^2 with
+ *            dot and |x|^2 sequential fma chains over the channel index
+ * Any c >= 1; requires 1 <= k <= min(n, 128) (k > 128: PCC_EINVAL).  A NaN distance never enters a list; a list that
+ * runs short because of NaN distances is padded with the in-range index n - 1. */
 int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_stream_t stream);
 
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */

@@ -104,7 +104,7 @@ def check(status: int, what: str) -> None:
 
 # include/pcc_test_hooks.h: measurement / bit-identity switches (inert unless PCC_TEST_HOOKS=1 is in the environment)
 TUNING = {'am_nocull': 2, 'am_nosplit': 3, 'am_noresident': 4, 'edge_scatter': 5, 'nbrsum_scatter': 6,
-          'auction_cluster': 7, 'knn_nosplit': 8}
+          'auction_cluster': 7, 'knn_nosplit': 8, 'knn_wide': 9}
 
 
 def set_tuning(name: str, value: int) -> None:

@@ -17,6 +17,8 @@
 //     registers: the (B,N,N) distance matrix never exists in memory.
 //   * knn_mfma_split_kernel (c >= 4, launches that fill the chip): the same arithmetic with the matrix waves and the
 //     selection waves of a workgroup apart, one query per selection lane (see the kernel).
+// These cover k <= 32 and c <= 128; every other call (k up to 128, any c) goes to knn_wide.hip, with the same formulas
+// and the same ordering contract.
 #include "pcc_common.hpp"
 #include "pcc_neighbour.h"
 #include "pcc_test_hooks.h"
@@ -990,11 +992,12 @@ extern "C" int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indi
     if (b < 0 || c < 1 || n < 0 || k < 1) return pcc::invalid("knn: bad size");
     if (b == 0 || n == 0) return PCC_OK;
     if (k > n) return pcc::invalid("knn: k exceeds the number of points (torch.topk raises too)");
-    if (k > 32) return pcc::invalid("knn: k > 32 is not supported");
-    if (c > 128) return pcc::invalid("knn: more than 128 channels is not supported");
+    if (k > 128) return pcc::invalid("knn: k > 128 is not supported");
     if (b > 65535) return pcc::invalid("knn: batch too large");
     if (!x || !indices) return pcc::invalid("knn: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // outside the box of the kernels below: knn_wide.hip (the test switch sends every call there)
+    if (k > 32 || c > 128 || pcc::tuning(PCC_TUNE_KNN_WIDE) == 1) return pcc::knn_wide(b, c, n, k, x, indices, st);
     if (c <= 3 && n <= kSortedMaxN) {
         // sorted search: workspace = packed sorted rows | boxes | permutation
         const int nb = pcc::ceil_div(n, kSortBoxK);

@@ -1,0 +1,357 @@
+// k-NN graph for the calls outside the box of knn.hip's kernels (k > 32, or c > 128), gfx950, wave64.
+//
+// Same formulas, same rounding and the same ordering contract as knn.hip (include/pcc_neighbour.h):
+//   * c <= 3: difference form sum_c (x_j - x_i)^2 as an fma chain over the channels, computed inside the selection
+//     kernel (exhaustive scan);
+//   * c >= 4: expanded form (-2*dot + |x_j|^2) + |x_i|^2.  knn_wide_dist_kernel computes the inner products of a block of
+//     128 queries x 128 candidates on v_mfma_f32_32x32x2_f32, streaming the channels in chunks of 16 through LDS and
+//     carrying one accumulator across the chunks, so every inner product is ONE sequential fma chain over the channel
+//     index (bit-identical to the oracle for any c).  The distances go to a workspace [query][candidate] (at most
+//     kWideRowsBytes per launch pair: larger calls run in chunks of samples or of queries).
+// Selection (knn_wide_select_kernel): one wave per query, the list of the L >= k smallest 64-bit keys (order-preserving
+// distance bits : candidate index -- one unsigned compare is "distance, then index") spread over the lanes, element
+// e = lane + 64 h in register h.  Candidates are tested 64 at a time against the current k-th key; the few that pass are
+// appended to a buffer of L keys in LDS (ballot + mbcnt: no lane waits for another), and a full buffer is merged into
+// the list by one bitonic sort of list + buffer in registers (the lower half is the new list).
+#include <algorithm>
+
+#include "pcc_common.hpp"
+#include "pcc_neighbour.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr u64 kWideKeyMax = ~0ull;                          // empty slot: above every key of a real candidate
+constexpr size_t kWideRowsBytes = (size_t)256 << 20;        // distance workspace per launch pair
+constexpr int kDT = 128;                                    // queries = candidates per distance workgroup
+constexpr int kDCH = 16;                                    // channels per staged chunk
+
+// Order-preserving key: -0 is first made +0 (the oracle compares with '<', so the two are equal); negative distances
+// (the expanded form can round below zero) flip all bits, the others only the sign bit.  NaN is filtered by the caller.
+__device__ __forceinline__ u64 wide_key(float d, int j) {
+    const unsigned u = __float_as_uint(d + 0.0f);
+    const unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+    return ((u64)o << 32) | (unsigned)j;
+}
+
+__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
+    const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
+    return ((u64)(unsigned)hi << 32) | (unsigned)lo;
+}
+
+__device__ __forceinline__ u64 readlane_u64(u64 v, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+    return ((u64)hi << 32) | lo;
+}
+
+// Ascending bitonic sort of the wave's 64 E keys, element e = lane + 64 h in v[h] (knn.hip's box sort, E registers).
+template <int E>
+__device__ __forceinline__ void wave_bitonic(u64 (&v)[E], int lane) {
+#pragma unroll
+    for (int kk = 2; kk <= 64 * E; kk <<= 1) {
+#pragma unroll
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            if (j >= 64) {
+                const int hj = j >> 6;
+#pragma unroll
+                for (int h = 0; h < E; h++) {
+                    if (h & hj) continue;
+                    const bool asc = ((lane + 64 * h) & kk) == 0;
+                    const u64 a = v[h], b = v[h | hj];
+                    const bool sw = asc ? b < a : a < b;
+                    v[h] = sw ? b : a;
+                    v[h | hj] = sw ? a : b;
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < E; h++) {
+                    const int i = lane + 64 * h;
+                    const u64 o = shfl_xor_u64(v[h], j);
+                    const bool take_min = ((i & j) == 0) == ((i & kk) == 0);
+                    v[h] = take_min ? (o < v[h] ? o : v[h]) : (o < v[h] ? v[h] : o);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void wide_sqnorm_kernel(int c, int n, const float *__restrict__ x, float *__restrict__ sq) {
+    // sq[b][i] = sum_c x[b,c,i]^2 as an fma chain in channel order (the oracle's |x_j|^2)
+    const int smp = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *xb = x + (size_t)smp * c * n;
+    float s = 0.f;
+    for (int ch = 0; ch < c; ch++) {
+        const float v = xb[(size_t)ch * n + i];
+        s = __builtin_fmaf(v, v, s);
+    }
+    sq[(size_t)smp * n + i] = s;
+}
+
+// c >= 4: distances of queries q0 + [0, nq) against all n candidates of samples s0 + blockIdx.z, to
+// D[blockIdx.z][q - q0][j].  Workgroup = 4 waves, 128 queries x 128 candidates; wave w owns queries w*32 + [0, 32) against
+// the four 32-candidate tiles (four independent accumulator chains).  MFMA A = queries, B = candidates, so accumulator
+// register r of lane (half, col) is query (r & 3) + 8 (r >> 2) + 4 half, candidate col: the stores of a register are
+// 32 consecutive candidates of one row.
+__global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq, int q0, int s0, const float *__restrict__ x,
+                                                            const float *__restrict__ sq, float *__restrict__ D) {
+    constexpr int E = kDCH * kDT / 256;  // elements per thread per operand per chunk
+    __shared__ __attribute__((aligned(16))) float sQ[2][kDCH][kDT];
+    __shared__ __attribute__((aligned(16))) float sC[2][kDCH][kDT];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, col = lane & 31;
+    const int smp = s0 + (int)blockIdx.z;
+    const float *xb = x + (size_t)smp * c * n;
+    const float *sqb = sq + (size_t)smp * n;
+    const int qt = blockIdx.x * kDT, ct = blockIdx.y * kDT;  // first local query / first candidate of the workgroup
+    const int nch = pcc::ceil_div(c, kDCH);
+
+    float pq[E], pc[E];
+    // loads at clamped addresses (issued before the MFMAs of the current chunk); the out-of-range select at commit
+    auto fetch = [&](int ch0) {
+#pragma unroll
+        for (int i = 0; i < E; i++) {
+            const int e = tid + i * 256, ch = min(ch0 + (e >> 7), c - 1), p = e & (kDT - 1);
+            pq[i] = xb[(size_t)ch * n + min(q0 + qt + p, n - 1)];
+            pc[i] = xb[(size_t)ch * n + min(ct + p, n - 1)];
+        }
+    };
+    auto commit = [&](int ch0, int buf) {
+#pragma unroll
+        for (int i = 0; i < E; i++) {
+            const int e = tid + i * 256, ch = e >> 7, p = e & (kDT - 1);
+            const bool cin = ch0 + ch < c;
+            sQ[buf][ch][p] = (cin && qt + p < nq) ? pq[i] : 0.f;  // (zero channels extend the chain exactly)
+            sC[buf][ch][p] = (cin && ct + p < n) ? pc[i] : 0.f;
+        }
+    };
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) acc[u] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    fetch(0);
+    commit(0, 0);
+    __syncthreads();
+    for (int t = 0; t < nch; t++) {
+        const int buf = t & 1;
+        if (t + 1 < nch) fetch((t + 1) * kDCH);
+#pragma unroll
+        for (int ks = 0; ks < kDCH / 2; ks++) {
+            const float a = sQ[buf][2 * ks + half][w * 32 + col];  // query[row = col][k = half] of channel pair ks
+            float bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) bv[u] = sC[buf][2 * ks + half][u * 32 + col];
+#pragma unroll
+            for (int u = 0; u < 4; u++) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv[u], acc[u], 0, 0, 0);
+        }
+        if (t + 1 < nch) commit((t + 1) * kDCH, buf ^ 1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int j = ct + u * 32 + col;
+        const float sqj = sqb[min(j, n - 1)];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int ql = qt + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (ql < nq && j < n) {
+                // the reference CPU path: dist = -2*dot ; dist += |xj|^2 ; dist += |xi|^2
+                const float d = (-2.0f * acc[u][r] + sqj) + sqb[q0 + ql];
+                D[((size_t)blockIdx.z * nq + ql) * n + j] = d;
+            }
+        }
+    }
+}
+
+struct WideSelArgs {
+    int c, n, k;
+    int rows;         // queries of this launch: row r is sample s0 + r / nq, query q0 + r % nq
+    int nq, q0, s0;
+    const float *x;   // DIFF: the cloud [b][c][n]
+    const float *D;   // otherwise: distances [rows][n]
+    int64_t *out;     // [b][n][k]
+};
+
+constexpr int kSelW = 4;  // waves (= queries) per selection workgroup
+
+// L = list slots (64 or 128, >= k).  One wave per query; see the file header.
+template <int L, bool DIFF>
+__global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs a) {
+    constexpr int R = L / 64;  // list keys per lane
+    __shared__ u64 sbuf[kSelW][L];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int row = (int)blockIdx.x * kSelW + w;
+    if (row >= a.rows) return;  // (whole wave; the kernel has no workgroup barrier)
+    u64 *buf = sbuf[w];
+    const int n = a.n, k = a.k;
+    const int smp = a.s0 + row / a.nq, q = a.q0 + row % a.nq;
+
+    const float *xb = nullptr, *drow = nullptr;
+    float qc[3] = {0.f, 0.f, 0.f};
+    if (DIFF) {
+        xb = a.x + (size_t)smp * a.c * n;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) qc[ch] = ch < a.c ? xb[(size_t)ch * n + q] : 0.f;
+    } else {
+        drow = a.D + (size_t)row * n;
+    }
+    auto dist = [&](int j) -> float {
+        if (DIFF) {
+            // sum over the channels in channel order: df0^2, then fma(df, df, acc)
+            float acc = 0.f;
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                if (ch < a.c) {
+                    const float df = xb[(size_t)ch * n + j] - qc[ch];
+                    acc = ch == 0 ? df * df : __builtin_fmaf(df, df, acc);
+                }
+            }
+            return acc;
+        }
+        return drow[j];
+    };
+
+    u64 list[R];
+#pragma unroll
+    for (int h = 0; h < R; h++) list[h] = kWideKeyMax;
+    u64 thr = kWideKeyMax;  // the k-th key of the list: nothing at or above it can end among the k nearest
+    int cnt = 0;            // keys in the buffer (wave-uniform)
+
+    auto merge = [&]() {
+        __builtin_amdgcn_wave_barrier();
+        u64 v[2 * R];
+#pragma unroll
+        for (int h = 0; h < R; h++) {
+            v[h] = list[h];
+            v[R + h] = lane + 64 * h < cnt ? buf[lane + 64 * h] : kWideKeyMax;
+        }
+        __builtin_amdgcn_wave_barrier();
+        wave_bitonic<2 * R>(v, lane);
+#pragma unroll
+        for (int h = 0; h < R; h++) list[h] = v[h];
+        const u64 kth = (R == 1 || k <= 64) ? list[0] : list[R - 1];
+        thr = readlane_u64(kth, (k - 1) & 63);
+        cnt = 0;
+    };
+
+    constexpr int U = 4;  // candidate blocks of 64 whose loads are issued together
+    for (int j0 = 0; j0 < n; j0 += 64 * U) {
+        float d[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) d[u] = dist(min(j0 + 64 * u + lane, n - 1));
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int j = j0 + 64 * u + lane;
+            if (j0 + 64 * u >= n) break;  // (wave-uniform)
+            const u64 key = wide_key(d[u], j);
+            bool pass = j < n && d[u] == d[u] && key < thr;  // (a NaN distance never enters)
+            u64 m = __ballot(pass);
+            int np = __popcll(m);
+            if (cnt + np > L) {
+                merge();
+                pass = pass && key < thr;
+                m = __ballot(pass);
+                np = __popcll(m);
+            }
+            if (pass) buf[cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = key;
+            cnt += np;
+        }
+    }
+    if (cnt > 0) merge();
+
+    int64_t *dst = a.out + ((size_t)smp * n + q) * k;
+#pragma unroll
+    for (int h = 0; h < R; h++) {
+        const int s = lane + 64 * h;
+        if (s < k) {
+            const unsigned j = (unsigned)list[h];
+            dst[s] = (int64_t)(j < (unsigned)n ? (int)j : n - 1);  // (an empty slot only when distances are NaN)
+        }
+    }
+}
+
+struct WsBlock {  // stream-ordered workspace block, freed behind the work enqueued so far
+    void *p = nullptr;
+    hipStream_t st;
+    explicit WsBlock(hipStream_t s) : st(s) {}
+    ~WsBlock() {
+        if (p) (void)pcc::ws_free(p, st);
+    }
+    bool alloc(size_t bytes) {
+        if (pcc::ws_malloc(&p, bytes, st) != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();
+            pcc::set_error(PCC_ENOMEM, "knn: workspace allocation failed");
+            return false;
+        }
+        return true;
+    }
+};
+
+template <int L, bool DIFF>
+void launch_select(const WideSelArgs &a, hipStream_t st) {
+    pcc::ProfScope prof("knn_wide_select_kernel", st);
+    hipLaunchKernelGGL((knn_wide_select_kernel<L, DIFF>), dim3(pcc::ceil_div(a.rows, kSelW)), dim3(64 * kSelW), 0, st, a);
+}
+
+template <bool DIFF>
+void launch_select(const WideSelArgs &a, hipStream_t st) {
+    if (a.k <= 64) launch_select<64, DIFF>(a, st);
+    else launch_select<128, DIFF>(a, st);
+}
+
+}  // namespace
+
+namespace pcc {
+
+// Sizes are validated by pcc_knn: 1 <= k <= min(n, 128), b <= 65535, non-null pointers.
+int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st) {
+    WideSelArgs a{};
+    a.c = c; a.n = n; a.k = k; a.x = x; a.out = indices;
+    if (c <= 3) {
+        a.rows = b * n; a.nq = n; a.q0 = 0; a.s0 = 0;
+        launch_select<true>(a, st);
+        return check_launch("knn(wide select)");
+    }
+    // distance rows per launch pair: whole samples while they fit, otherwise a multiple of 128 queries of one sample
+    const size_t cap = kWideRowsBytes / sizeof(float);
+    const size_t per_smp = (size_t)n * n;
+    int ns, nq;
+    if (per_smp <= cap) {
+        ns = (int)std::min<size_t>((size_t)b, cap / per_smp);
+        nq = n;
+    } else {
+        ns = 1;
+        nq = (int)std::min<size_t>((size_t)n, std::max<size_t>(kDT, cap / n / kDT * kDT));
+    }
+    WsBlock sq(st), dw(st);
+    if (!sq.alloc((size_t)b * n * sizeof(float)) || !dw.alloc((size_t)ns * nq * n * sizeof(float))) return PCC_ENOMEM;
+    float *sqp = static_cast<float *>(sq.p), *D = static_cast<float *>(dw.p);
+    hipLaunchKernelGGL(wide_sqnorm_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, st, c, n, x, sqp);
+    if (int rc = check_launch("knn(wide sqnorm)")) return rc;
+    a.D = D;
+    for (int s0 = 0; s0 < b; s0 += ns) {
+        const int cs = std::min(ns, b - s0);
+        for (int q0 = 0; q0 < n; q0 += nq) {
+            const int cq = std::min(nq, n - q0);
+            {
+                pcc::ProfScope prof("knn_wide_dist_kernel", st);
+                hipLaunchKernelGGL(knn_wide_dist_kernel, dim3(ceil_div(cq, kDT), ceil_div(n, kDT), cs), dim3(256), 0, st, c, n, cq,
+                                   q0, s0, x, sqp, D);
+            }
+            if (int rc = check_launch("knn(wide distances)")) return rc;
+            a.rows = cs * cq; a.nq = cq; a.q0 = q0; a.s0 = s0;
+            launch_select<false>(a, st);
+            if (int rc = check_launch("knn(wide select)")) return rc;
+        }
+    }
+    return PCC_OK;
+}
+
+}  // namespace pcc

@@ -94,6 +94,10 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
 constexpr int kSortBox = 16;
 int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st);
 
+// k-NN graph outside the range of knn.hip's kernels (knn_wide.hip): any c >= 1, 1 <= k <= min(n, 128); sizes and
+// pointers already validated by pcc_knn.
+int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st);
+
 // true while `st` is being captured into a graph (a failed query counts as not capturing)
 bool capturing(hipStream_t st);
 

@@ -190,7 +190,7 @@ class SquareDistance:
 
     def argKmin(self, K: int, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
         """``[B,N,K]`` int64 nearest neighbours, ascending; implemented for a cloud against itself
-        (``pykeops_knn``, neighbour_ops.py:77-82)."""
+        (``pykeops_knn``, neighbour_ops.py:77-82), any feature width, ``K <= min(N, 128)``."""
         ax = self._axis(axis, dim)
         same = (self.rows.data_ptr() == self.cols.data_ptr() and self.rows.shape == self.cols.shape
                 and self.rows.stride() == self.cols.stride())

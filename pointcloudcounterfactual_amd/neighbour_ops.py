@@ -95,7 +95,8 @@ def torch_knn(x: torch.Tensor, k: int) -> torch.Tensor:
 
 
 def hip_knn(x: torch.Tensor, k: int) -> torch.Tensor:
-    """``x[B,C,N] -> indices[B,N,k]`` int64, ascending distance, ties by ascending index (replaces ``pykeops_knn``)."""
+    """``x[B,C,N] -> indices[B,N,k]`` int64, ascending distance, ties by ascending index (replaces ``pykeops_knn``).
+    Any channel count C >= 1 and ``1 <= k <= min(N, 128)``."""
     x = x.contiguous()
     _prep(x)
     b, c, n = x.shape
