@@ -36,6 +36,7 @@
 // (one read of match each).
 #include "pcc_common.hpp"
 #include "pcc_test_hooks.h"
+#include "wave_sort.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -1106,7 +1107,7 @@ __global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a
         qx[j] = Q[q];
         qy[j] = Q[a.q_n4 + q];
         qz[j] = Q[2 * a.q_n4 + q];
-        bk[j] = ((unsigned long long)__float_as_uint(__builtin_inff()) << 32) | 0x7fffffffull;
+        bk[j] = pcc::kKeyInf;
     }
     const float4 *gb = reinterpret_cast<const float4 *>(a.q_box + ((size_t)smp * a.q_nb + grp) * 8);
     const float4 glo = gb[0], ghi = gb[1];
@@ -1155,51 +1156,12 @@ __global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a
     float r = __builtin_inff();  // the group's radius: the largest of its queries' best distances so far
     for (int b0 = 0; b0 < a.c_nb; b0 += 128) {  // windows of 128 candidate blocks (2048 candidates)
         // every lane: two blocks of the window, keyed by the lower bound of every distance between the group's box and
-        // the block's box.  key = lower bound with its 7 lowest mantissa bits replaced by the block's slot: positive
-        // floats order like unsigned integers, and the truncation only makes the bound smaller (conservative)
+        // the block's box (the candidates' own chain); nearest boxes first
         unsigned key[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int blk = b0 + lane + 64 * h;
-            key[h] = 0xffffffffu;
-            if (blk < a.c_nb) {
-                const float4 *cb = reinterpret_cast<const float4 *>(a.c_box + ((size_t)smp * a.c_nb + blk) * 8);
-                const float4 lo = cb[0], hi = cb[1];
-                const float dx = fmaxf(fmaxf(glo.x - hi.x, lo.x - ghi.x), 0.f);
-                const float dy = fmaxf(fmaxf(glo.y - hi.y, lo.y - ghi.y), 0.f);
-                const float dz = fmaxf(fmaxf(glo.z - hi.z, lo.z - ghi.z), 0.f);
-                key[h] = (__float_as_uint(sq3(dx, dy, dz)) & ~127u) | (unsigned)(lane + 64 * h);  // (the candidates' own chain: monotone)
-            }
-        }
-        // ascending bitonic sort of the 128 keys held by the wave (element lane + 64 h): nearest boxes first
-#pragma unroll
-        for (int k = 2; k <= 128; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                if (j == 64) {
-                    const unsigned mn = min(key[0], key[1]), mx = max(key[0], key[1]);
-                    key[0] = mn;
-                    key[1] = mx;
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const int i = lane + 64 * h;
-                        const unsigned other = (unsigned)__shfl_xor((int)key[h], j, 64);
-                        const bool take_min = ((i & j) == 0) == ((i & k) == 0);
-                        key[h] = take_min ? min(key[h], other) : max(key[h], other);
-                    }
-                }
-            }
-        }
+        pcc::sort_box_window(key, a.c_box, smp, a.c_nb, b0, glo, ghi, lane, sq3);
         // walk the window nearest-first; a block farther than the radius ends it (everything behind is farther still):
         // nothing that could win, or tie with a lower original index, is skipped.  Two blocks are in flight ahead.
         // (branch-free: a branch around the look-ahead loads makes the compiler drain them before every use)
-        auto key_at = [&](int p) -> unsigned {
-            const int pl = __builtin_amdgcn_readfirstlane(p) & 63;
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)key[0], pl);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)key[1], pl);
-            return p < 64 ? lo : hi;
-        };
         const int nwin = min(128, a.c_nb - b0);
         // batches of four blocks: their sixteen loads are issued together, each block is consumed as soon as ITS loads
         // have landed (straight-line code: the compiler counts the outstanding loads exactly), the radius is refreshed
@@ -1210,7 +1172,7 @@ __global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a
             Cand cc[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                kk[u] = key_at(min(p + u, nwin - 1));  // (past the end: the last block again, never consumed)
+                kk[u] = pcc::window_key(key, min(p + u, nwin - 1));  // (past the end: the last block again, never consumed)
                 cc[u] = load_block(b0 + (int)(kk[u] & 127u));
             }
 #pragma unroll
@@ -1228,9 +1190,7 @@ __global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a
     for (int j = 0; j < kFineQ; j++) {
 #pragma unroll
         for (int off = 1; off < kBox; off <<= 1) {
-            const unsigned hi = (unsigned)__shfl_xor((int)(bk[j] >> 32), off, 64);
-            const unsigned lo = (unsigned)__shfl_xor((int)(bk[j] & 0xffffffffu), off, 64);
-            const unsigned long long ok = ((unsigned long long)hi << 32) | lo;
+            const unsigned long long ok = pcc::shfl_xor_u64(bk[j], off);
             bk[j] = ok < bk[j] ? ok : bk[j];
         }
     }
@@ -2390,22 +2350,6 @@ int launch_phase(const PhaseArgs &a, int b, int var, hipStream_t st, const char 
     return launch_phase_rs<MODE, 1, 8>(a, b, var, st, what);
 }
 
-struct StreamBuf {  // stream-ordered scratch from the library's private pool (pcc::ws_malloc / ws_free)
-    void *p = nullptr;
-    hipStream_t st;
-    explicit StreamBuf(hipStream_t s) : st(s) {}
-    int alloc(size_t bytes) {
-        if (pcc::ws_malloc(&p, bytes, st) != hipSuccess) {
-            pcc::set_error(PCC_ENOMEM, "workspace allocation failed");
-            return PCC_ENOMEM;
-        }
-        return PCC_OK;
-    }
-    ~StreamBuf() {
-        if (p) (void)pcc::ws_free(p, st);
-    }
-};
-
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 size_t cost_parts(int n, int m) { return (size_t)pcc::ceil_div(n, kMatKT) * pcc::ceil_div(m, kMatLT); }
@@ -2775,8 +2719,8 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
     const size_t part1_off = up(cpart_off + (size_t)b * col_blocks * row_tiles * 4);
     const size_t part2_off = up(part1_off + (grad ? (size_t)b * row_tiles * L.n4 * 3 * 4 : 0));
     const size_t total = up(part2_off + (grad ? (size_t)b * col_blocks * L.m4 * 3 * 4 : 0));
-    StreamBuf ws(st);
-    if (int rc = ws.alloc(total)) return rc;
+    pcc::WsBlock ws(st);
+    if (int rc = ws.alloc(total, "workspace allocation failed")) return rc;
     char *base = static_cast<char *>(ws.p);
     const size_t nm4 = (size_t)L.n4 + L.m4;
     // pair + finish kernels of the samples [s0, s0 + bc) on `lst` (every section of the workspace is indexed by sample)
@@ -2904,9 +2848,9 @@ int pcc_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, f
     if (b == 0 || n == 0 || m == 0) return PCC_OK;
     if (!xyz1 || !xyz2 || !match || !temp) return pcc::invalid("approxmatch: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    StreamBuf ws(st);
+    pcc::WsBlock ws(st);
     const size_t bytes = WsLayout(b, n, m).total;
-    if (int rc = ws.alloc(bytes)) return rc;
+    if (int rc = ws.alloc(bytes, "workspace allocation failed")) return rc;
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, ws.p, bytes, nullptr, st);
 }
 
@@ -2922,9 +2866,9 @@ int pcc_approxmatch_cost(int b, int n, int m, const float *xyz1, const float *xy
         return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, "approxmatch_cost: memset failed"), (int)e);
     }
     if (!xyz1 || !xyz2 || !match || !temp) return pcc::invalid("approxmatch_cost: null pointer");
-    StreamBuf ws(st);
+    pcc::WsBlock ws(st);
     const size_t bytes = pcc_approxmatch_workspace_bytes(b, n, m);
-    if (int rc = ws.alloc(bytes)) return rc;
+    if (int rc = ws.alloc(bytes, "workspace allocation failed")) return rc;
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, ws.p, bytes, cost, st);
 }
 
@@ -2964,8 +2908,8 @@ int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, con
     }
     if (!xyz1 || !xyz2 || !match) return pcc::invalid("matchcost: null pointer");
     const int tiles = pcc::ceil_div(m, kRowRT);
-    StreamBuf ws(st);
-    if (int rc = ws.alloc((size_t)b * tiles * sizeof(float))) return rc;
+    pcc::WsBlock ws(st);
+    if (int rc = ws.alloc((size_t)b * tiles * sizeof(float), "workspace allocation failed")) return rc;
     float *part = static_cast<float *>(ws.p);
     const bool vec = (n % 4 == 0) && aligned16(match);
     {
@@ -2998,9 +2942,9 @@ int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float
     if (!xyz1 || !xyz2 || !match || !grad1 || !grad2) return pcc::invalid("matchcostgrad: null pointer");
     const bool vec = (n % 4 == 0) && aligned16(match);
     const int row_tiles = pcc::ceil_div(m, kGradRT), slabs = pcc::ceil_div(n, kGradSlab);
-    StreamBuf ws(st);
+    pcc::WsBlock ws(st);
     const size_t p1_elems = (size_t)b * row_tiles * n * 3, p2_elems = slabs > 1 ? (size_t)b * slabs * m * 3 : 0;
-    if (int rc = ws.alloc((p1_elems + p2_elems) * sizeof(float))) return rc;
+    if (int rc = ws.alloc((p1_elems + p2_elems) * sizeof(float), "workspace allocation failed")) return rc;
     float *part1 = static_cast<float *>(ws.p);
     float *part2 = slabs > 1 ? part1 + p1_elems : grad2;  // a single slab writes grad2 directly
     {

@@ -336,24 +336,15 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
         if (C > 1 && lds <= 160 * 1024 - 256) {
             pcc::CoresidentGate gate(pcc::kAuctionCluster, st);  // declines while capturing: auction_kernel below, same bits
             if (gate.ok) {
-                static bool attr2 = [] {  // the kernel also has a few bytes of static LDS (barrier flag)
-                    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(auction_cluster_kernel),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
-                    if (!ok) (void)hipGetLastError();
-                    return ok;
-                }();
-                (void)attr2;
+                // (the kernel also has a few bytes of static LDS: barrier flag)
+                (void)pcc::allow_lds<auction_cluster_kernel>(160 * 1024 - 256);
                 const int group = std::max(1, cus / C);          // samples per launch
                 const size_t sync_words = 1 + (size_t)b * (2 + iters);
                 const size_t bytes = (size_t)b * 4 * n * 4 + sync_words * 4;
-                char *ws = nullptr;
-                if (pcc::ws_malloc(reinterpret_cast<void **>(&ws), bytes, st) != hipSuccess) {
-                    (void)hipGetLastError();
-                    pcc::set_error(PCC_ENOMEM, "auction: workspace allocation failed");
-                    return PCC_ENOMEM;
-                }
-                int *scratch = reinterpret_cast<int *>(ws);
-                unsigned *sync = reinterpret_cast<unsigned *>(ws + (size_t)b * 4 * n * 4);
+                pcc::WsBlock ws(st);
+                if (int rc = ws.alloc(bytes, "auction: workspace allocation failed")) return rc;
+                int *scratch = static_cast<int *>(ws.p);
+                unsigned *sync = reinterpret_cast<unsigned *>(static_cast<char *>(ws.p) + (size_t)b * 4 * n * 4);
                 (void)hipMemsetAsync(sync, 0, sync_words * 4, st);
                 if (gate.inject) (void)hipMemsetAsync(sync, 1, 1, st);  // test hook: start with the error word raised
                 for (int s0 = 0; s0 < b; s0 += group) {
@@ -362,7 +353,6 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
                     hipLaunchKernelGGL(auction_cluster_kernel, dim3((unsigned)(gb * C)), dim3(1024), lds, st, n, C, xyz1, xyz2, eps,
                                        iters, dist, assignment, scratch, sync, s0, gate.sticky);
                 }
-                (void)pcc::ws_free(ws, st);
                 return pcc::check_launch("auction_forward(cluster)");
             }
         }
@@ -370,23 +360,16 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
     const size_t hot = (size_t)5 * n * 4 + 16, state = (size_t)5 * n * 4;
     const int in_lds = hot + state <= 160 * 1024;
     const size_t lds = in_lds ? hot + state : hot;
-    static bool attr_done = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(auction_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    }();
-    (void)attr_done;
-    int *scratch = nullptr;
-    if (!in_lds && pcc::ws_malloc(reinterpret_cast<void **>(&scratch), (size_t)b * state, st) != hipSuccess) {
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "auction: workspace allocation failed");
-        return PCC_ENOMEM;
+    (void)pcc::allow_lds<auction_kernel>(160 * 1024);
+    pcc::WsBlock scratch(st);
+    if (!in_lds) {
+        if (int rc = scratch.alloc((size_t)b * state, "auction: workspace allocation failed")) return rc;
     }
     {
         pcc::ProfScope prof("auction_kernel", st);
         hipLaunchKernelGGL(auction_kernel, dim3(b), dim3(1024), lds, st, n, xyz1, xyz2, eps, iters, dist, assignment,
-                           scratch, in_lds);
+                           static_cast<int *>(scratch.p), in_lds);
     }
-    if (scratch) (void)pcc::ws_free(scratch, st);
     return pcc::check_launch("auction_forward");
 }
 

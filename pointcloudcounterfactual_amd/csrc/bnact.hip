@@ -230,19 +230,15 @@ int pcc_bn_stats(int b, int c, int n, const float *z, float *mean, float *var, p
     if (!z || !mean || !var) return pcc::invalid("bn_stats: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int splits = pick_splits(b, c);
-    double *part = nullptr;
-    if (pcc::ws_malloc(reinterpret_cast<void **>(&part), (size_t)c * splits * 2 * sizeof(double), st) != hipSuccess) {
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "bn_stats: workspace allocation failed");
-        return PCC_ENOMEM;
-    }
+    pcc::WsBlock ws(st);
+    if (int rc = ws.alloc((size_t)c * splits * 2 * sizeof(double), "bn_stats: workspace allocation failed")) return rc;
+    double *part = static_cast<double *>(ws.p);
     {
         pcc::ProfScope prof("bn_stats_partial_kernel", st);
         hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(c, splits), dim3(256), 0, st, b, c, n, splits, z, part);
     }
     hipLaunchKernelGGL((bn_finalize_kernel<0>), dim3(pcc::ceil_div(c, 256)), dim3(256), 0, st, c, splits, (double)b * n, part,
                        mean, var);
-    (void)pcc::ws_free(part, st);
     return pcc::check_launch("bn_stats");
 }
 
@@ -273,20 +269,18 @@ int pcc_bn_relu_bwd(int b, int c, int n, const float *z, const float *mean, cons
     if ((long long)b * c > 65535LL) return pcc::invalid("bn_relu_bwd: more than 65535 (sample, channel) rows");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int splits = pick_splits(b, c);
-    double *part = nullptr;
-    if (pcc::ws_malloc(reinterpret_cast<void **>(&part), (size_t)c * splits * 2 * sizeof(double), st) != hipSuccess) {
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "bn_relu_bwd: workspace allocation failed");
-        return PCC_ENOMEM;
+    {  // the partial sums are freed before the apply launch
+        pcc::WsBlock ws(st);
+        if (int rc = ws.alloc((size_t)c * splits * 2 * sizeof(double), "bn_relu_bwd: workspace allocation failed")) return rc;
+        double *part = static_cast<double *>(ws.p);
+        {
+            pcc::ProfScope prof("bn_relu_bwd_partial_kernel", st);
+            hipLaunchKernelGGL(bn_relu_bwd_partial_kernel, dim3(c, splits), dim3(256), 0, st, b, c, n, splits, z, mean, var, eps,
+                               gamma, beta, grad_y, part);
+        }
+        hipLaunchKernelGGL((bn_finalize_kernel<1>), dim3(pcc::ceil_div(c, 256)), dim3(256), 0, st, c, splits, 1.0, part,
+                           grad_beta, grad_gamma);
     }
-    {
-        pcc::ProfScope prof("bn_relu_bwd_partial_kernel", st);
-        hipLaunchKernelGGL(bn_relu_bwd_partial_kernel, dim3(c, splits), dim3(256), 0, st, b, c, n, splits, z, mean, var, eps,
-                           gamma, beta, grad_y, part);
-    }
-    hipLaunchKernelGGL((bn_finalize_kernel<1>), dim3(pcc::ceil_div(c, 256)), dim3(256), 0, st, c, splits, 1.0, part, grad_beta,
-                       grad_gamma);
-    (void)pcc::ws_free(part, st);
     {
         pcc::ProfScope prof("bn_relu_bwd_apply_kernel", st);
         const float inv_count = 1.0f / ((float)b * (float)n);

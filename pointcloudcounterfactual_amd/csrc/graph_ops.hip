@@ -8,6 +8,7 @@
 #include "pcc_common.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 #include "pcc_neighbour.h"
 #include "pcc_test_hooks.h"
 
@@ -749,21 +750,17 @@ int gather_fwd(int b, int c, int n, int k, const float *x, const int64_t *indice
     }
     const dim3 grid((unsigned)(pcc::ceil_div(c, cb) * b));
     pcc::ProfScope prof(what, st);
-#define PCC_LAUNCH(CB)                                                                                              \
-    do {                                                                                                            \
-        static bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(gather_lds_kernel<MODE, CB>),         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; \
-        (void)attr;                                                                                                 \
-        hipLaunchKernelGGL((gather_lds_kernel<MODE, CB>), grid, dim3(1024), lds, st, c, n, k, x, indices, out, argmax, tsel, \
-                           stage_off);                                                                              \
-    } while (0)
+    auto launch = [&](auto CB) {
+        (void)pcc::allow_lds<gather_lds_kernel<MODE, CB>>(160 * 1024);
+        hipLaunchKernelGGL((gather_lds_kernel<MODE, CB>), grid, dim3(1024), lds, st, c, n, k, x, indices, out, argmax, tsel,
+                           stage_off);
+    };
     switch (cb) {
-    case 8: PCC_LAUNCH(8); break;
-    case 4: PCC_LAUNCH(4); break;
-    case 2: PCC_LAUNCH(2); break;
-    default: PCC_LAUNCH(1); break;
+    case 8: launch(std::integral_constant<int, 8>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    default: launch(std::integral_constant<int, 1>{}); break;
     }
-#undef PCC_LAUNCH
     return pcc::check_launch(what);
 }
 
@@ -780,22 +777,12 @@ int edge_stream_bwd(int b, int c, int n, int k, const int64_t *indices, const fl
     const size_t lds = lds_of(cb), lds_sort = ((size_t)2 * n + kEsCE) * sizeof(int);
     if (lds > 160 * 1024 - 256 || lds_sort > 160 * 1024 - 256) return -1;
     const size_t nk = (size_t)n * k;
-    char *ws = nullptr;
     const size_t ent_bytes = ((size_t)b * nk * sizeof(unsigned) + 15) & ~(size_t)15;
-    if (pcc::ws_malloc(reinterpret_cast<void **>(&ws), ent_bytes + (size_t)b * nk, st) != hipSuccess) {
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "graph op backward: workspace allocation failed");
-        return PCC_ENOMEM;
-    }
-    unsigned *ent = reinterpret_cast<unsigned *>(ws);
-    unsigned char *flg = reinterpret_cast<unsigned char *>(ws + ent_bytes);
-    static bool attr_sort = [] {
-        const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(edge_chunk_sort_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        return ok;
-    }();
-    (void)attr_sort;
+    pcc::WsBlock ws(st);
+    if (int rc = ws.alloc(ent_bytes + (size_t)b * nk, "graph op backward: workspace allocation failed")) return rc;
+    unsigned *ent = static_cast<unsigned *>(ws.p);
+    unsigned char *flg = static_cast<unsigned char *>(ws.p) + ent_bytes;
+    (void)pcc::allow_lds<edge_chunk_sort_kernel>(160 * 1024 - 256);
     {
         pcc::ProfScope prof("edge_chunk_sort_kernel", st);
         hipLaunchKernelGGL(edge_chunk_sort_kernel, dim3((unsigned)pcc::ceil_div(n, P), (unsigned)b), dim3(1024), lds_sort, st, n, k, P,
@@ -803,17 +790,8 @@ int edge_stream_bwd(int b, int c, int n, int k, const int64_t *indices, const fl
     }
     if (MODE == 1) {
         const long long wgs = (long long)pcc::ceil_div(n, kSelfPts) * b * c;
-        if (wgs > 0x7fffffffLL) {
-            (void)pcc::ws_free(ws, st);
-            return -1;
-        }
-        static bool attr_self = [] {
-            const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(edge_self_sum_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
-            if (!ok) (void)hipGetLastError();
-            return ok;
-        }();
-        (void)attr_self;
+        if (wgs > 0x7fffffffLL) return -1;
+        (void)pcc::allow_lds<edge_self_sum_kernel>(160 * 1024 - 256);
         pcc::ProfScope prof("edge_self_sum_kernel", st);
         hipLaunchKernelGGL(edge_self_sum_kernel, dim3((unsigned)wgs), dim3(256), (size_t)kSelfPts * k * sizeof(float), st, c, n, k, g,
                            grad_x);
@@ -821,22 +799,14 @@ int edge_stream_bwd(int b, int c, int n, int k, const int64_t *indices, const fl
     const dim3 grid((unsigned)(pcc::ceil_div(c, cb) * b));
     {
         pcc::ProfScope prof(MODE == 1 ? "edge_stream_bwd_kernel<features>" : "edge_stream_bwd_kernel<gather>", st);
-#define PCC_LAUNCH_E(CB)                                                                                                  \
-    do {                                                                                                                  \
-        static bool attr = [] {                                                                                           \
-            const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(edge_stream_bwd_kernel<MODE, CB>),         \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess; \
-            if (!ok) (void)hipGetLastError();                                                                             \
-            return ok;                                                                                                    \
-        }();                                                                                                              \
-        (void)attr;                                                                                                       \
-        hipLaunchKernelGGL((edge_stream_bwd_kernel<MODE, CB>), grid, dim3(kEsT), lds, st, c, n, k, P, ent, flg, g, grad_x); \
-    } while (0)
-        if (cb == 2) PCC_LAUNCH_E(2);
-        else PCC_LAUNCH_E(1);
-#undef PCC_LAUNCH_E
+        if (cb == 2) {
+            (void)pcc::allow_lds<edge_stream_bwd_kernel<MODE, 2>>(160 * 1024 - 256);
+            hipLaunchKernelGGL((edge_stream_bwd_kernel<MODE, 2>), grid, dim3(kEsT), lds, st, c, n, k, P, ent, flg, g, grad_x);
+        } else {
+            (void)pcc::allow_lds<edge_stream_bwd_kernel<MODE, 1>>(160 * 1024 - 256);
+            hipLaunchKernelGGL((edge_stream_bwd_kernel<MODE, 1>), grid, dim3(kEsT), lds, st, c, n, k, P, ent, flg, g, grad_x);
+        }
     }
-    (void)pcc::ws_free(ws, st);
     return pcc::check_launch("graph op backward (edge stream)");
 }
 
@@ -854,21 +824,16 @@ int scatter_bwd(int b, int c, int n, int k, const int64_t *indices, const int32_
     if (lds > 160 * 1024) return pcc::invalid("graph op backward: n too large for the LDS bins");
     const dim3 grid((unsigned)(pcc::ceil_div(c, cb) * b));
     pcc::ProfScope prof(what, st);
-#define PCC_LAUNCH(CB)                                                                                               \
-    do {                                                                                                             \
-        static bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(scatter_lds_kernel<MODE, CB>),         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; \
-        (void)attr;                                                                                                  \
-        hipLaunchKernelGGL((scatter_lds_kernel<MODE, CB>), grid, dim3(1024), lds, st, c, n, k, indices, argmax, g,   \
-                           grad_x);                                                                                  \
-    } while (0)
+    auto launch = [&](auto CB) {
+        (void)pcc::allow_lds<scatter_lds_kernel<MODE, CB>>(160 * 1024);
+        hipLaunchKernelGGL((scatter_lds_kernel<MODE, CB>), grid, dim3(1024), lds, st, c, n, k, indices, argmax, g, grad_x);
+    };
     switch (cb) {
-    case 8: PCC_LAUNCH(8); break;
-    case 4: PCC_LAUNCH(4); break;
-    case 2: PCC_LAUNCH(2); break;
-    default: PCC_LAUNCH(1); break;
+    case 8: launch(std::integral_constant<int, 8>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    default: launch(std::integral_constant<int, 1>{}); break;
     }
-#undef PCC_LAUNCH
     return pcc::check_launch(what);
 }
 
@@ -952,19 +917,10 @@ int pcc_neighbour_sum_bwd(int b, int c, int n, int k, const int64_t *indices, co
     const bool sorted_enabled = pcc::tuning(PCC_TUNE_NBRSUM_SCATTER) == 0;  // (measurement switch: the per-edge atomic scatter)
     // sorted-edge schedule: needs 16-bit point ids and rows + bins of >= 1 channel in LDS
     if (sorted_enabled && n <= 65536 && (size_t)n * 8 <= 128 * 1024 && (size_t)n * 4 <= 160 * 1024 - 256) {
-        unsigned *rev = nullptr;
-        if (pcc::ws_malloc(reinterpret_cast<void **>(&rev), (size_t)b * n * k * sizeof(unsigned), st) != hipSuccess) {
-            (void)hipGetLastError();
-            pcc::set_error(PCC_ENOMEM, "neighbour_sum_bwd: workspace allocation failed");
-            return PCC_ENOMEM;
-        }
-        static bool attr_sort = [] {
-            const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(edge_sort_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) == hipSuccess;
-            if (!ok) (void)hipGetLastError();
-            return ok;
-        }();
-        (void)attr_sort;
+        pcc::WsBlock ws(st);
+        if (int rc = ws.alloc((size_t)b * n * k * sizeof(unsigned), "neighbour_sum_bwd: workspace allocation failed")) return rc;
+        unsigned *rev = static_cast<unsigned *>(ws.p);
+        (void)pcc::allow_lds<edge_sort_kernel>(160 * 1024 - 256);
         {
             pcc::ProfScope prof("edge_sort_kernel", st);
             hipLaunchKernelGGL(edge_sort_kernel, dim3(b), dim3(1024), (size_t)n * sizeof(int), st, n, k, indices, rev);
@@ -975,15 +931,16 @@ int pcc_neighbour_sum_bwd(int b, int c, int n, int k, const int64_t *indices, co
         const dim3 grid((unsigned)(pcc::ceil_div(c, cb) * b));
         {
             pcc::ProfScope prof("nbrsum_bwd_sorted_kernel", st);
-#define PCC_LAUNCH_S(CB)                                                                                                  do {                                                                                                                      static bool attr = [] {                                                                                                   const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(nbrsum_bwd_sorted_kernel<CB>),                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;             if (!ok) (void)hipGetLastError();                                                                                     return ok;                                                                                                        }();                                                                                                                  (void)attr;                                                                                                           hipLaunchKernelGGL((nbrsum_bwd_sorted_kernel<CB>), grid, dim3(1024), lds, st, c, n, k, rev, grad_out, grad_x);     } while (0)
+            auto launch = [&](auto CB) {
+                (void)pcc::allow_lds<nbrsum_bwd_sorted_kernel<CB>>(160 * 1024);
+                hipLaunchKernelGGL((nbrsum_bwd_sorted_kernel<CB>), grid, dim3(1024), lds, st, c, n, k, rev, grad_out, grad_x);
+            };
             switch (cb) {
-            case 4: PCC_LAUNCH_S(4); break;
-            case 2: PCC_LAUNCH_S(2); break;
-            default: PCC_LAUNCH_S(1); break;
+            case 4: launch(std::integral_constant<int, 4>{}); break;
+            case 2: launch(std::integral_constant<int, 2>{}); break;
+            default: launch(std::integral_constant<int, 1>{}); break;
             }
-#undef PCC_LAUNCH_S
         }
-        (void)pcc::ws_free(rev, st);
         return pcc::check_launch("neighbour_sum_bwd(sorted)");
     }
     return scatter_bwd<3>(b, c, n, k, indices, nullptr, grad_out, grad_x, st, "scatter_lds_kernel<nbrsum>");

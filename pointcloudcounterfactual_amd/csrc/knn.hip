@@ -23,14 +23,17 @@
 #include "pcc_neighbour.h"
 #include "pcc_test_hooks.h"
 #include "topk.hpp"
+#include "wave_sort.hpp"
+
+#include <type_traits>
 
 namespace {
 
 constexpr int kCap = 16;     // FIFO slots per lane
 constexpr int kCH = 2048;    // candidates staged per chunk (small-c kernel)
 constexpr int kSortBoxK = pcc::kSortBox;
-constexpr int kTT128 = 1;
-constexpr int kSortedMaxN = 16384;  // the sort kernel orders up to 16384 points per cloud    // tiles per stage of the 128-channel MFMA instantiation
+constexpr int kTT128 = 1;  // tiles per stage of the 128-channel MFMA instantiation
+constexpr int kSortedMaxN = 16384;  // the sort kernel orders up to 16384 points per cloud
 
 template <int K, int S>
 struct SmallLayout {
@@ -168,7 +171,7 @@ __global__ __launch_bounds__(64 * S) void knn_small_kernel(int c, int n, int k, 
 constexpr int kSW = 4;     // independent waves per workgroup (no barrier; the workgroup only shares the LDS allocation)
 constexpr int kSQ = 16;    // queries per wave = one box of the sort
 constexpr int kSlices = 4; // candidate slices per query
-constexpr unsigned long long kKeyInf = ((unsigned long long)0x7f800000u << 32) | 0x7fffffffull;
+using pcc::kKeyInf;
 
 // One step of the insertion chain: (slot, carry) <- (min, max) of the two 64-bit keys.  Keys are unique, so once the
 // carry displaces an entry everything behind shifts.  One v_cmp_lt_u64 and four v_cndmask_b32 on ITS mask (written as
@@ -272,60 +275,24 @@ __global__ __launch_bounds__(64 * kSW, (K == 16 ? 3 : K <= 25 ? 4 : 1)) void knn
 
     for (int b0 = 0; b0 < a.nb; b0 += 128) {  // windows of 128 candidate blocks
         unsigned bkey[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int blk = b0 + lane + 64 * h;
-            bkey[h] = 0xffffffffu;
-            if (blk < a.nb) {
-                const float4 *cb = reinterpret_cast<const float4 *>(a.box + ((size_t)smp * a.nb + blk) * 8);
-                const float4 lo = cb[0], hi = cb[1];
-                const float dx = fmaxf(fmaxf(glo.x - hi.x, lo.x - ghi.x), 0.f);
-                const float dy = fmaxf(fmaxf(glo.y - hi.y, lo.y - ghi.y), 0.f);
-                const float dz = fmaxf(fmaxf(glo.z - hi.z, lo.z - ghi.z), 0.f);
-                // the candidates' own fma chain on the box gaps (every step is monotone: a true lower bound in f32), its 7
-                // lowest mantissa bits replaced by the slot: truncation only lowers the bound
-                const float lb = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                bkey[h] = (__float_as_uint(lb) & ~127u) | (unsigned)(lane + 64 * h);
-            }
-        }
-#pragma unroll
-        for (int kk = 2; kk <= 128; kk <<= 1) {  // ascending bitonic sort of the wave's 128 keys (element lane + 64 h)
-#pragma unroll
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                if (j == 64) {
-                    const unsigned mn = min(bkey[0], bkey[1]), mx = max(bkey[0], bkey[1]);
-                    bkey[0] = mn;
-                    bkey[1] = mx;
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const int i = lane + 64 * h;
-                        const unsigned other = (unsigned)__shfl_xor((int)bkey[h], j, 64);
-                        const bool take_min = ((i & j) == 0) == ((i & kk) == 0);
-                        bkey[h] = take_min ? min(bkey[h], other) : max(bkey[h], other);
-                    }
-                }
-            }
-        }
+        // the candidates' own fma chain on the box gaps
+        pcc::sort_box_window(bkey, a.box, smp, a.nb, b0, glo, ghi, lane, [](float dx, float dy, float dz) {
+            return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+        });
         const int nwin = min(128, a.nb - b0);
-        auto key_at = [&](int p) -> unsigned {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)bkey[0], p & 63);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)bkey[1], p & 63);
-            return p < 64 ? lo : hi;
-        };
         // a lane's four candidates of a block are 64 contiguous bytes; the next block's are in flight while this one is
         // consumed.  Rows past the cloud's end are loaded (the workspace is padded) and never offered.
         auto load4 = [&](float4 (&v)[4], int c0) {
 #pragma unroll
             for (int j = 0; j < 4; j++) v[j] = C[c0 + cs * 4 + j];
         };
-        unsigned bk = key_at(0);
+        unsigned bk = pcc::window_key(bkey, 0);
         float4 cur[4], nxt[4];
         load4(cur, (b0 + (int)(bk & 127u)) * kSortBoxK);
         for (int p = 0; p < nwin; p++) {
             if (__uint_as_float(bk & ~127u) > r) break;  // everything behind is farther still
             const int c0 = (b0 + (int)(bk & 127u)) * kSortBoxK;
-            const unsigned bk_next = key_at(min(p + 1, nwin - 1));
+            const unsigned bk_next = pcc::window_key(bkey, min(p + 1, nwin - 1));
             load4(nxt, (b0 + (int)(bk_next & 127u)) * kSortBoxK);
             if (__any(cnt > kCap - 4)) flush();
             const int left = n - c0 - cs * 4;  // real candidates from cur[0] on
@@ -916,6 +883,25 @@ __global__ __launch_bounds__(512) void knn_mfma_split_kernel(int c, int n, int k
     }
 }
 
+// list slots of the instantiations for k <= 32
+constexpr int kSlots[] = {4, 8, 16, 20, 25, 32};
+
+// f(std::integral_constant<int, K>) for the fewest slots K >= k (1 <= k <= 32)
+template <int I = 0, class F>
+int with_slots(int k, F &&f) {
+    if constexpr (I + 1 < (int)(sizeof kSlots / sizeof kSlots[0])) {
+        if (k > kSlots[I]) return with_slots<I + 1>(k, f);
+    }
+    return f(std::integral_constant<int, kSlots[I]>{});
+}
+
+// the next smaller instantiation (0 below the first): the sorted kernel of K serves k in (prev_slots(K), K]
+constexpr int prev_slots(int K) {
+    int p = 0;
+    for (int s : kSlots) p = s < K ? s : p;
+    return p;
+}
+
 template <int K>
 int launch_small(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st) {
     pcc::ProfScope prof("knn_small_kernel", st);
@@ -923,38 +909,23 @@ int launch_small(int b, int c, int n, int k, const float *x, int64_t *indices, h
     return PCC_OK;
 }
 
-template <int K, int KPREV>
-void launch_sorted(const KnnSortedArgs &a, hipStream_t st) {
+template <int K>
+int launch_sorted(const KnnSortedArgs &a, hipStream_t st) {
     pcc::ProfScope prof("knn_sorted_kernel", st);
     const int waves = a.batch * a.nb;
-    hipLaunchKernelGGL((knn_sorted_kernel<K, KPREV>), dim3(pcc::ceil_div(waves, kSW)), dim3(64 * kSW), 0, st, a);
+    hipLaunchKernelGGL((knn_sorted_kernel<K, prev_slots(K)>), dim3(pcc::ceil_div(waves, kSW)), dim3(64 * kSW), 0, st, a);
+    return PCC_OK;
 }
-
-struct SqBuf {  // stream-ordered workspace block, freed behind the work enqueued so far
-    float *p = nullptr;
-    hipStream_t st;
-    explicit SqBuf(hipStream_t s) : st(s) {}
-    ~SqBuf() {
-        if (p) (void)pcc::ws_free(p, st);
-    }
-};
 
 template <int K, int CP>
 int launch_split(int b, int c, int n, int k, const float *x, const float *sq, int64_t *indices, hipStream_t st) {
     constexpr int lds = split_lds_bytes<K, CP>();
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_mfma_split_kernel<K, CP>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) {
+    if (const hipError_t attr = pcc::allow_lds<knn_mfma_split_kernel<K, CP>>(lds)) {
         pcc::set_error((int)attr, "knn: cannot reserve the role-split kernel's LDS");
         return (int)attr;
     }
-    SqBuf logs(st);  // the selection waves' records (stream-ordered: freed behind the kernel)
-    if (pcc::ws_malloc(reinterpret_cast<void **>(&logs.p), split_log_bytes(b, n), st) != hipSuccess) {
-        logs.p = nullptr;
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "knn: workspace allocation failed");
-        return PCC_ENOMEM;
-    }
+    pcc::WsBlock logs(st);  // the selection waves' records (stream-ordered: freed behind the kernel)
+    if (int rc = logs.alloc(split_log_bytes(b, n), "knn: workspace allocation failed")) return rc;
     pcc::ProfScope prof("knn_mfma_split_kernel", st);
     hipLaunchKernelGGL((knn_mfma_split_kernel<K, CP>), dim3(pcc::ceil_div(n, kSplitQ), b), dim3(512), lds, st, c, n, k, x, sq,
                        reinterpret_cast<float2 *>(logs.p), indices);
@@ -987,6 +958,10 @@ int launch_mfma(int b, int c, int n, int k, const float *x, const float *sq, int
 
 }  // namespace
 
+void pcc::launch_sqnorm(int b, int c, int n, const float *x, float *sq, hipStream_t st) {
+    hipLaunchKernelGGL(sqnorm_kernel, dim3(pcc::ceil_div(n, 256), b), dim3(256), 0, st, c, n, x, sq);
+}
+
 extern "C" int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_stream_t stream) {
     pcc::clear_error();
     if (b < 0 || c < 1 || n < 0 || k < 1) return pcc::invalid("knn: bad size");
@@ -1003,14 +978,9 @@ extern "C" int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indi
         const int nb = pcc::ceil_div(n, kSortBoxK);
         // (+256: the search loads whole 16-row blocks; the last block of the last sample may run past the cloud)
         const size_t aos_b = (size_t)b * n * 16 + 256, box_b = (size_t)b * nb * 32;
-        SqBuf ws(st);
-        if (pcc::ws_malloc(reinterpret_cast<void **>(&ws.p), aos_b + box_b + (size_t)b * n * 4, st) != hipSuccess) {
-            ws.p = nullptr;
-            (void)hipGetLastError();
-            pcc::set_error(PCC_ENOMEM, "knn: workspace allocation failed");
-            return PCC_ENOMEM;
-        }
-        char *base = reinterpret_cast<char *>(ws.p);
+        pcc::WsBlock ws(st);
+        if (int rc = ws.alloc(aos_b + box_b + (size_t)b * n * 4, "knn: workspace allocation failed")) return rc;
+        char *base = static_cast<char *>(ws.p);
         KnnSortedArgs a{};
         a.n = n; a.nb = nb; a.batch = b; a.k = k;
         a.aos = reinterpret_cast<const float4 *>(base);
@@ -1020,39 +990,18 @@ extern "C" int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indi
         if (int rc = pcc::sort_cloud_cmajor(b, c, n, x, reinterpret_cast<float4 *>(base), reinterpret_cast<float *>(base + aos_b),
                                             reinterpret_cast<int *>(base + aos_b + box_b), st))
             return rc;
-        if (k <= 4) launch_sorted<4, 0>(a, st);
-        else if (k <= 8) launch_sorted<8, 4>(a, st);
-        else if (k <= 16) launch_sorted<16, 8>(a, st);
-        else if (k <= 20) launch_sorted<20, 16>(a, st);
-        else if (k <= 25) launch_sorted<25, 20>(a, st);
-        else launch_sorted<32, 25>(a, st);
+        with_slots(k, [&](auto K) { return launch_sorted<K>(a, st); });
         return pcc::check_launch("knn(sorted)");
     }
     if (c <= 3) {  // clouds too large for the one-workgroup sort: exhaustive scan
-        if (k <= 4) launch_small<4>(b, c, n, k, x, indices, st);
-        else if (k <= 8) launch_small<8>(b, c, n, k, x, indices, st);
-        else if (k <= 16) launch_small<16>(b, c, n, k, x, indices, st);
-        else if (k <= 20) launch_small<20>(b, c, n, k, x, indices, st);
-        else if (k <= 25) launch_small<25>(b, c, n, k, x, indices, st);
-        else launch_small<32>(b, c, n, k, x, indices, st);
+        with_slots(k, [&](auto K) { return launch_small<K>(b, c, n, k, x, indices, st); });
         return pcc::check_launch("knn(small)");
     }
-    SqBuf sq(st);
-    if (pcc::ws_malloc(reinterpret_cast<void **>(&sq.p), (size_t)b * n * sizeof(float), st) != hipSuccess) {
-        sq.p = nullptr;
-        (void)hipGetLastError();
-        pcc::set_error(PCC_ENOMEM, "knn: workspace allocation failed");
-        return PCC_ENOMEM;
-    }
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(pcc::ceil_div(n, 256), b), dim3(256), 0, st, c, n, x, sq.p);
+    pcc::WsBlock ws(st);
+    if (int rc = ws.alloc((size_t)b * n * sizeof(float), "knn: workspace allocation failed")) return rc;
+    float *sq = static_cast<float *>(ws.p);
+    pcc::launch_sqnorm(b, c, n, x, sq, st);
     if (int rc = pcc::check_launch("knn(sqnorm)")) return rc;
-    int rc;
-    if (k <= 4) rc = launch_mfma<4>(b, c, n, k, x, sq.p, indices, st);
-    else if (k <= 8) rc = launch_mfma<8>(b, c, n, k, x, sq.p, indices, st);
-    else if (k <= 16) rc = launch_mfma<16>(b, c, n, k, x, sq.p, indices, st);
-    else if (k <= 20) rc = launch_mfma<20>(b, c, n, k, x, sq.p, indices, st);
-    else if (k <= 25) rc = launch_mfma<25>(b, c, n, k, x, sq.p, indices, st);
-    else rc = launch_mfma<32>(b, c, n, k, x, sq.p, indices, st);
-    if (rc) return rc;
+    if (int rc = with_slots(k, [&](auto K) { return launch_mfma<K>(b, c, n, k, x, sq, indices, st); })) return rc;
     return pcc::check_launch("knn(mfma)");
 }

@@ -17,6 +17,7 @@
 
 #include "pcc_common.hpp"
 #include "pcc_neighbour.h"
+#include "wave_sort.hpp"
 
 namespace {
 
@@ -34,62 +35,6 @@ __device__ __forceinline__ u64 wide_key(float d, int j) {
     const unsigned u = __float_as_uint(d + 0.0f);
     const unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
     return ((u64)o << 32) | (unsigned)j;
-}
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-    const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
-    return ((u64)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-__device__ __forceinline__ u64 readlane_u64(u64 v, int l) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((u64)hi << 32) | lo;
-}
-
-// Ascending bitonic sort of the wave's 64 E keys, element e = lane + 64 h in v[h] (knn.hip's box sort, E registers).
-template <int E>
-__device__ __forceinline__ void wave_bitonic(u64 (&v)[E], int lane) {
-#pragma unroll
-    for (int kk = 2; kk <= 64 * E; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            if (j >= 64) {
-                const int hj = j >> 6;
-#pragma unroll
-                for (int h = 0; h < E; h++) {
-                    if (h & hj) continue;
-                    const bool asc = ((lane + 64 * h) & kk) == 0;
-                    const u64 a = v[h], b = v[h | hj];
-                    const bool sw = asc ? b < a : a < b;
-                    v[h] = sw ? b : a;
-                    v[h | hj] = sw ? a : b;
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < E; h++) {
-                    const int i = lane + 64 * h;
-                    const u64 o = shfl_xor_u64(v[h], j);
-                    const bool take_min = ((i & j) == 0) == ((i & kk) == 0);
-                    v[h] = take_min ? (o < v[h] ? o : v[h]) : (o < v[h] ? v[h] : o);
-                }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void wide_sqnorm_kernel(int c, int n, const float *__restrict__ x, float *__restrict__ sq) {
-    // sq[b][i] = sum_c x[b,c,i]^2 as an fma chain in channel order (the oracle's |x_j|^2)
-    const int smp = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float *xb = x + (size_t)smp * c * n;
-    float s = 0.f;
-    for (int ch = 0; ch < c; ch++) {
-        const float v = xb[(size_t)ch * n + i];
-        s = __builtin_fmaf(v, v, s);
-    }
-    sq[(size_t)smp * n + i] = s;
 }
 
 // c >= 4: distances of queries q0 + [0, nq) against all n candidates of samples s0 + blockIdx.z, to
@@ -232,11 +177,11 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
             v[R + h] = lane + 64 * h < cnt ? buf[lane + 64 * h] : kWideKeyMax;
         }
         __builtin_amdgcn_wave_barrier();
-        wave_bitonic<2 * R>(v, lane);
+        pcc::wave_bitonic(v, lane);
 #pragma unroll
         for (int h = 0; h < R; h++) list[h] = v[h];
         const u64 kth = (R == 1 || k <= 64) ? list[0] : list[R - 1];
-        thr = readlane_u64(kth, (k - 1) & 63);
+        thr = pcc::readlane_u64(kth, (k - 1) & 63);
         cnt = 0;
     };
 
@@ -276,24 +221,6 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
     }
 }
 
-struct WsBlock {  // stream-ordered workspace block, freed behind the work enqueued so far
-    void *p = nullptr;
-    hipStream_t st;
-    explicit WsBlock(hipStream_t s) : st(s) {}
-    ~WsBlock() {
-        if (p) (void)pcc::ws_free(p, st);
-    }
-    bool alloc(size_t bytes) {
-        if (pcc::ws_malloc(&p, bytes, st) != hipSuccess) {
-            p = nullptr;
-            (void)hipGetLastError();
-            pcc::set_error(PCC_ENOMEM, "knn: workspace allocation failed");
-            return false;
-        }
-        return true;
-    }
-};
-
 template <int L, bool DIFF>
 void launch_select(const WideSelArgs &a, hipStream_t st) {
     pcc::ProfScope prof("knn_wide_select_kernel", st);
@@ -331,9 +258,10 @@ int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipSt
         nq = (int)std::min<size_t>((size_t)n, std::max<size_t>(kDT, cap / n / kDT * kDT));
     }
     WsBlock sq(st), dw(st);
-    if (!sq.alloc((size_t)b * n * sizeof(float)) || !dw.alloc((size_t)ns * nq * n * sizeof(float))) return PCC_ENOMEM;
+    if (int rc = sq.alloc((size_t)b * n * sizeof(float), "knn: workspace allocation failed")) return rc;
+    if (int rc = dw.alloc((size_t)ns * nq * n * sizeof(float), "knn: workspace allocation failed")) return rc;
     float *sqp = static_cast<float *>(sq.p), *D = static_cast<float *>(dw.p);
-    hipLaunchKernelGGL(wide_sqnorm_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, st, c, n, x, sqp);
+    launch_sqnorm(b, c, n, x, sqp, st);
     if (int rc = check_launch("knn(wide sqnorm)")) return rc;
     a.D = D;
     for (int s0 = 0; s0 < b; s0 += ns) {

@@ -70,6 +70,39 @@ constexpr unsigned long long kPoolKeepBytes = 1ull << 30;
 hipError_t ws_malloc(void **p, size_t bytes, hipStream_t st);
 hipError_t ws_free(void *p, hipStream_t st);
 
+// One block of that workspace, freed on its stream when the scope ends: behind the work enqueued so far.
+struct WsBlock {
+    void *p = nullptr;
+    hipStream_t st;
+    explicit WsBlock(hipStream_t s) : st(s) {}
+    WsBlock(const WsBlock &) = delete;
+    WsBlock &operator=(const WsBlock &) = delete;
+    ~WsBlock() { (void)ws_free(p, st); }
+    // PCC_OK, or PCC_ENOMEM with `what` as the error message
+    int alloc(size_t bytes, const char *what) {
+        if (ws_malloc(&p, bytes, st) != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();
+            set_error(PCC_ENOMEM, what);
+            return PCC_ENOMEM;
+        }
+        return PCC_OK;
+    }
+};
+
+// Lets `Kernel` take up to `bytes` of dynamic LDS: one hipFuncSetAttribute per kernel and process (a kernel is always
+// asked for the same size); a failure clears the sticky error and is returned on every call.
+template <auto Kernel>
+hipError_t allow_lds(size_t bytes) {
+    static const hipError_t e = [bytes] {
+        const hipError_t r =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (r != hipSuccess) (void)hipGetLastError();
+        return r;
+    }();
+    return e;
+}
+
 // The Chamfer half of pcc_chamfer_emd: computed inside the approximate-EMD call, on the clouds that call sorts
 // (approxmatch.hip); the loss reduction rides in that call's finish launch.
 struct ChamferOut {
@@ -97,6 +130,9 @@ int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *b
 // k-NN graph outside the range of knn.hip's kernels (knn_wide.hip): any c >= 1, 1 <= k <= min(n, 128); sizes and
 // pointers already validated by pcc_knn.
 int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st);
+
+// sq[b][n] = sum_c x[b][c][n]^2 as one fma chain in channel order (the oracle's |x_j|^2; knn.hip's sqnorm_kernel)
+void launch_sqnorm(int b, int c, int n, const float *x, float *sq, hipStream_t st);
 
 // true while `st` is being captured into a graph (a failed query counts as not capturing)
 bool capturing(hipStream_t st);
