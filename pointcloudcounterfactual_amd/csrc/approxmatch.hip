@@ -163,9 +163,14 @@ struct Sched {
     LevelConsts lc;
 };
 
-__host__ __device__ inline int sched_phases() { return 2 * kLevels + 1; }
+inline int sched_phases() { return 2 * kLevels + 1; }
 
-__host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mode_out, int *var_out) {
+inline int mask_words(int m4) { return (m4 + 31) / 32; }
+
+// squared radius beyond which every exp2(c * d2) of level constant c is exactly 0
+inline float zero_cut2(const LevelConsts &lc, int i) { return kZeroExp / -lc.c[i]; }
+
+inline PhaseArgs build_phase(const Sched &sc, int p, int *mode_out, int *var_out) {
     const long long nm4 = (long long)sc.n4 + sc.m4;
     const long long rs = (long long)sc.n4 + 2LL * sc.m4;
     PhaseArgs a{};
@@ -187,7 +192,7 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
         var = sc.skip ? V_CULL : V_PLAIN;
         a.level = 0;
         a.w0 = nullptr; a.w0c = sc.multiR; a.c0 = sc.lc.c[0]; a.first = 1;
-        a.cut2 = kZeroExp / -sc.lc.c[0];
+        a.cut2 = zero_cut2(sc.lc, 0);
         a.ratio_out = sc.lv; a.ratio_stride = kLevels * nm4;
     } else {
         const int i = (p - 1) / 2;
@@ -200,14 +205,14 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
             // box culling while the zero radius is small against the cloud (levels 0-2), live-owner compaction after
             var = !sc.skip ? V_PLAIN : i <= 2 ? V_CULL : V_COWN;
             a.w0 = ratioL; a.w0_stride = kLevels * nm4;
-            a.cut2 = kZeroExp / -sc.lc.c[i];
+            a.cut2 = zero_cut2(sc.lc, i);
             a.remain = sc.rem + sc.n4 + (i & 1) * sc.m4;
             a.remain_out = sc.rem + sc.n4 + ((i + 1) & 1) * sc.m4;
             a.remain_stride = rs;
             a.ratio_out = ratioR; a.ratio_stride = kLevels * nm4;
             if (var == V_COWN) { a.clist = sc.clist; a.clist_cnt = sc.clist_cnt; a.cl_n4 = sc.m4; }
             if (sc.live_mask) {
-                const int words = (sc.m4 + 31) / 32;
+                const int words = mask_words(sc.m4);
                 a.mask_words = words;
                 if (i + 1 < kLevels && (var == V_COWN || i == 2)) a.mask_out = sc.live_mask + (size_t)(i + 1) * words;
                 if (var == V_COWN) {
@@ -233,8 +238,8 @@ __host__ __device__ inline PhaseArgs build_phase(const Sched &sc, int p, int *mo
             a.remain = sc.rem; a.remain_stride = rs;
             a.ratio_in = ratioL; a.ratio_stride = kLevels * nm4;
             const int lc_i = i + 1 < kLevels ? i + 1 : i;
-            a.cut2 = kZeroExp / -sc.lc.c[lc_i];  // the coarser of the two levels decides what is 0
-            a.cut2_fine = kZeroExp / -sc.lc.c[i];
+            a.cut2 = zero_cut2(sc.lc, lc_i);  // the coarser of the two levels decides what is 0
+            a.cut2_fine = zero_cut2(sc.lc, i);
             if (i + 1 < kLevels) {
                 a.c1 = sc.lc.c[i + 1];
                 a.ratio_out = sc.lv + (size_t)(i + 1) * nm4;
@@ -2354,38 +2359,76 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 size_t cost_parts(int n, int m) { return (size_t)pcc::ceil_div(n, kMatKT) * pcc::ceil_div(m, kMatLT); }
 
-// Workspace carve (bytes, every section 16-byte aligned).
-inline int mask_words(int m4) { return (m4 + 31) / 32; }
+// Every workspace section offset to one sample (each is indexed [sample][...]): a lane of samples [s0, s0 + bc) runs
+// on the view at s0.  Sizes below are per sample.
+struct WsView {
+    float *soa1, *soa2;                // [3][n4] / [3][m4] Hilbert-sorted coordinates
+    int *rank1, *rank2, *perm1, *perm2;  // [n] / [m] caller's index -> sorted position, and back
+    float *box1, *box2;                // [nb][8] per 16 sorted points
+    float *rem;                        // sorted space: remainL (n4) | remainR ping (m4) | pong (m4)
+    float *lv;                         // [kLevels][n4 + m4] sorted space: ratioL | ratioR
+    float *lv_orig;                    // [kLevels][n + m] the level rows in the caller's order
+    float *cpart;                      // [cost_parts] cost partials of the materialise pass
+    float *clist;                      // [5][m4] dense candidate list handed from pass B to pass C/A
+    int *clist_cnt;                    // [1]
+    int *live_cnt;                     // [kLiveRow] live-owner counters and flags
+    unsigned *live_mask;               // [kLevels][mask_words] live bits of set2 per level (V_COWN)
+    float4 *aos1, *aos2;               // [n] / [m] packed sorted points for the nearest-neighbour search of pcc_chamfer_emd
+    float *pair_cost, *part1, *part2;  // implicit path only: am_pair_kernel's cost and gradient partials (PairArgs)
+};
 
+// Workspace carve (bytes, every section 16-byte aligned).  The implicit path (match_cost_implicit_impl) passes its
+// am_pair_kernel tiling: its three sections follow the others and are empty on the materialising path.
 struct WsLayout {
-    int n4, m4, nb1, nb2;
-    size_t soa1, soa2, rank1, rank2, perm1, perm2, box1, box2, rem, lv, lv_orig, cpart, clist, clist_cnt, live_cnt, live_mask, aos1, aos2, total;
-    WsLayout(int b, int n, int m) {
-        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        n4 = (n + 3) & ~3;
-        m4 = (m + 3) & ~3;
-        nb1 = pcc::ceil_div(n, kBox);
-        nb2 = pcc::ceil_div(m, kBox);
+    int b, n, m, n4, m4, nb1, nb2;
+    int col_blocks, row_tiles;
+    bool grad;
+    size_t total;
+    WsLayout(int b_, int n_, int m_, int col_blocks_ = 0, int row_tiles_ = 0, bool grad_ = false)
+        : b(b_), n(n_), m(m_), n4((n_ + 3) & ~3), m4((m_ + 3) & ~3), nb1(pcc::ceil_div(n_, kBox)),
+          nb2(pcc::ceil_div(m_, kBox)), col_blocks(col_blocks_), row_tiles(row_tiles_), grad(grad_) {
+        WsView unused;
+        total = carve(0, 0, unused);
+    }
+    WsView view(char *base, int s) const {
+        WsView v;
+        carve(reinterpret_cast<uintptr_t>(base), (size_t)s, v);
+        return v;
+    }
+    size_t rem_floats() const { return (size_t)n4 + 2 * (size_t)m4; }   // per sample
+    size_t lv_floats() const { return kLevels * ((size_t)n4 + m4); }
+
+  private:
+    // The sections in order: points every pointer of `v` at sample s of the workspace at `base`; returns the end offset.
+    size_t carve(uintptr_t base, size_t s, WsView &v) const {
         size_t o = 0;
-        soa1 = o; o = up(o + (size_t)b * 3 * n4 * 4);
-        soa2 = o; o = up(o + (size_t)b * 3 * m4 * 4);
-        rank1 = o; o = up(o + (size_t)b * n * 4);
-        rank2 = o; o = up(o + (size_t)b * m * 4);
-        perm1 = o; o = up(o + (size_t)b * n * 4);
-        perm2 = o; o = up(o + (size_t)b * m * 4);
-        box1 = o; o = up(o + (size_t)b * nb1 * 8 * 4);
-        box2 = o; o = up(o + (size_t)b * nb2 * 8 * 4);
-        rem = o; o = up(o + (size_t)b * ((size_t)n4 + 2 * (size_t)m4) * 4);    // sorted space: remainL | remainR x2
-        lv = o; o = up(o + (size_t)b * kLevels * ((size_t)n4 + m4) * 4);      // sorted space, padded halves
-        lv_orig = o; o = up(o + (size_t)b * kLevels * ((size_t)n + m) * 4);
-        cpart = o; o = up(o + (size_t)b * cost_parts(n, m) * 4);
-        clist = o; o = up(o + (size_t)b * 5 * m4 * 4);   // dense candidate list handed from pass B to pass C/A
-        clist_cnt = o; o = up(o + (size_t)b * 4);
-        live_cnt = o; o = up(o + (size_t)b * kLiveRow * 4);
-        live_mask = o; o = up(o + (size_t)b * kLevels * mask_words(m4) * 4);  // live bits of set2 per level (V_COWN)
-        aos1 = o; o = up(o + (size_t)b * n * 16);   // packed sorted points for the nearest-neighbour search of pcc_chamfer_emd
-        aos2 = o; o = up(o + (size_t)b * m * 16);
-        total = o;
+        auto sec = [&](auto *&p, size_t per) {  // per: elements per sample
+            using T = std::remove_reference_t<decltype(*p)>;
+            p = reinterpret_cast<T *>(base + o + s * per * sizeof(T));
+            o = (o + (size_t)b * per * sizeof(T) + 15) & ~(size_t)15;
+        };
+        sec(v.soa1, 3 * (size_t)n4);
+        sec(v.soa2, 3 * (size_t)m4);
+        sec(v.rank1, n);
+        sec(v.rank2, m);
+        sec(v.perm1, n);
+        sec(v.perm2, m);
+        sec(v.box1, (size_t)nb1 * 8);
+        sec(v.box2, (size_t)nb2 * 8);
+        sec(v.rem, rem_floats());
+        sec(v.lv, lv_floats());
+        sec(v.lv_orig, kLevels * ((size_t)n + m));
+        sec(v.cpart, cost_parts(n, m));
+        sec(v.clist, 5 * (size_t)m4);
+        sec(v.clist_cnt, 1);
+        sec(v.live_cnt, kLiveRow);
+        sec(v.live_mask, (size_t)kLevels * mask_words(m4));
+        sec(v.aos1, n);
+        sec(v.aos2, m);
+        sec(v.pair_cost, (size_t)col_blocks * row_tiles);
+        sec(v.part1, grad ? (size_t)row_tiles * n4 * 3 : 0);
+        sec(v.part2, grad ? (size_t)col_blocks * m4 * 3 : 0);
+        return o;
     }
 };
 
@@ -2400,20 +2443,19 @@ void launch_sort(const SortArgs &a, int slots, dim3 grid, hipStream_t st) {
     }
 }
 
-int sort_clouds(int b, const WsLayout &L, int n, int m, const float *xyz1, const float *xyz2, float *soa1, float *soa2,
-                int *rank1, int *rank2, int *perm1, int *perm2, float *box1, float *box2, float *rem, float *lv,
-                int *live_cnt, unsigned *live_mask, float4 *aos1, float4 *aos2, hipStream_t st) {
+// Sorts the bc samples of the view `v` (xyz1 / xyz2: their first sample); `aos`: also write the packed rows aos1 / aos2.
+int sort_clouds(const WsLayout &L, const WsView &v, int bc, const float *xyz1, const float *xyz2, bool aos, hipStream_t st) {
     SortArgs a{};
-    a.live_cnt = live_cnt;
-    a.live_mask = live_mask;
+    a.live_cnt = v.live_cnt;
+    a.live_mask = v.live_mask;
     a.mask_words = mask_words(L.m4);
-    a.aos[0] = aos1; a.aos[1] = aos2;
+    if (aos) { a.aos[0] = v.aos1; a.aos[1] = v.aos2; }
     // the padded tails of the weight rows are staged as float4: they must be finite (their candidates sit at the
     // origin with these weights), and V_COWN relies on zero-filled level arrays for the exhausted owners it never
     // touches: remain rows are cleared by the workgroup sorting set1, level rows by the one sorting set2
-    a.zero[0] = rem; a.zero_stride[0] = a.zero_count[0] = (long long)L.n4 + 2LL * L.m4;
-    a.zero[1] = lv; a.zero_stride[1] = a.zero_count[1] = (long long)kLevels * ((long long)L.n4 + L.m4);
-    const int nn[2] = {n, m};
+    a.zero[0] = v.rem; a.zero_stride[0] = a.zero_count[0] = (long long)L.rem_floats();
+    a.zero[1] = v.lv; a.zero_stride[1] = a.zero_count[1] = (long long)L.lv_floats();
+    const int nn[2] = {L.n, L.m};
     int slots = 4;
     for (int w = 0; w < 2; w++) {
         int npad = 4 * kSortT;
@@ -2426,12 +2468,12 @@ int sort_clouds(int b, const WsLayout &L, int n, int m, const float *xyz1, const
     for (int w = 0; w < 2; w++)
         if (a.npad[w]) a.npad[w] = kSortT * slots;  // one SLOTS instantiation serves both clouds
     a.n4[0] = L.n4; a.n4[1] = L.m4; a.nb[0] = L.nb1; a.nb[1] = L.nb2;
-    a.xyz[0] = xyz1; a.xyz[1] = xyz2; a.soa[0] = soa1; a.soa[1] = soa2;
+    a.xyz[0] = xyz1; a.xyz[1] = xyz2; a.soa[0] = v.soa1; a.soa[1] = v.soa2;
     for (int w = 0; w < 2; w++) {
         a.sstride[w] = (long long)nn[w] * 3; a.pstride[w] = 3; a.cstride[w] = 1; a.nch[w] = 3;
     }
-    a.rank[0] = rank1; a.rank[1] = rank2; a.perm[0] = perm1; a.perm[1] = perm2; a.box[0] = box1; a.box[1] = box2;
-    launch_sort(a, slots, dim3(b, 2), st);
+    a.rank[0] = v.rank1; a.rank[1] = v.rank2; a.perm[0] = v.perm1; a.perm[1] = v.perm2; a.box[0] = v.box1; a.box[1] = v.box2;
+    launch_sort(a, slots, dim3(bc, 2), st);
     return pcc::check_launch("approxmatch(sort)");
 }
 
@@ -2508,7 +2550,7 @@ int launch_fine_resident(const Sched &sc, int bc, hipStream_t st) {
     a.rem = sc.rem; a.lv = sc.lv; a.multiL = sc.multiL; a.multiR = sc.multiR;
     for (int i = 0; i < 4; i++) {
         a.c[i] = sc.lc.c[i];
-        a.cut2[i] = kZeroExp / -sc.lc.c[i];
+        a.cut2[i] = zero_cut2(sc.lc, i);
     }
     a.live_cnt = sc.live_cnt;
     a.live_mask = sc.live_mask;
@@ -2532,9 +2574,24 @@ int launch_fine_resident(const Sched &sc, int bc, hipStream_t st) {
     return pcc::check_launch("approxmatch(resident fine levels)");
 }
 
+// The schedule of one lane: the samples of the workspace view `v`.
+Sched lane_sched(const WsLayout &L, const WsView &v, const LevelConsts &lc) {
+    Sched sc{};
+    sc.n = L.n; sc.m = L.m; sc.n4 = L.n4; sc.m4 = L.m4; sc.nb1 = L.nb1; sc.nb2 = L.nb2;
+    sc.soa1 = v.soa1; sc.soa2 = v.soa2; sc.box1 = v.box1; sc.box2 = v.box2; sc.rem = v.rem; sc.lv = v.lv;
+    // approxmatch.cu:6-12 (integer division)
+    if (L.n >= L.m) { sc.multiL = 1; sc.multiR = (float)(L.n / L.m); }
+    else { sc.multiL = (float)(L.m / L.n); sc.multiR = 1; }
+    sc.skip = cull_enabled() ? 1 : 0;
+    sc.lc = lc;
+    sc.clist = v.clist; sc.clist_cnt = v.clist_cnt;
+    if (sc.skip) { sc.live_cnt = v.live_cnt; sc.live_mask = v.live_mask; }
+    return sc;
+}
+
 // Sort + the 19 passes: leaves the nine (ratioL | ratioR) level rows and remainL | remainR in the workspace, in the
 // Hilbert-sorted index space.
-int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const WsLayout &L, char *base, hipStream_t st,
+int run_levels(const WsLayout &L, char *base, const float *xyz1, const float *xyz2, const LevelConsts &lc, hipStream_t st,
                const std::function<int(int, int, hipStream_t)> &lane_tail = nullptr,
                const std::function<int(int, int, hipStream_t)> &after_sort = nullptr) {
     if (const unsigned fw = pcc::take_coresident_failure(pcc::kFineResident)) {
@@ -2544,69 +2601,38 @@ int run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, const 
                       "samples); this call was not started", (fw >> 4) & 0xfu, fw >> 20, (fw >> 8) & 0xfffu);
         return pcc::invalid(buf);
     }
-    const LevelConsts lc = make_levels();
-    float multiL, multiR;  // approxmatch.cu:6-12 (integer division)
-    if (n >= m) { multiL = 1; multiR = (float)(n / m); }
-    else { multiL = (float)(m / n); multiR = 1; }
-    const long long nm4 = (long long)L.n4 + L.m4;  // sorted-space level row: ratioL (n4) | ratioR (m4)
-    const long long rs = (long long)L.n4 + 2LL * L.m4;  // remain row: remainL (n4) | remainR ping (m4) | pong (m4)
-
     const bool split_enabled = pcc::tuning(PCC_TUNE_AM_NOSPLIT) == 0;  // (measurement switch: everything on the caller's stream)
 
     // Lanes: disjoint sample ranges that run the same schedule on different streams.  Two lanes when each half still
-    // is a sizeable launch (B=32, N=2048: EMD forward+backward 530 -> 49x us); every workspace section is indexed
-    // [sample][...], so a lane is the same schedule on pointers offset to its first sample.
+    // is a sizeable launch (B=32, N=2048: EMD forward+backward 530 -> 49x us); a lane is the same schedule on the
+    // workspace view at its first sample.
     struct Lane {
         int s0, bc;
         hipStream_t st;
+        WsView v;
         Sched sc;
     };
     Lane lanes[kMaxLanes];
     int nlanes = 1;
     bool fork = false;
-    if (split_enabled && b >= 8 && (long long)b * std::max(n, m) >= 32768) {
+    if (split_enabled && L.b >= 8 && (long long)L.b * std::max(L.n, L.m) >= 32768) {
         fork = !pcc::capturing(st);  // a capture stays a single-stream chain
     }
     ForkJoin fj(st, fork);
     if (fj.side) nlanes = 2;
     for (int l = 0; l < nlanes; l++) {
         Lane &ln = lanes[l];
-        ln.s0 = (int)((long long)b * l / nlanes);
-        ln.bc = (int)((long long)b * (l + 1) / nlanes) - ln.s0;
+        ln.s0 = (int)((long long)L.b * l / nlanes);
+        ln.bc = (int)((long long)L.b * (l + 1) / nlanes) - ln.s0;
         ln.st = l == 0 ? st : fj.side;
-        const size_t s0 = (size_t)ln.s0;
-        Sched &sc = ln.sc;
-        sc = Sched{};
-        sc.n = n; sc.m = m; sc.n4 = L.n4; sc.m4 = L.m4; sc.nb1 = L.nb1; sc.nb2 = L.nb2;
-        sc.soa1 = reinterpret_cast<float *>(base + L.soa1) + s0 * 3 * L.n4;
-        sc.soa2 = reinterpret_cast<float *>(base + L.soa2) + s0 * 3 * L.m4;
-        sc.box1 = reinterpret_cast<float *>(base + L.box1) + s0 * L.nb1 * 8;
-        sc.box2 = reinterpret_cast<float *>(base + L.box2) + s0 * L.nb2 * 8;
-        sc.rem = reinterpret_cast<float *>(base + L.rem) + s0 * rs;
-        sc.lv = reinterpret_cast<float *>(base + L.lv) + s0 * kLevels * nm4;
-        sc.multiL = multiL; sc.multiR = multiR;
-        sc.skip = cull_enabled() ? 1 : 0;
-        sc.lc = lc;
-        {
-            sc.clist = reinterpret_cast<float *>(base + L.clist) + s0 * 5 * L.m4;
-            sc.clist_cnt = reinterpret_cast<int *>(base + L.clist_cnt) + s0;
-        }
-        if (sc.skip) sc.live_cnt = reinterpret_cast<int *>(base + L.live_cnt) + s0 * kLiveRow;
-        if (sc.skip) sc.live_mask = reinterpret_cast<unsigned *>(base + L.live_mask) + s0 * kLevels * mask_words(L.m4);
+        ln.v = L.view(base, ln.s0);
+        ln.sc = lane_sched(L, ln.v, lc);
     }
     int rc = PCC_OK;
     auto enqueue_head = [&](int l) -> int {
         const Lane &ln = lanes[l];
         const size_t s0 = (size_t)ln.s0;
-        int r = sort_clouds(ln.bc, L, n, m, xyz1 + s0 * n * 3, xyz2 + s0 * m * 3, const_cast<float *>(ln.sc.soa1),
-                            const_cast<float *>(ln.sc.soa2), reinterpret_cast<int *>(base + L.rank1) + s0 * n,
-                            reinterpret_cast<int *>(base + L.rank2) + s0 * m, reinterpret_cast<int *>(base + L.perm1) + s0 * n,
-                            reinterpret_cast<int *>(base + L.perm2) + s0 * m, const_cast<float *>(ln.sc.box1),
-                            const_cast<float *>(ln.sc.box2), ln.sc.rem, ln.sc.lv,
-                            reinterpret_cast<int *>(base + L.live_cnt) + s0 * kLiveRow,
-                            reinterpret_cast<unsigned *>(base + L.live_mask) + s0 * kLevels * mask_words(L.m4),
-                            after_sort ? reinterpret_cast<float4 *>(base + L.aos1) + s0 * n : nullptr,
-                            after_sort ? reinterpret_cast<float4 *>(base + L.aos2) + s0 * m : nullptr, ln.st);
+        int r = sort_clouds(L, ln.v, ln.bc, xyz1 + s0 * L.n * 3, xyz2 + s0 * L.m * 3, (bool)after_sort, ln.st);
         // work that only needs the sorted clouds of this lane's samples (pcc_chamfer_emd: the nearest-neighbour search).
         // Even lanes run it here, odd lanes behind their passes: two searches at the same moment halve each other (each
         // wants every SIMD); against the other lane's pass chain a search costs less (chamfer_emd 447.7 -> 440.4 us, step
@@ -2664,17 +2690,13 @@ int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, 
     if (workspace_bytes < L.total) return pcc::invalid("approxmatch: workspace too small");
     if (!aligned16(workspace)) return pcc::invalid("approxmatch: workspace must be 16-byte aligned");
     char *base = static_cast<char *>(workspace);
-    int rc = run_levels(b, n, m, xyz1, xyz2, L, base, st);
-    if (rc) return rc;
-    int *rank1 = reinterpret_cast<int *>(base + L.rank1), *rank2 = reinterpret_cast<int *>(base + L.rank2);
-    float *rem = reinterpret_cast<float *>(base + L.rem);
-    float *lv = reinterpret_cast<float *>(base + L.lv);
-    float *lv_orig = reinterpret_cast<float *>(base + L.lv_orig);
-    float *cpart = reinterpret_cast<float *>(base + L.cpart);
     const LevelConsts lc = make_levels();
-    const int *flags = reinterpret_cast<const int *>(base + L.live_cnt);  // (written by this call's sort and passes)
-    hipLaunchKernelGGL(am_unpermute_kernel, dim3(pcc::ceil_div(n + m, 256), b), dim3(256), 0, st, n, m, L.n4, L.m4, lv, rem,
-                       rank1, rank2, flags, lv_orig, temp);
+    int rc = run_levels(L, base, xyz1, xyz2, lc, st);
+    if (rc) return rc;
+    const WsView v = L.view(base, 0);
+    // (v.live_cnt: the flags written by this call's sort and passes)
+    hipLaunchKernelGGL(am_unpermute_kernel, dim3(pcc::ceil_div(n + m, 256), b), dim3(256), 0, st, n, m, L.n4, L.m4, v.lv, v.rem,
+                       v.rank1, v.rank2, v.live_cnt, v.lv_orig, temp);
     rc = pcc::check_launch("approxmatch(unpermute)");
     if (rc) return rc;
     const dim3 grid(pcc::ceil_div(n, kMatKT), pcc::ceil_div(m, kMatLT), b);
@@ -2682,18 +2704,18 @@ int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, 
     if (cost_out) {
         {
             pcc::ProfScope prof("am_materialise_kernel<cost>", st);
-            if (vec) hipLaunchKernelGGL((am_materialise_kernel<true, true>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, lv_orig, lc, match, cpart);
-            else hipLaunchKernelGGL((am_materialise_kernel<true, false>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, lv_orig, lc, match, cpart);
+            if (vec) hipLaunchKernelGGL((am_materialise_kernel<true, true>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, v.lv_orig, lc, match, v.cpart);
+            else hipLaunchKernelGGL((am_materialise_kernel<true, false>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, v.lv_orig, lc, match, v.cpart);
         }
         rc = pcc::check_launch("approxmatch(materialise+cost)");
         if (rc) return rc;
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3(b), dim3(256), 0, st, (int)cost_parts(n, m), cpart, cost_out);
+        hipLaunchKernelGGL(reduce_rows_kernel, dim3(b), dim3(256), 0, st, (int)cost_parts(n, m), v.cpart, cost_out);
         return pcc::check_launch("approxmatch(cost reduce)");
     }
     {
         pcc::ProfScope prof("am_materialise_kernel", st);
-        if (vec) hipLaunchKernelGGL((am_materialise_kernel<false, true>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, lv_orig, lc, match, nullptr);
-        else hipLaunchKernelGGL((am_materialise_kernel<false, false>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, lv_orig, lc, match, nullptr);
+        if (vec) hipLaunchKernelGGL((am_materialise_kernel<false, true>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, v.lv_orig, lc, match, nullptr);
+        else hipLaunchKernelGGL((am_materialise_kernel<false, false>), grid, dim3(256), 0, st, n, m, xyz1, xyz2, v.lv_orig, lc, match, nullptr);
     }
     return pcc::check_launch("approxmatch(materialise)");
 }
@@ -2710,32 +2732,26 @@ int launch_pair(const PairArgs &pa, dim3 grid, bool grad, hipStream_t st) {
 int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost,
                              float *cost, float *grad1, float *grad2, hipStream_t st,
                              const pcc::ChamferOut *chamfer = nullptr) {
-    const WsLayout L(b, n, m);
     constexpr int q_cols = 4;  // columns per lane of am_pair_kernel (2 measured slower)
     const bool grad = grad1 && grad2;
     const int col_blocks = pcc::ceil_div(n, 64 * q_cols), row_tiles = pcc::ceil_div(m, kPairRT);
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t cpart_off = up(L.total);
-    const size_t part1_off = up(cpart_off + (size_t)b * col_blocks * row_tiles * 4);
-    const size_t part2_off = up(part1_off + (grad ? (size_t)b * row_tiles * L.n4 * 3 * 4 : 0));
-    const size_t total = up(part2_off + (grad ? (size_t)b * col_blocks * L.m4 * 3 * 4 : 0));
+    const WsLayout L(b, n, m, col_blocks, row_tiles, grad);
     pcc::WsBlock ws(st);
-    if (int rc = ws.alloc(total, "workspace allocation failed")) return rc;
+    if (int rc = ws.alloc(L.total, "workspace allocation failed")) return rc;
     char *base = static_cast<char *>(ws.p);
-    const size_t nm4 = (size_t)L.n4 + L.m4;
-    // pair + finish kernels of the samples [s0, s0 + bc) on `lst` (every section of the workspace is indexed by sample)
+    const LevelConsts lc = make_levels();
+    // pair + finish kernels of the samples [s0, s0 + bc) on `lst`
     auto tail = [&](int s0, int bc, hipStream_t lst) -> int {
         const size_t o = (size_t)s0;
+        const WsView v = L.view(base, s0);
         PairArgs pa{};
         pa.n = n; pa.m = m; pa.n4 = L.n4; pa.m4 = L.m4;
-        pa.soa1 = reinterpret_cast<const float *>(base + L.soa1) + o * 3 * L.n4;
-        pa.soa2 = reinterpret_cast<const float *>(base + L.soa2) + o * 3 * L.m4;
-        pa.lv = reinterpret_cast<const float *>(base + L.lv) + o * kLevels * nm4;
-        pa.lc = make_levels();
-        for (int i = 0; i < kLevels; i++) pa.cut2[i] = kZeroExp / -pa.lc.c[i];
-        pa.cost_part = reinterpret_cast<float *>(base + cpart_off) + o * col_blocks * row_tiles;
-        pa.part1 = grad ? reinterpret_cast<float *>(base + part1_off) + o * row_tiles * L.n4 * 3 : nullptr;
-        pa.part2 = grad ? reinterpret_cast<float *>(base + part2_off) + o * col_blocks * L.m4 * 3 : nullptr;
+        pa.soa1 = v.soa1; pa.soa2 = v.soa2; pa.lv = v.lv;
+        pa.lc = lc;
+        for (int i = 0; i < kLevels; i++) pa.cut2[i] = zero_cut2(lc, i);
+        pa.cost_part = v.pair_cost;
+        pa.part1 = grad ? v.part1 : nullptr;
+        pa.part2 = grad ? v.part2 : nullptr;
         pa.col_blocks = col_blocks; pa.row_tiles = row_tiles; pa.bc = bc;
         if ((long long)col_blocks * row_tiles * bc > 0x7fffffffLL) return pcc::invalid("match_cost: grid too large");
         const dim3 grid((unsigned)(col_blocks * row_tiles * bc));
@@ -2744,13 +2760,12 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
         f.parts[0] = row_tiles; f.parts[1] = col_blocks; f.parts[2] = col_blocks * row_tiles;
         f.npts[0] = n; f.npts[1] = m; f.pitch[0] = L.n4; f.pitch[1] = L.m4;
         f.part[0] = pa.part1; f.part[1] = pa.part2; f.part[2] = pa.cost_part;
-        f.perm[0] = reinterpret_cast<const int *>(base + L.perm1) + o * n;
-        f.perm[1] = reinterpret_cast<const int *>(base + L.perm2) + o * m;
+        f.perm[0] = v.perm1; f.perm[1] = v.perm2;
         f.scale = grad_cost ? grad_cost + o : nullptr;
         f.out[0] = grad ? grad1 + o * n * 3 : nullptr;
         f.out[1] = grad ? grad2 + o * m * 3 : nullptr;
         f.out[2] = cost + o;
-        f.flags = reinterpret_cast<const int *>(base + L.live_cnt) + o * kLiveRow;  // (written by this call's sort)
+        f.flags = v.live_cnt;  // (written by this call's sort)
         if (chamfer) {
             f.ch_d1 = chamfer->dist1 + o * n; f.ch_d2 = chamfer->dist2 + o * m; f.ch_loss = chamfer->loss + o;
             f.ch_n = n; f.ch_m = m; f.ch_mean = chamfer->mean;
@@ -2766,21 +2781,15 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
     // in one launch, then the loss reduction -- on the lane's stream, between the sort and the first pass
     auto nn_after_sort = [&](int s0, int bc, hipStream_t lst) -> int {
         const size_t o = (size_t)s0;
+        const WsView v = L.view(base, s0);
         NNSortedArgs q1{}, q2{};
         q1.n_q = n; q1.n_c = m; q1.q_n4 = L.n4; q1.c_n4 = L.m4; q1.q_nb = L.nb1; q1.c_nb = L.nb2;
         q1.groups = L.nb1; q1.batch = bc;
-        q1.q_soa = reinterpret_cast<const float *>(base + L.soa1) + o * 3 * L.n4;
-        q1.c_aos = reinterpret_cast<const float4 *>(base + L.aos2) + o * m;
-        q1.q_box = reinterpret_cast<const float *>(base + L.box1) + o * L.nb1 * 8;
-        q1.c_box = reinterpret_cast<const float *>(base + L.box2) + o * L.nb2 * 8;
-        q1.q_perm = reinterpret_cast<const int *>(base + L.perm1) + o * n;
+        q1.q_soa = v.soa1; q1.c_aos = v.aos2; q1.q_box = v.box1; q1.c_box = v.box2; q1.q_perm = v.perm1;
         q1.out_d = chamfer->dist1 + o * n; q1.out_i = chamfer->idx1 + o * n;
         q2.n_q = m; q2.n_c = n; q2.q_n4 = L.m4; q2.c_n4 = L.n4; q2.q_nb = L.nb2; q2.c_nb = L.nb1;
         q2.groups = L.nb2; q2.batch = bc;
-        q2.q_soa = reinterpret_cast<const float *>(base + L.soa2) + o * 3 * L.m4;
-        q2.c_aos = reinterpret_cast<const float4 *>(base + L.aos1) + o * n;
-        q2.q_box = q1.c_box; q2.c_box = q1.q_box;
-        q2.q_perm = reinterpret_cast<const int *>(base + L.perm2) + o * m;
+        q2.q_soa = v.soa2; q2.c_aos = v.aos1; q2.q_box = v.box2; q2.c_box = v.box1; q2.q_perm = v.perm2;
         q2.out_d = chamfer->dist2 + o * m; q2.out_i = chamfer->idx2 + o * m;
         const long long w0 = (long long)bc * q1.groups, w1 = (long long)bc * q2.groups;
         const long long grid = (w0 + w1 + kNNWaves - 1) / kNNWaves;
@@ -2791,14 +2800,40 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
         }
         return pcc::check_launch("chamfer_emd(nearest neighbours)");  // (the loss reduction rides in the finish launch)
     };
-    if (chamfer) return run_levels(b, n, m, xyz1, xyz2, L, base, st, tail, nn_after_sort);
-    return run_levels(b, n, m, xyz1, xyz2, L, base, st, tail);
+    if (chamfer) return run_levels(L, base, xyz1, xyz2, lc, st, tail, nn_after_sort);
+    return run_levels(L, base, xyz1, xyz2, lc, st, tail);
 }
 
 int check_sizes(const char *who, int b, int n, int m) {
     if (b < 0 || n < 0 || m < 0) return pcc::invalid(who);
     if ((long long)n * 3 > 0x7fffffffLL || (long long)m * 3 > 0x7fffffffLL) return pcc::invalid(who);
     return PCC_OK;
+}
+
+// n == 0 or m == 0: the sums are empty, so cost[b] and the gradients that have elements are 0 (null: not requested)
+int zero_fill_empty(int b, int n, int m, float *cost, float *grad1, float *grad2, hipStream_t st, const char *what) {
+    hipError_t e = hipSuccess;
+    if (cost) e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st);
+    if (n && grad1 && e == hipSuccess) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(float), st);
+    if (m && grad2 && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(float), st);
+    return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, what), (int)e);
+}
+
+// pcc_approxmatch (with_cost false) and pcc_approxmatch_cost: the same checks, each under its own name
+int approxmatch_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, bool with_cost,
+                      float *cost, hipStream_t st) {
+    pcc::clear_error();
+    if (int rc = check_sizes(with_cost ? "approxmatch_cost: bad size" : "approxmatch: bad size", b, n, m)) return rc;
+    const char *null_ptr = with_cost ? "approxmatch_cost: null pointer" : "approxmatch: null pointer";
+    if (b == 0) return PCC_OK;
+    if (with_cost && !cost) return pcc::invalid(null_ptr);
+    if (n == 0 || m == 0)  // nothing to match (reference: empty loops)
+        return with_cost ? zero_fill_empty(b, n, m, cost, nullptr, nullptr, st, "approxmatch_cost: memset failed") : PCC_OK;
+    if (!xyz1 || !xyz2 || !match || !temp) return pcc::invalid(null_ptr);
+    pcc::WsBlock ws(st);
+    const size_t bytes = WsLayout(b, n, m).total;
+    if (int rc = ws.alloc(bytes, "workspace allocation failed")) return rc;
+    return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, ws.p, bytes, cost, st);
 }
 
 }  // namespace
@@ -2843,33 +2878,12 @@ int pcc_approxmatch_ws(int b, int n, int m, const float *xyz1, const float *xyz2
 
 int pcc_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                     pcc_stream_t stream) {
-    pcc::clear_error();
-    if (int rc = check_sizes("approxmatch: bad size", b, n, m)) return rc;
-    if (b == 0 || n == 0 || m == 0) return PCC_OK;
-    if (!xyz1 || !xyz2 || !match || !temp) return pcc::invalid("approxmatch: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    pcc::WsBlock ws(st);
-    const size_t bytes = WsLayout(b, n, m).total;
-    if (int rc = ws.alloc(bytes, "workspace allocation failed")) return rc;
-    return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, ws.p, bytes, nullptr, st);
+    return approxmatch_entry(b, n, m, xyz1, xyz2, match, temp, false, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int pcc_approxmatch_cost(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                          float *cost, pcc_stream_t stream) {
-    pcc::clear_error();
-    if (int rc = check_sizes("approxmatch_cost: bad size", b, n, m)) return rc;
-    if (b == 0) return PCC_OK;
-    if (!cost) return pcc::invalid("approxmatch_cost: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) {
-        hipError_t e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st);
-        return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, "approxmatch_cost: memset failed"), (int)e);
-    }
-    if (!xyz1 || !xyz2 || !match || !temp) return pcc::invalid("approxmatch_cost: null pointer");
-    pcc::WsBlock ws(st);
-    const size_t bytes = pcc_approxmatch_workspace_bytes(b, n, m);
-    if (int rc = ws.alloc(bytes, "workspace allocation failed")) return rc;
-    return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, ws.p, bytes, cost, st);
+    return approxmatch_entry(b, n, m, xyz1, xyz2, match, temp, true, cost, static_cast<hipStream_t>(stream));
 }
 
 int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost, float *cost,
@@ -2879,12 +2893,7 @@ int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, co
     if (b == 0) return PCC_OK;
     if (!cost) return pcc::invalid("match_cost: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) {  // empty sums
-        hipError_t e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st);
-        if (n && grad1 && e == hipSuccess) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(float), st);
-        if (m && grad2 && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(float), st);
-        return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, "match_cost: memset failed"), (int)e);
-    }
+    if (n == 0 || m == 0) return zero_fill_empty(b, n, m, cost, grad1, grad2, st, "match_cost: memset failed");
     if (!xyz1 || !xyz2) return pcc::invalid("match_cost: null pointer");
     if ((grad1 == nullptr) != (grad2 == nullptr)) return pcc::invalid("match_cost: grad1 and grad2 go together");
     return match_cost_implicit_impl(b, n, m, xyz1, xyz2, grad_cost, cost, grad1, grad2, st);
@@ -2902,10 +2911,7 @@ int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, con
     if (b == 0) return PCC_OK;
     if (!out) return pcc::invalid("matchcost: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) {  // empty sums
-        hipError_t e = hipMemsetAsync(out, 0, (size_t)b * sizeof(float), st);
-        return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, "matchcost: memset failed"), (int)e);
-    }
+    if (n == 0 || m == 0) return zero_fill_empty(b, n, m, out, nullptr, nullptr, st, "matchcost: memset failed");
     if (!xyz1 || !xyz2 || !match) return pcc::invalid("matchcost: null pointer");
     const int tiles = pcc::ceil_div(m, kRowRT);
     pcc::WsBlock ws(st);
@@ -2933,12 +2939,7 @@ int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float
     if (int rc = check_sizes("matchcostgrad: bad size", b, n, m)) return rc;
     if (b == 0) return PCC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) {
-        hipError_t e = hipSuccess;
-        if (n && grad1) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(float), st);
-        if (m && grad2 && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(float), st);
-        return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, "matchcostgrad: memset failed"), (int)e);
-    }
+    if (n == 0 || m == 0) return zero_fill_empty(b, n, m, nullptr, grad1, grad2, st, "matchcostgrad: memset failed");
     if (!xyz1 || !xyz2 || !match || !grad1 || !grad2) return pcc::invalid("matchcostgrad: null pointer");
     const bool vec = (n % 4 == 0) && aligned16(match);
     const int row_tiles = pcc::ceil_div(m, kGradRT), slabs = pcc::ceil_div(n, kGradSlab);

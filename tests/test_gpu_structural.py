@@ -349,7 +349,7 @@ def test_implicit_match_cost_vs_oracle(cuda, oracle_mod, b, n, m):
 
 
 def test_implicit_match_cost_edge_cases(cuda):
-    from pointcloudcounterfactual_amd import backend
+    from pointcloudcounterfactual_amd import _lib, backend
 
     # far clouds: every exponential underflows -> no mass, cost 0, zero gradients
     a, c = pair(5, 2, 300, 300)
@@ -368,6 +368,34 @@ def test_implicit_match_cost_edge_cases(cuda):
     z1, z2 = torch.zeros(2, 0, 3, device=cuda), torch.zeros(2, 4, 3, device=cuda)
     cost, g1, g2 = backend.MatchCostImplicit(z1, z2, True)
     assert float(cost.abs().sum()) == 0.0 and g1.shape == (2, 0, 3) and float(g2.abs().sum()) == 0.0
+    # the other entry points zero-fill empty clouds too (C ABI, outputs pre-filled with NaN; temp is not written)
+    lib, st = _lib.lib, torch.cuda.current_stream(cuda).cuda_stream
+
+    def nan(*shape):
+        return torch.full(shape, float('nan'), device=cuda)
+
+    for n, m in ((0, 4), (4, 0)):
+        x1, x2 = torch.zeros(2, n, 3, device=cuda), torch.zeros(2, m, 3, device=cuda)
+        match, temp = torch.zeros(2, m, n, device=cuda), nan(2, 2 * (n + m))
+        cost = nan(2)
+        assert lib.pcc_approxmatch_cost(2, n, m, x1.data_ptr(), x2.data_ptr(), match.data_ptr(), temp.data_ptr(),
+                                        cost.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(cost, torch.zeros_like(cost))
+        cost = nan(2)
+        assert lib.pcc_matchcost(2, n, m, x1.data_ptr(), x2.data_ptr(), match.data_ptr(), cost.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(cost, torch.zeros_like(cost))
+        for scaled in (False, True):
+            g1, g2, gc = nan(2, n, 3), nan(2, m, 3), torch.ones(2, device=cuda)
+            if scaled:
+                rc = lib.pcc_matchcostgrad_scaled(2, n, m, x1.data_ptr(), x2.data_ptr(), match.data_ptr(), gc.data_ptr(),
+                                                  g1.data_ptr(), g2.data_ptr(), st)
+            else:
+                rc = lib.pcc_matchcostgrad(2, n, m, x1.data_ptr(), x2.data_ptr(), match.data_ptr(), g1.data_ptr(),
+                                           g2.data_ptr(), st)
+            torch.cuda.synchronize()
+            assert rc == 0 and torch.equal(g1, torch.zeros_like(g1)) and torch.equal(g2, torch.zeros_like(g2))
 
 
 def test_implicit_match_cost_bit_reproducible(cuda):
