@@ -7,17 +7,10 @@ from __future__ import annotations
 import torch
 
 from pointcloudcounterfactual_amd import _lib
+from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
-
-
-def _chk(t: torch.Tensor, name: str, dtype: torch.dtype) -> None:
-    if t.device.type != 'cuda':
-        raise RuntimeError(f'{name} must be a CUDA tensor')
-    if not t.is_contiguous():
-        raise RuntimeError(f'{name} must be contiguous')
-    if t.dtype != dtype:
-        raise RuntimeError(f'{name} must be {dtype}')
+F32, I32 = torch.float32, torch.int32
 
 
 def forward(xyz1, xyz2, dist, assignment, price=None, assignment_inv=None, bid=None, bid_increments=None,
@@ -25,10 +18,6 @@ def forward(xyz1, xyz2, dist, assignment, price=None, assignment_inv=None, bid=N
             eps: float = 0.005, iters: int = 50) -> int:
     """emd_cuda_forward (emd_cuda.cu:227-281): fills ``dist[B,n]`` and ``assignment[B,n]``; returns 1, or -1 with the
     reference's input errors (:235-248)."""
-    _chk(xyz1, 'xyz1', torch.float32)
-    _chk(xyz2, 'xyz2', torch.float32)
-    _chk(dist, 'dist', torch.float32)
-    _chk(assignment, 'assignment', torch.int32)
     b, n, _ = xyz1.shape
     if xyz2.shape[1] != n:
         print('Input Error! The two point clouds should have the same size.')
@@ -39,23 +28,16 @@ def forward(xyz1, xyz2, dist, assignment, price=None, assignment_inv=None, bid=N
     if n % 1024 != 0:
         print('Input Error! The size of the point clouds should be a multiple of 1024.')
         return -1
-    with torch.cuda.device(xyz1.device):
-        _lib.check(_L.pcc_auction_forward(b, n, xyz1.data_ptr(), xyz2.data_ptr(), float(eps), int(iters),
-                                          dist.data_ptr(), assignment.data_ptr(),
-                                          torch.cuda.current_stream(xyz1.device).cuda_stream), 'emd forward')
+    dev = xyz1.device
+    call(_L.pcc_auction_forward, 'emd forward', dev, b, n, ptr(xyz1, 'xyz1', F32, dev), ptr(xyz2, 'xyz2', F32, dev),
+         float(eps), int(iters), ptr(dist, 'dist', F32, dev), ptr(assignment, 'assignment', I32, dev))
     return 1
 
 
 def backward(xyz1, xyz2, gradxyz, graddist, idx) -> int:
     """emd_cuda_backward (emd_cuda.cu:301-315): ``gradxyz = 2 graddist (xyz1 - xyz2[idx])``."""
-    _chk(xyz1, 'xyz1', torch.float32)
-    _chk(xyz2, 'xyz2', torch.float32)
-    _chk(gradxyz, 'gradxyz', torch.float32)
-    _chk(graddist, 'graddist', torch.float32)
-    _chk(idx, 'idx', torch.int32)
     b, n, _ = xyz1.shape
-    with torch.cuda.device(xyz1.device):
-        _lib.check(_L.pcc_auction_backward(b, n, xyz1.data_ptr(), xyz2.data_ptr(), graddist.data_ptr(), idx.data_ptr(),
-                                           gradxyz.data_ptr(), torch.cuda.current_stream(xyz1.device).cuda_stream),
-                   'emd backward')
+    dev = xyz1.device
+    call(_L.pcc_auction_backward, 'emd backward', dev, b, n, ptr(xyz1, 'xyz1', F32, dev), ptr(xyz2, 'xyz2', F32, dev),
+         ptr(graddist, 'graddist', F32, dev), ptr(idx, 'idx', I32, dev), ptr(gradxyz, 'gradxyz', F32, dev))
     return 1

@@ -9,12 +9,13 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import Any
 
 # torch FIRST: libpcc_structural.so needs libamdhip64.so.7, and the process must end up with ONE HIP runtime.  With
 # torch imported before the library is loaded, the loader resolves that name to the runtime torch already brought in
 # (the copy bundled in torch/lib); loaded the other way round, the library pulls /opt/rocm's copy, torch then loads
 # its own, and launches through the first runtime on memory of the second fail with hipErrorNoDevice.
-import torch  # noqa: F401
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PCC_LIB_OVERRIDE') or os.path.join(_HERE, 'lib', 'libpcc_structural.so')  # override: A/B builds only
@@ -100,6 +101,30 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = lib.pcc_last_error().decode() or f'HIP kernel failed : {status}'
         raise RuntimeError(f'{what}: {msg}')
+
+
+def ptr(t: torch.Tensor | None, name: str, dtype: torch.dtype, device: torch.device) -> int | None:
+    """``t.data_ptr()`` once ``t`` is a contiguous ``dtype`` tensor on exactly the CUDA device ``device``; ``None`` is
+    passed through as NULL.  Every pointer handed to ``lib`` goes through here: a host pointer, another GPU's memory or
+    8-byte indices read from a 4-byte buffer can fault the card, so they are refused before anything is enqueued.
+    Reads tensor metadata only (no allocation, copy or synchronisation)."""
+    if t is None:
+        return None
+    if t.device != device or device.type != 'cuda':
+        if t.device.type != 'cuda':
+            raise RuntimeError(f'{name} must be a CUDA tensor')
+        raise RuntimeError(f'{name} is on {t.device}, expected {device}')
+    if not t.is_contiguous():
+        raise RuntimeError(f'{name} must be contiguous')
+    if t.dtype != dtype:
+        raise RuntimeError(f'{name} must be {dtype}, found {t.dtype}')
+    return t.data_ptr()
+
+
+def call(fn: Any, what: str, device: torch.device, *args: Any) -> None:
+    """``fn(*args, stream)`` on ``device`` and its current stream, raising through ``check(status, what)``."""
+    with torch.cuda.device(device):
+        check(fn(*args, torch.cuda.current_stream(device).cuda_stream), what)
 
 
 # include/pcc_test_hooks.h: measurement / bit-identity switches (inert unless PCC_TEST_HOOKS=1 is in the environment)

@@ -35,8 +35,10 @@ from torch.autograd import Function
 
 from pointcloudcounterfactual_amd import _lib
 from pointcloudcounterfactual_amd import neighbour_ops as ops
+from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
+F32, I64 = torch.float32, torch.int64
 
 
 class _NeighbourSum(Function):
@@ -47,10 +49,10 @@ class _NeighbourSum(Function):
         y = y.contiguous()
         b, c, n = y.shape
         k = idx.shape[2]
+        dev = y.device
         out = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            _lib.check(_L.pcc_neighbour_sum(b, c, n, k, y.data_ptr(), idx.data_ptr(), out.data_ptr(),
-                                            torch.cuda.current_stream(y.device).cuda_stream), 'neighbour_sum')
+        call(_L.pcc_neighbour_sum, 'neighbour_sum', dev, b, c, n, k, ptr(y, 'y', F32, dev), ptr(idx, 'idx', I64, dev),
+             ptr(out, 'out', F32, dev))
         ctx.save_for_backward(idx)
         return out
 
@@ -59,10 +61,10 @@ class _NeighbourSum(Function):
         (idx,) = ctx.saved_tensors
         grad = grad.contiguous()
         b, c, n = grad.shape
+        dev = grad.device
         gy = torch.empty_like(grad)
-        with torch.cuda.device(grad.device):
-            _lib.check(_L.pcc_neighbour_sum_bwd(b, c, n, idx.shape[2], idx.data_ptr(), grad.data_ptr(), gy.data_ptr(),
-                                                torch.cuda.current_stream(grad.device).cuda_stream), 'neighbour_sum_bwd')
+        call(_L.pcc_neighbour_sum_bwd, 'neighbour_sum_bwd', dev, b, c, n, idx.shape[2], ptr(idx, 'idx', I64, dev),
+             ptr(grad, 'grad', F32, dev), ptr(gy, 'grad_y', F32, dev))
         return gy, None
 
 
@@ -77,11 +79,10 @@ def neighbour_minmax_target(y: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     y = y.detach().contiguous()
     b, c, n = y.shape
     if y.device.type == 'cuda':
-        tsel = torch.empty((b, 2, c, n), dtype=torch.int64, device=y.device)
-        with torch.cuda.device(y.device):
-            _lib.check(_L.pcc_neighbour_minmax_target(b, c, n, idx.shape[2], y.data_ptr(), idx.contiguous().data_ptr(),
-                                                      tsel.data_ptr(), torch.cuda.current_stream(y.device).cuda_stream),
-                       'neighbour_minmax_target')
+        dev = y.device
+        tsel = torch.empty((b, 2, c, n), dtype=torch.int64, device=dev)
+        call(_L.pcc_neighbour_minmax_target, 'neighbour_minmax_target', dev, b, c, n, idx.shape[2], ptr(y, 'y', F32, dev),
+             ptr(idx.contiguous(), 'idx', I64, dev), ptr(tsel, 'tsel', I64, dev))
         return tsel
     nb = ops.get_neighbours(y, idx, idx.shape[2])[1]                      # [B,C,N,k]
     ie = idx[:, None, :, :].expand(-1, c, -1, -1)

@@ -32,9 +32,12 @@ from torch import nn
 
 from pointcloudcounterfactual_amd import _lib
 from pointcloudcounterfactual_amd import neighbour_ops as ops
+from pointcloudcounterfactual_amd._lib import call, ptr
 from pointcloudcounterfactual_amd.edgeconv import FusedEdgeConv
 from pointcloudcounterfactual_amd.keops_shim import SquareDistance
 from pointcloudcounterfactual_amd.losses import chamfer_emd
+
+F32 = torch.float32
 
 
 class EdgeConv(nn.Module):
@@ -57,14 +60,12 @@ class _BNReLURes(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, gamma, beta, res, r, mean, var, eps, training):  # noqa: ANN001
         b, c, n = z.shape
+        dev = z.device
         y = torch.empty_like(z)
-        st = torch.cuda.current_stream(z.device).cuda_stream
-        with torch.cuda.device(z.device):
-            _lib.check(_lib.lib.pcc_bn_relu_res_fwd(b, c, n, z.data_ptr(), mean.data_ptr(), var.data_ptr(), float(eps),
-                                                    gamma.data_ptr(), beta.data_ptr(),
-                                                    res.data_ptr() if res is not None else None,
-                                                    res.shape[1] if res is not None else 0, int(r), y.data_ptr(), st),
-                       'bn_relu_res_fwd')
+        call(_lib.lib.pcc_bn_relu_res_fwd, 'bn_relu_res_fwd', dev, b, c, n, ptr(z, 'z', F32, dev),
+             ptr(mean, 'mean', F32, dev), ptr(var, 'var', F32, dev), float(eps), ptr(gamma, 'gamma', F32, dev),
+             ptr(beta, 'beta', F32, dev), ptr(res, 'res', F32, dev), res.shape[1] if res is not None else 0, int(r),
+             ptr(y, 'y', F32, dev))
         ctx.save_for_backward(z, gamma, beta, mean, var)
         ctx.eps, ctx.training, ctx.r = float(eps), bool(training), int(r)
         ctx.res_shape = None if res is None else tuple(res.shape)
@@ -74,15 +75,15 @@ class _BNReLURes(torch.autograd.Function):
     def backward(ctx, gy):  # noqa: ANN001
         z, gamma, beta, mean, var = ctx.saved_tensors
         b, c, n = z.shape
+        dev = z.device
         gy = gy.contiguous()
         dz = torch.empty_like(z)
         dgamma = torch.empty_like(gamma)
         dbeta = torch.empty_like(beta)
-        st = torch.cuda.current_stream(z.device).cuda_stream
-        with torch.cuda.device(z.device):
-            _lib.check(_lib.lib.pcc_bn_relu_bwd(b, c, n, z.data_ptr(), mean.data_ptr(), var.data_ptr(), ctx.eps,
-                                                gamma.data_ptr(), beta.data_ptr(), gy.data_ptr(), int(ctx.training),
-                                                dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), st), 'bn_relu_bwd')
+        call(_lib.lib.pcc_bn_relu_bwd, 'bn_relu_bwd', dev, b, c, n, ptr(z, 'z', F32, dev), ptr(mean, 'mean', F32, dev),
+             ptr(var, 'var', F32, dev), ctx.eps, ptr(gamma, 'gamma', F32, dev), ptr(beta, 'beta', F32, dev),
+             ptr(gy, 'grad', F32, dev), int(ctx.training), ptr(dz, 'grad_z', F32, dev),
+             ptr(dgamma, 'grad_gamma', F32, dev), ptr(dbeta, 'grad_beta', F32, dev))
         dres = None
         if ctx.res_shape is not None and ctx.needs_input_grad[3]:
             r, used = ctx.r, c // ctx.r
@@ -112,9 +113,8 @@ class PointsConv(nn.Module):
         if self.training:
             mean = torch.empty(c, device=z.device, dtype=torch.float32)
             var = torch.empty_like(mean)
-            with torch.cuda.device(z.device):
-                _lib.check(_lib.lib.pcc_bn_stats(b, c, n, z.data_ptr(), mean.data_ptr(), var.data_ptr(),
-                                                 torch.cuda.current_stream(z.device).cuda_stream), 'bn_stats')
+            call(_lib.lib.pcc_bn_stats, 'bn_stats', z.device, b, c, n, ptr(z, 'z', F32, z.device),
+                 ptr(mean, 'mean', F32, z.device), ptr(var, 'var', F32, z.device))
             with torch.no_grad():  # running statistics exactly as nn.BatchNorm1d keeps them (unbiased variance)
                 m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
                 cnt = b * n

@@ -27,20 +27,10 @@ import torch
 from torch.autograd import Function
 
 from pointcloudcounterfactual_amd import _lib, backend
+from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
-
-
-def _stream(x: torch.Tensor) -> int:
-    return torch.cuda.current_stream(x.device).cuda_stream
-
-
-def _need_device(x: torch.Tensor, name: str) -> None:
-    if x.device.type != 'cuda':
-        raise RuntimeError(f'{name} must be a CUDA tensor (the reference only reaches PyKeOps on the accelerator, '
-                           'neighbour_ops.py:29,65)')
-    if x.dtype != torch.float32:
-        raise RuntimeError(f'expected scalar type Float but found {x.dtype} ({name})')
+F32 = torch.float32
 
 
 class LazyTensor:
@@ -106,10 +96,10 @@ class _PairSqdistSum(Function):
         p, q = p.contiguous(), q.contiguous()
         b, n_p, d = p.shape
         n_q = q.shape[1]
-        out = torch.empty((b, n_p), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_L.pcc_pair_sqdist_sum(b, n_p, n_q, d, p.data_ptr(), q.data_ptr(), out.data_ptr(), _stream(p)),
-                       'pair_sqdist_sum')
+        dev = p.device
+        out = torch.empty((b, n_p), dtype=torch.float32, device=dev)
+        call(_L.pcc_pair_sqdist_sum, 'pair_sqdist_sum', dev, b, n_p, n_q, d, ptr(p, 'p', F32, dev), ptr(q, 'q', F32, dev),
+             ptr(out, 'out', F32, dev))
         ctx.save_for_backward(p, q)
         return out
 
@@ -119,13 +109,11 @@ class _PairSqdistSum(Function):
         g = grad_outputs[0].contiguous().float()
         b, n_p, d = p.shape
         n_q = q.shape[1]
+        dev = p.device
         gp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
         gq = torch.empty_like(q) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(p.device):
-            _lib.check(_L.pcc_pair_sqdist_sum_bwd(b, n_p, n_q, d, p.data_ptr(), q.data_ptr(), g.data_ptr(),
-                                                  gp.data_ptr() if gp is not None else None,
-                                                  gq.data_ptr() if gq is not None else None, _stream(p)),
-                       'pair_sqdist_sum_bwd')
+        call(_L.pcc_pair_sqdist_sum_bwd, 'pair_sqdist_sum_bwd', dev, b, n_p, n_q, d, ptr(p, 'p', F32, dev),
+             ptr(q, 'q', F32, dev), ptr(g, 'grad', F32, dev), ptr(gp, 'grad_p', F32, dev), ptr(gq, 'grad_q', F32, dev))
         return gp, gq
 
 
@@ -148,9 +136,14 @@ class SquareDistance:
             raise NotImplementedError('LazyTensor shim: reductions run over axis 1 (i) or 2 (j)')
         return ax
 
+    def _need_device(self) -> None:
+        for x, name in ((self.rows, 'x_i'), (self.cols, 'y_j')):
+            if x.device.type != 'cuda':
+                raise RuntimeError(f'{name} must be a CUDA tensor (the reference only reaches PyKeOps on the '
+                                   'accelerator, neighbour_ops.py:29,65)')
+
     def _prepared(self) -> tuple[torch.Tensor, torch.Tensor]:
-        _need_device(self.rows, 'x_i')
-        _need_device(self.cols, 'y_j')
+        self._need_device()
         return self.rows.contiguous(), self.cols.contiguous()
 
     def _nearest(self) -> list[torch.Tensor]:
@@ -164,11 +157,11 @@ class SquareDistance:
         rows, cols = self._prepared()
         p, q = (rows, cols) if ax == 2 else (cols, rows)
         b, n_p, d = p.shape
-        idx = torch.empty((b, n_p), dtype=torch.int64, device=p.device)
-        val = torch.empty((b, n_p), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_L.pcc_pair_argmin(b, n_p, q.shape[1], d, p.data_ptr(), q.data_ptr(), idx.data_ptr(),
-                                          val.data_ptr(), _stream(p)), 'pair_argmin')
+        dev = p.device
+        idx = torch.empty((b, n_p), dtype=torch.int64, device=dev)
+        val = torch.empty((b, n_p), dtype=torch.float32, device=dev)
+        call(_L.pcc_pair_argmin, 'pair_argmin', dev, b, n_p, q.shape[1], d, ptr(p, 'p', F32, dev), ptr(q, 'q', F32, dev),
+             ptr(idx, 'idx', torch.int64, dev), ptr(val, 'val', F32, dev))
         return idx, val
 
     def argmin(self, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
@@ -205,8 +198,7 @@ class SquareDistance:
     def sum(self, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
         """``sum_i D`` -> ``[B,M,1]`` (axis=1) or ``sum_j D`` -> ``[B,N,1]`` (axis=2); differentiable."""
         ax = self._axis(axis, dim)
-        _need_device(self.rows, 'x_i')
-        _need_device(self.cols, 'y_j')
+        self._need_device()
         p, q = (self.rows, self.cols) if ax == 2 else (self.cols, self.rows)
         return _PairSqdistSum.apply(p, q).unsqueeze(-1)
 

@@ -18,20 +18,10 @@ import torch
 from torch.autograd import Function
 
 from pointcloudcounterfactual_amd import _lib
+from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
-
-
-def _stream(x: torch.Tensor) -> int:
-    return torch.cuda.current_stream(x.device).cuda_stream
-
-
-def _prep(x: torch.Tensor, indices: torch.Tensor | None = None) -> None:
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise RuntimeError('x must be a contiguous float32 tensor [B,C,N]')
-    if indices is not None and (indices.dtype != torch.int64 or not indices.is_contiguous()
-                                or indices.device != x.device):
-        raise RuntimeError('indices must be a contiguous int64 tensor [B,N,k] on the device of x')
+F32, I32, I64 = torch.float32, torch.int32, torch.int64
 
 
 # ---- squared distances (reference neighbour_ops.py:16-50) -----------------------------------------------------------------
@@ -98,11 +88,10 @@ def hip_knn(x: torch.Tensor, k: int) -> torch.Tensor:
     """``x[B,C,N] -> indices[B,N,k]`` int64, ascending distance, ties by ascending index (replaces ``pykeops_knn``).
     Any channel count C >= 1 and ``1 <= k <= min(N, 128)``."""
     x = x.contiguous()
-    _prep(x)
     b, c, n = x.shape
-    out = torch.empty((b, n, k), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_L.pcc_knn(b, c, n, k, x.data_ptr(), out.data_ptr(), _stream(x)), 'knn')
+    dev = x.device
+    out = torch.empty((b, n, k), dtype=torch.int64, device=dev)
+    call(_L.pcc_knn, 'knn', dev, b, c, n, k, ptr(x, 'x', F32, dev), ptr(out, 'indices', I64, dev))
     return out
 
 
@@ -127,13 +116,12 @@ class _Gather(Function):
     def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         indices = indices.contiguous()
-        _prep(x, indices)
         b, c, n = x.shape
         k = indices.shape[2]
-        out = torch.empty((b, c, n, k), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_L.pcc_gather_neighbours(b, c, n, k, x.data_ptr(), indices.data_ptr(), out.data_ptr(),
-                                                _stream(x)), 'gather_neighbours')
+        dev = x.device
+        out = torch.empty((b, c, n, k), dtype=torch.float32, device=dev)
+        call(_L.pcc_gather_neighbours, 'gather_neighbours', dev, b, c, n, k, ptr(x, 'x', F32, dev),
+             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev))
         ctx.save_for_backward(indices)
         ctx.shape = (b, c, n, k)
         return out
@@ -143,10 +131,10 @@ class _Gather(Function):
         (indices,) = ctx.saved_tensors
         b, c, n, k = ctx.shape
         grad = grad.contiguous()
-        gx = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
-        with torch.cuda.device(grad.device):
-            _lib.check(_L.pcc_gather_neighbours_bwd(b, c, n, k, indices.data_ptr(), grad.data_ptr(), gx.data_ptr(),
-                                                    _stream(grad)), 'gather_neighbours_bwd')
+        dev = grad.device
+        gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
+        call(_L.pcc_gather_neighbours_bwd, 'gather_neighbours_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
+             ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
         return gx, None
 
 
@@ -155,13 +143,12 @@ class _GraphFeatures(Function):
     def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         indices = indices.contiguous()
-        _prep(x, indices)
         b, c, n = x.shape
         k = indices.shape[2]
-        out = torch.empty((b, 2 * c, n, k), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_L.pcc_graph_features(b, c, n, k, x.data_ptr(), indices.data_ptr(), out.data_ptr(),
-                                             _stream(x)), 'graph_features')
+        dev = x.device
+        out = torch.empty((b, 2 * c, n, k), dtype=torch.float32, device=dev)
+        call(_L.pcc_graph_features, 'graph_features', dev, b, c, n, k, ptr(x, 'x', F32, dev),
+             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev))
         ctx.save_for_backward(indices)
         ctx.shape = (b, c, n, k)
         return out
@@ -171,10 +158,10 @@ class _GraphFeatures(Function):
         (indices,) = ctx.saved_tensors
         b, c, n, k = ctx.shape
         grad = grad.contiguous()
-        gx = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
-        with torch.cuda.device(grad.device):
-            _lib.check(_L.pcc_graph_features_bwd(b, c, n, k, indices.data_ptr(), grad.data_ptr(), gx.data_ptr(),
-                                                 _stream(grad)), 'graph_features_bwd')
+        dev = grad.device
+        gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
+        call(_L.pcc_graph_features_bwd, 'graph_features_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
+             ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
         return gx, None
 
 
@@ -183,14 +170,13 @@ class _GraphMaxPool(Function):
     def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         indices = indices.contiguous()
-        _prep(x, indices)
         b, c, n = x.shape
         k = indices.shape[2]
-        out = torch.empty((b, c, n), dtype=torch.float32, device=x.device)
-        arg = torch.empty((b, c, n), dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_L.pcc_graph_max_pool(b, c, n, k, x.data_ptr(), indices.data_ptr(), out.data_ptr(),
-                                             arg.data_ptr(), _stream(x)), 'graph_max_pool')
+        dev = x.device
+        out = torch.empty((b, c, n), dtype=torch.float32, device=dev)
+        arg = torch.empty((b, c, n), dtype=torch.int32, device=dev)
+        call(_L.pcc_graph_max_pool, 'graph_max_pool', dev, b, c, n, k, ptr(x, 'x', F32, dev),
+             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev), ptr(arg, 'arg', I32, dev))
         ctx.save_for_backward(indices, arg)
         ctx.shape = (b, c, n, k)
         return out
@@ -200,10 +186,10 @@ class _GraphMaxPool(Function):
         indices, arg = ctx.saved_tensors
         b, c, n, k = ctx.shape
         grad = grad.contiguous()
-        gx = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
-        with torch.cuda.device(grad.device):
-            _lib.check(_L.pcc_graph_max_pool_bwd(b, c, n, k, indices.data_ptr(), arg.data_ptr(), grad.data_ptr(),
-                                                 gx.data_ptr(), _stream(grad)), 'graph_max_pool_bwd')
+        dev = grad.device
+        gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
+        call(_L.pcc_graph_max_pool_bwd, 'graph_max_pool_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
+             ptr(arg, 'arg', I32, dev), ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
         return gx, None
 
 
@@ -211,13 +197,12 @@ class _GlobalMaxPool(Function):
     @staticmethod
     def forward(ctx: Any, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
-        _prep(x)
         b, c, n = x.shape
-        out = torch.empty((b, c), dtype=torch.float32, device=x.device)
-        arg = torch.empty((b, c), dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_L.pcc_global_pool(b, c, n, x.data_ptr(), out.data_ptr(), arg.data_ptr(), None, _stream(x)),
-                       'global_pool')
+        dev = x.device
+        out = torch.empty((b, c), dtype=torch.float32, device=dev)
+        arg = torch.empty((b, c), dtype=torch.int32, device=dev)
+        call(_L.pcc_global_pool, 'global_pool', dev, b, c, n, ptr(x, 'x', F32, dev), ptr(out, 'out', F32, dev),
+             ptr(arg, 'arg', I32, dev), None)
         ctx.save_for_backward(arg)
         ctx.n = n
         return out
@@ -299,15 +284,14 @@ def global_max_mean_pool(x: torch.Tensor) -> torch.Tensor:
     """``cat(max_n, mean_n)`` of the classifier head (``classifier.py:63-65``) in one read (inference only)."""
     if _on_gpu(x) and not x.requires_grad:
         x = x.contiguous()
-        _prep(x)
         b, c, n = x.shape
-        out = torch.empty((b, 2 * c), dtype=torch.float32, device=x.device)
+        dev = x.device
+        out = torch.empty((b, 2 * c), dtype=torch.float32, device=dev)
         mx = out[:, :c]
-        mean = torch.empty((b, c), dtype=torch.float32, device=x.device)
-        mxc = torch.empty((b, c), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_L.pcc_global_pool(b, c, n, x.data_ptr(), mxc.data_ptr(), None, mean.data_ptr(), _stream(x)),
-                       'global_pool')
+        mean = torch.empty((b, c), dtype=torch.float32, device=dev)
+        mxc = torch.empty((b, c), dtype=torch.float32, device=dev)
+        call(_L.pcc_global_pool, 'global_pool', dev, b, c, n, ptr(x, 'x', F32, dev), ptr(mxc, 'max', F32, dev), None,
+             ptr(mean, 'mean', F32, dev))
         mx.copy_(mxc)
         out[:, c:] = mean
         return out
