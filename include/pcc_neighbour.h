@@ -85,7 +85,9 @@ int pcc_global_pool(int b, int c, int n, const float *x, float *out_max, int32_t
  *   VectorQuantizer.quantize's `dist.argmin(axis=2)` (src/module/quantize.py:26-28); swap p and q for axis=1.
  * pcc_pair_sqdist_sum: out[b,i] = sum_j D[b,i,j] -- `dist.sum(1)` of quantize.py:31 (with p = codebook rows, q = the
  *   single query); pcc_pair_sqdist_sum_bwd: its gradients, grad_p[b,i,:] = 2 g[b,i] sum_j (p_i - q_j),
- *   grad_q[b,j,:] = -2 sum_i g[b,i] (p_i - q_j); either output may be NULL. */
+ *   grad_q[b,j,:] = -2 sum_i g[b,i] (p_i - q_j); either output may be NULL.
+ * pcc_pair_argmin: a NaN distance never wins; a row whose distances are all NaN (or all +inf) returns index 0 and
+ *   dist = +inf.  nq = 0: pcc_pair_argmin is PCC_EINVAL, pcc_pair_sqdist_sum writes zeros. */
 int pcc_pair_argmin(int b, int np, int nq, int d, const float *p, const float *q, int64_t *idx, float *dist,
                     pcc_stream_t stream);
 int pcc_pair_sqdist_sum(int b, int np, int nq, int d, const float *p, const float *q, float *out, pcc_stream_t stream);
@@ -98,7 +100,12 @@ int pcc_pair_sqdist_sum_bwd(int b, int np, int nq, int d, const float *p, const 
  * biased variance over b*n, accumulated in double), pcc_bn_relu_res_fwd
  *   y[b,ch,i] = max(0, (z - mean[ch]) * rsqrt(var[ch] + eps) * gamma[ch] + beta[ch]) + res[b, ch / r, i]   (res may be NULL)
  * and pcc_bn_relu_bwd (grad_z, grad_gamma[c], grad_beta[c]; `training` = the statistics depend on z).  The gradient of
- * the residual operand is grad_y summed over each group of r channels (left to the caller).  b*c <= 65535. */
+ * the residual operand is grad_y summed over each group of r channels (left to the caller).  b*c <= 65535.
+ * Non-finite values follow the PyTorch composition: a channel whose sum or sum of squares is not finite gets a NaN
+ * variance (only a finite negative rounding residue is clamped to 0); relu(NaN) = NaN; the backward zeroes the gradient
+ * where the pre-activation is <= 0 only, so a NaN pre-activation passes it (threshold_backward).
+ * The 16-byte accesses are used only when n % 4 == 0 and z, y, res / z, grad_y, grad_z are 16-byte aligned; any
+ * 4-byte-aligned contiguous tensor is accepted. */
 int pcc_bn_stats(int b, int c, int n, const float *z, float *mean, float *var, pcc_stream_t stream);
 int pcc_bn_relu_res_fwd(int b, int c, int n, const float *z, const float *mean, const float *var, float eps,
                         const float *gamma, const float *beta, const float *res, int res_c, int r, float *y,

@@ -5,11 +5,24 @@
 // backward = one reduction pass + one apply pass (PyTorch: threshold 3, BN backward ~5).  Everything here is
 // HBM-bound streaming with float4 accesses; statistics are accumulated in double and combined in a fixed order.
 //   y[b,c,i] = max(0, (z[b,c,i] - mean[c]) * invstd[c] * gamma[c] + beta[c]) + res[b, c / r, i]
+// Non-finite values follow the PyTorch composition: relu(NaN) = NaN, the variance of a channel that holds a NaN or an
+// infinity is NaN, and the backward passes the gradient where the pre-activation is NaN (threshold_backward zeroes
+// `pre <= 0` only).  The 16-byte accesses are taken only when n % 4 == 0 and every base they touch is 16-byte aligned.
 #include "pcc_common.hpp"
 
 #include "pcc_neighbour.h"
 
 namespace {
+
+// The pre-activation in the centred form fma(z - mean, sc, beta), as the composition evaluates it: z - mean is exact or
+// nearly so where a channel's mean is large, which fma(z, sc, beta - mean * sc) loses to cancellation, and the error
+// stays within (delta + 2u)(|z sc| + |mean sc|) + u |beta| (delta: the error of sc).  Forward and backward share it,
+// so both see the same ReLU mask.
+__device__ __forceinline__ float pre_act(float z, float mu, float sc, float bt) { return __builtin_fmaf(z - mu, sc, bt); }
+// torch.relu: a NaN stays NaN (fmaxf would return the 0)
+__device__ __forceinline__ float relu(float v) { return v < 0.f ? 0.f : v; }
+// the gradient that passes a ReLU with pre-activation `pre`: only pre <= 0 stops it (NaN passes, as in PyTorch)
+__device__ __forceinline__ float relu_grad(float pre, float g) { return pre <= 0.f ? 0.f : g; }
 
 // Channel reductions are cut into `splits` sample ranges (grid = channels x splits, so that even a 16-channel layer
 // fills the chip); every workgroup leaves two double partials and a small second kernel adds them in index order.
@@ -68,7 +81,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(int c, int splits, dou
     if (MODE == 0) {
         const double m = a / count;
         out0[ch] = (float)m;
-        out1[ch] = (float)fmax(q / count - m * m, 0.0);
+        const double v = q / count - m * m;
+        out1[ch] = (float)(v < 0.0 ? 0.0 : v);  // a negative rounding residue is 0; NaN (non-finite input) stays NaN
     } else {
         out0[ch] = (float)a;
         out1[ch] = (float)q;
@@ -86,23 +100,25 @@ __global__ __launch_bounds__(256) void bn_relu_res_fwd_kernel(int c, int n, cons
     const int row = blockIdx.y;  // b * c + ch
     const int ch = row % c, smp = row / c;
     const float sc = gamma[ch] * __builtin_amdgcn_rsqf(var[ch] + eps);
-    const float sh = beta[ch] - mean[ch] * sc;
+    const float mu = mean[ch], bt = beta[ch];
     const float *zr = z + (size_t)row * n;
     float *yr = y + (size_t)row * n;
     const float *rr = res ? res + ((size_t)smp * res_c + ch / r) * n : nullptr;
     const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
-    if (i + 3 < n && (n % 4 == 0)) {
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res);
+    const bool vec = (n % 4 == 0) && ((bases & 15) == 0);
+    if (vec) {
         const float4 v = *reinterpret_cast<const float4 *>(zr + i);
-        float4 o = make_float4(fmaxf(__builtin_fmaf(v.x, sc, sh), 0.f), fmaxf(__builtin_fmaf(v.y, sc, sh), 0.f),
-                               fmaxf(__builtin_fmaf(v.z, sc, sh), 0.f), fmaxf(__builtin_fmaf(v.w, sc, sh), 0.f));
+        float4 o = make_float4(relu(pre_act(v.x, mu, sc, bt)), relu(pre_act(v.y, mu, sc, bt)),
+                               relu(pre_act(v.z, mu, sc, bt)), relu(pre_act(v.w, mu, sc, bt)));
         if (rr) {
             const float4 q = *reinterpret_cast<const float4 *>(rr + i);
             o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
         }
         *reinterpret_cast<float4 *>(yr + i) = o;
     } else {
-        for (int j = i; j < min(i + 4, n); j++) yr[j] = fmaxf(__builtin_fmaf(zr[j], sc, sh), 0.f) + (rr ? rr[j] : 0.f);
+        for (int j = i; j < min(i + 4, n); j++) yr[j] = relu(pre_act(zr[j], mu, sc, bt)) + (rr ? rr[j] : 0.f);
     }
 }
 
@@ -118,7 +134,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_partial_kernel(int b, int c, 
     const int ch = blockIdx.x, sp = blockIdx.y, tid = threadIdx.x;
     const int s0 = (int)((long long)b * sp / splits), s1 = (int)((long long)b * (sp + 1) / splits);
     const float mu = mean[ch], inv = __builtin_amdgcn_rsqf(var[ch] + eps);
-    const float sc = gamma[ch] * inv, sh = beta[ch] - mu * sc;
+    const float sc = gamma[ch] * inv, bt = beta[ch];
     double s = 0.0, sx = 0.0;
     const bool vec = (n % 4 == 0) && (((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0);
     for (int smp = s0; smp < s1; smp++) {
@@ -132,7 +148,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_partial_kernel(int b, int c, 
                 float ps = 0.f, px = 0.f;  // four terms in float, the running sums in double
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    const float g = __builtin_fmaf(vv[q], sc, sh) > 0.f ? gg[q] : 0.f;
+                    const float g = relu_grad(pre_act(vv[q], mu, sc, bt), gg[q]);
                     ps += g;
                     px = __builtin_fmaf(g, (vv[q] - mu) * inv, px);
                 }
@@ -142,7 +158,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_partial_kernel(int b, int c, 
         } else {
             for (int i = tid; i < n; i += 256) {
                 const float v = zr[i];
-                const float g = __builtin_fmaf(v, sc, sh) > 0.f ? gr[i] : 0.f;
+                const float g = relu_grad(pre_act(v, mu, sc, bt), gr[i]);
                 s += g;
                 sx += (double)g * ((v - mu) * inv);
             }
@@ -179,29 +195,32 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(int c, int n, fl
     const int row = blockIdx.y;
     const int ch = row % c;
     const float mu = mean[ch], inv = __builtin_amdgcn_rsqf(var[ch] + eps);
-    const float gsc = gamma[ch] * inv, sh = beta[ch] - mu * gsc;
-    const float a = sum_g ? sum_g[ch] * inv_count : 0.f, bq = sum_gx ? sum_gx[ch] * inv_count : 0.f;
+    const float gsc = gamma[ch] * inv, bt = beta[ch];
+    const bool training = sum_g != nullptr;  // eval: dz = gsc * g_act, whatever xhat is (0 * inf would be NaN)
+    const float a = training ? sum_g[ch] * inv_count : 0.f, bq = training ? sum_gx[ch] * inv_count : 0.f;
     const float *zr = z + (size_t)row * n;
     const float *gr = gy + (size_t)row * n;
     float *dr = dz + (size_t)row * n;
     const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
-    if (i0 + 3 < n && n % 4 == 0) {
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(dz);
+    const bool vec = (n % 4 == 0) && ((bases & 15) == 0);
+    if (vec) {
         const float4 v4 = *reinterpret_cast<const float4 *>(zr + i0);
         const float4 g4 = *reinterpret_cast<const float4 *>(gr + i0);
         const float vv[4] = {v4.x, v4.y, v4.z, v4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
         float o[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const float g = __builtin_fmaf(vv[q], gsc, sh) > 0.f ? gg[q] : 0.f;
-            o[q] = gsc * (g - a - ((vv[q] - mu) * inv) * bq);
+            const float g = relu_grad(pre_act(vv[q], mu, gsc, bt), gg[q]);
+            o[q] = gsc * (training ? g - a - ((vv[q] - mu) * inv) * bq : g);
         }
         *reinterpret_cast<float4 *>(dr + i0) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
         for (int j = i0; j < min(i0 + 4, n); j++) {
             const float v = zr[j];
-            const float g = __builtin_fmaf(v, gsc, sh) > 0.f ? gr[j] : 0.f;
-            dr[j] = gsc * (g - a - ((v - mu) * inv) * bq);
+            const float g = relu_grad(pre_act(v, mu, gsc, bt), gr[j]);
+            dr[j] = gsc * (training ? g - a - ((v - mu) * inv) * bq : g);
         }
     }
 }

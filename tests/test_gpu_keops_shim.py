@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.bn_pair_reference import assert_close
+from tests.bn_pair_reference import g as gamma_k  # k u / (1 - k u)
 from tests.util import pair
 
 pytestmark = pytest.mark.gpu
@@ -90,10 +92,14 @@ def test_vector_quantizer_restated(cuda, batch, n_codes, book, d):
     dense = ((xd[:, :, None, :] - cd.repeat(batch, 1, 1)[:, None, :, :]) ** 2).sum(-1)  # [B', 1, book]
     assert torch.equal(idx_flat.view(-1), dense.argmin(2).view(-1))
     dense_sum = dense.sum(1).view(batch, n_codes, book)
-    np.testing.assert_allclose(dist_sum.detach().cpu().numpy(), dense_sum.detach().cpu().numpy(), rtol=1e-5, atol=1e-6)
+    # the bounds of tests/bn_pair_reference.py with p = the book rows (np = book), q = the single query (nq = 1):
+    # the sum g(nq + d + 3) sum64; the query's gradient 2 g(np + 3) sum_i |w_i (p_i - q)|; a book row's gradient
+    # 2 |w| g(nq + 2) |p - q| per repeated copy, and autograd's sum over the `batch` copies, g(batch + 3) in all
+    assert_close('dist_sum', dist_sum.detach(), dense_sum.detach(), gamma_k(1 + d + 3) * dense_sum.detach())
     (dense_sum * w.double()).sum().backward()
-    np.testing.assert_allclose(x.grad.cpu().numpy(), xd.grad.view(batch, n_codes * d).cpu().numpy(), rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(codebook.grad.cpu().numpy(), cd.grad.cpu().numpy(), rtol=1e-4, atol=1e-4)
+    mag = 2 * w.double().view(batch, n_codes, book, 1) * (xd.detach().view(batch, n_codes, 1, d) - cd.detach()).abs()
+    assert_close('x.grad', x.grad.view(batch, n_codes, d), xd.grad.view(batch, n_codes, d), gamma_k(book + 3) * mag.sum(2))
+    assert_close('codebook.grad', codebook.grad, cd.grad, gamma_k(batch + 3) * mag.sum(0))
 
 
 def test_general_dimension_argmin_and_sum_axes(cuda):
@@ -108,12 +114,14 @@ def test_general_dimension_argmin_and_sum_axes(cuda):
     a2, a1 = dist.argmin(axis=2), dist.argmin(dim=1)
     assert a2.shape == (2, 40, 1) and a1.shape == (2, 33, 1)
     assert not (a2 == 20).any()
-    np.testing.assert_allclose(D.gather(2, a2).squeeze(-1).cpu().numpy(), D.min(2)[0].cpu().numpy(), rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(D.gather(1, a1.transpose(1, 2)).squeeze(1).cpu().numpy(), D.min(1)[0].cpu().numpy(),
-                               rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(dist.min(axis=2).squeeze(-1).cpu().numpy(), D.min(2)[0].cpu().numpy(), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(dist.sum(axis=2).squeeze(-1).cpu().numpy(), D.sum(2).cpu().numpy(), rtol=1e-5)
-    np.testing.assert_allclose(dist.sum(axis=1).squeeze(-1).cpu().numpy(), D.sum(1).cpu().numpy(), rtol=1e-5)
+    # the bounds of tests/bn_pair_reference.py, d = 5: a distance g(d + 3) relative, the distance at the returned index
+    # within 2 g(d + 3) of the minimum, a sum over m points g(m + d + 3) relative
+    at2, at1 = D.gather(2, a2).squeeze(-1), D.gather(1, a1.transpose(1, 2)).squeeze(1)
+    assert (at2 <= D.min(2)[0] * (1 + 2 * gamma_k(8))).all() and (at1 <= D.min(1)[0] * (1 + 2 * gamma_k(8))).all()
+    assert_close('min over j', dist.min(axis=2).squeeze(-1), at2, gamma_k(8) * at2)
+    assert_close('min over i', dist.min(axis=1).squeeze(-1), at1, gamma_k(8) * at1)
+    assert_close('sum over j', dist.sum(axis=2).squeeze(-1), D.sum(2), gamma_k(33 + 8) * D.sum(2))
+    assert_close('sum over i', dist.sum(axis=1).squeeze(-1), D.sum(1), gamma_k(40 + 8) * D.sum(1))
 
 
 def test_neighbour_ops_square_distance_exports(cuda):
