@@ -32,6 +32,23 @@ extern "C" {
  * runs short because of NaN distances is padded with the in-range index n - 1. */
 int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_stream_t stream);
 
+/* k-NN between two clouds: for every query q[b, :, i] (q[b, c, nq], channels-major like x) its k nearest candidates of
+ * x[b, c, n]: indices[b, nq, k] into x and, when dist is non-null, dist[b, nq, k], the squared distances of those entries.
+ * The contract is pcc_knn's with the query taken from q:
+ *   c <= 3 : difference form, df = x[ch][j] - q[ch][i], acc = df0 * df0, then fmaf(df, df, acc) in channel order
+ *   c >= 4 : expanded form (-2*dot + |x_j|^2) + |q_i|^2, dot and both norms sequential fma chains over the channel index
+ * Per query the k candidates ascending by (distance, index); -0 equals +0 (and is reported as +0); a NaN distance never
+ * enters a list; a list that runs short because of NaN distances is padded with index n - 1, and dist of a padded slot is
+ * NaN.  Requires c >= 1, 1 <= k <= min(n, 128), b <= 65535, b * nq < 2^31, and n <= 65535 * 128 when c >= 4
+ * (PCC_EINVAL otherwise); nq = 0 or b = 0 enqueues nothing and returns PCC_OK.  64-bit offsets throughout.  Workspace
+ * comes from the library's private pool; the distance rows of c >= 4 are capped at 256 MB per launch pair (larger calls
+ * run in chunks of samples or of queries).  With few queries and many candidates the candidate axis is searched in slices
+ * that are merged afterwards; the result does not depend on it.
+ * pcc_knn_cross(b, c, n, n, k, x, x, ...) returns the indices of pcc_knn(b, c, n, k, x, ...) bit for bit, and q and x may
+ * alias. */
+int pcc_knn_cross(int b, int c, int nq, int n, int k, const float *q, const float *x, int64_t *indices, float *dist,
+                  pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

@@ -31,7 +31,8 @@ enum {
     PCC_TUNE_NBRSUM_SCATTER = 6,   /* neighbour-sum backward: the per-edge ds_add_f32 scatter */
     PCC_TUNE_AUCTION_CLUSTER = 7,  /* auction: value 1 = one workgroup per sample, 2..16 = that many per sample */
     PCC_TUNE_KNN_NOSPLIT = 8,      /* c >= 4 k-NN: 1 = the 128-query kernel everywhere, 2 = the role-split kernel everywhere */
-    PCC_TUNE_KNN_WIDE = 9          /* k-NN: 1 = every call through the wide path (knn_wide.hip), also where k <= 32, c <= 128 */
+    PCC_TUNE_KNN_WIDE = 9,         /* k-NN: 1 = every call through the wide path (knn_wide.hip), also where k <= 32, c <= 128 */
+    PCC_TUNE_KNN_CROSS_SPLIT = 10  /* pcc_knn_cross: S >= 1 = the candidate axis in S slices (1 = one wave per query); 0 = by the row count */
 };
 int pcc_test_set_tuning(int key, int value);
 

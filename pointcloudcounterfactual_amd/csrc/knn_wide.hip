@@ -13,10 +13,19 @@
 // e = lane + 64 h in register h.  Candidates are tested 64 at a time against the current k-th key; the few that pass are
 // appended to a buffer of L keys in LDS (ballot + mbcnt: no lane waits for another), and a full buffer is merged into
 // the list by one bitonic sort of list + buffer in registers (the lower half is the new list).
+//
+// pcc_knn_cross (k neighbours of one cloud IN another, include/pcc_neighbour.h) runs the same two kernels with a second
+// operand: the queries come from q[b][c][nq], the candidates from x[b][c][n]; the self search passes q = x.  The distances
+// of the selected entries are recovered from the keys (the map of wide_key is invertible) when the caller asks for them.
+// Few queries against many candidates (rows < 8 x CUs) would leave the chip empty with one wave per query: the selection
+// then runs per (query, slice of the candidate axis), every wave writes its sorted list of L keys to workspace, and the
+// same kernel, reading keys instead of distances, keeps the lowest k of a query's lists.  Keys are a total order
+// (distance bits : candidate index), so the result does not depend on the number of slices.
 #include <algorithm>
 
 #include "pcc_common.hpp"
 #include "pcc_neighbour.h"
+#include "pcc_test_hooks.h"
 #include "wave_sort.hpp"
 
 namespace {
@@ -37,13 +46,22 @@ __device__ __forceinline__ u64 wide_key(float d, int j) {
     return ((u64)o << 32) | (unsigned)j;
 }
 
-// c >= 4: distances of queries q0 + [0, nq) against all n candidates of samples s0 + blockIdx.z, to
-// D[blockIdx.z][q - q0][j].  Workgroup = 4 waves, 128 queries x 128 candidates; wave w owns queries w*32 + [0, 32) against
+// the distance a key was made from (+0 for either zero)
+__device__ __forceinline__ float wide_key_dist(u64 key) {
+    const unsigned o = (unsigned)(key >> 32);
+    return __uint_as_float((o & 0x80000000u) ? o ^ 0x80000000u : ~o);
+}
+
+// c >= 4: distances of queries q0 + [0, nq) of q[b][c][nqt] against all n candidates of x[b][c][n], samples
+// s0 + blockIdx.z, to D[blockIdx.z][q - q0][j] (sqq, sqx: the squared norms of the two clouds; the self search passes
+// q = x, sqq = sqx, nqt = n).  Workgroup = 4 waves, 128 queries x 128 candidates; wave w owns queries w*32 + [0, 32) against
 // the four 32-candidate tiles (four independent accumulator chains).  MFMA A = queries, B = candidates, so accumulator
 // register r of lane (half, col) is query (r & 3) + 8 (r >> 2) + 4 half, candidate col: the stores of a register are
 // 32 consecutive candidates of one row.
-__global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq, int q0, int s0, const float *__restrict__ x,
-                                                            const float *__restrict__ sq, float *__restrict__ D) {
+__global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nqt, int nq, int q0, int s0,
+                                                            const float *__restrict__ q, const float *__restrict__ x,
+                                                            const float *__restrict__ sqq, const float *__restrict__ sqx,
+                                                            float *__restrict__ D) {
     constexpr int E = kDCH * kDT / 256;  // elements per thread per operand per chunk
     __shared__ __attribute__((aligned(16))) float sQ[2][kDCH][kDT];
     __shared__ __attribute__((aligned(16))) float sC[2][kDCH][kDT];
@@ -51,8 +69,8 @@ __global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, col = lane & 31;
     const int smp = s0 + (int)blockIdx.z;
-    const float *xb = x + (size_t)smp * c * n;
-    const float *sqb = sq + (size_t)smp * n;
+    const float *qb = q + (size_t)smp * c * nqt, *xb = x + (size_t)smp * c * n;
+    const float *sqqb = sqq + (size_t)smp * nqt, *sqxb = sqx + (size_t)smp * n;
     const int qt = blockIdx.x * kDT, ct = blockIdx.y * kDT;  // first local query / first candidate of the workgroup
     const int nch = pcc::ceil_div(c, kDCH);
 
@@ -62,7 +80,7 @@ __global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq
 #pragma unroll
         for (int i = 0; i < E; i++) {
             const int e = tid + i * 256, ch = min(ch0 + (e >> 7), c - 1), p = e & (kDT - 1);
-            pq[i] = xb[(size_t)ch * n + min(q0 + qt + p, n - 1)];
+            pq[i] = qb[(size_t)ch * nqt + min(q0 + qt + p, nqt - 1)];
             pc[i] = xb[(size_t)ch * n + min(ct + p, n - 1)];
         }
     };
@@ -100,34 +118,44 @@ __global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq
 #pragma unroll
     for (int u = 0; u < 4; u++) {
         const int j = ct + u * 32 + col;
-        const float sqj = sqb[min(j, n - 1)];
+        const float sqj = sqxb[min(j, n - 1)];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int ql = qt + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
             if (ql < nq && j < n) {
-                // the reference CPU path: dist = -2*dot ; dist += |xj|^2 ; dist += |xi|^2
-                const float d = (-2.0f * acc[u][r] + sqj) + sqb[q0 + ql];
+                // the reference CPU path: dist = -2*dot ; dist += |xj|^2 ; dist += |qi|^2
+                const float d = (-2.0f * acc[u][r] + sqj) + sqqb[q0 + ql];
                 D[((size_t)blockIdx.z * nq + ql) * n + j] = d;
             }
         }
     }
 }
 
+enum WideSrc { kSrcDiff = 0, kSrcRows = 1, kSrcKeys = 2 };  // where the selection kernel takes its candidates from
+
 struct WideSelArgs {
     int c, n, k;
     int rows;         // queries of this launch: row r is sample s0 + r / nq, query q0 + r % nq
     int nq, q0, s0;
-    const float *x;   // DIFF: the cloud [b][c][n]
-    const float *D;   // otherwise: distances [rows][n]
-    int64_t *out;     // [b][n][k]
+    int nqt;          // queries per sample of the whole call: the row stride of q and of the outputs
+    int slices, slice_len;  // the candidate axis in `slices` runs of slice_len candidates (blockIdx.y); 1: one wave scans all
+    const float *q;   // kSrcDiff: the query cloud [b][c][nqt]
+    const float *x;   // kSrcDiff: the candidate cloud [b][c][n]
+    const float *D;   // kSrcRows: distances [rows][n]
+    u64 *part;        // slices > 1: the sorted lists of the slices, [rows][slices][L] (written; kSrcKeys reads them)
+    int64_t *out;     // [b][nqt][k]
+    float *dist;      // [b][nqt][k] or null
 };
 
 constexpr int kSelW = 4;  // waves (= queries) per selection workgroup
 
-// L = list slots (64 or 128, >= k).  One wave per query; see the file header.
-template <int L, bool DIFF>
+// L = list slots (64 or 128, >= k).  One wave per query (per query and slice when the candidate axis is cut, with the
+// list going to a.part instead of the outputs); kSrcKeys selects among the keys of a query's slice lists.  See the file
+// header.
+template <int L, int SRC>
 __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs a) {
     constexpr int R = L / 64;  // list keys per lane
+    constexpr bool DIFF = SRC == kSrcDiff;
     __shared__ u64 sbuf[kSelW][L];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -136,14 +164,20 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
     u64 *buf = sbuf[w];
     const int n = a.n, k = a.k;
     const int smp = a.s0 + row / a.nq, q = a.q0 + row % a.nq;
+    const bool partial = SRC != kSrcKeys && a.slices > 1;
+    u64 *plist = a.slices > 1 ? a.part + (size_t)row * a.slices * L : nullptr;
+    // candidates [lo, hi) of this wave: indices into the cloud, or into the keys of the query's slice lists
+    const int lo = partial ? (int)blockIdx.y * a.slice_len : 0;
+    const int hi = SRC == kSrcKeys ? a.slices * L : (partial ? min(n, lo + a.slice_len) : n);
 
     const float *xb = nullptr, *drow = nullptr;
     float qc[3] = {0.f, 0.f, 0.f};
     if (DIFF) {
         xb = a.x + (size_t)smp * a.c * n;
+        const float *qb = a.q + (size_t)smp * a.c * a.nqt;
 #pragma unroll
-        for (int ch = 0; ch < 3; ch++) qc[ch] = ch < a.c ? xb[(size_t)ch * n + q] : 0.f;
-    } else {
+        for (int ch = 0; ch < 3; ch++) qc[ch] = ch < a.c ? qb[(size_t)ch * a.nqt + q] : 0.f;
+    } else if (SRC == kSrcRows) {
         drow = a.D + (size_t)row * n;
     }
     auto dist = [&](int j) -> float {
@@ -160,6 +194,12 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
             return acc;
         }
         return drow[j];
+    };
+    // the key of candidate j (j clamped into [lo, hi) by the caller), kWideKeyMax if it can never enter a list
+    auto cand = [&](int j) -> u64 {
+        if (SRC == kSrcKeys) return plist[j];
+        const float d = dist(j);
+        return d == d ? wide_key(d, j) : kWideKeyMax;  // (a NaN distance never enters)
     };
 
     u64 list[R];
@@ -186,51 +226,138 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
     };
 
     constexpr int U = 4;  // candidate blocks of 64 whose loads are issued together
-    for (int j0 = 0; j0 < n; j0 += 64 * U) {
-        float d[U];
+    for (int j0 = lo; j0 < hi; j0 += 64 * U) {
+        u64 key[U];
 #pragma unroll
-        for (int u = 0; u < U; u++) d[u] = dist(min(j0 + 64 * u + lane, n - 1));
+        for (int u = 0; u < U; u++) key[u] = cand(min(j0 + 64 * u + lane, hi - 1));
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int j = j0 + 64 * u + lane;
-            if (j0 + 64 * u >= n) break;  // (wave-uniform)
-            const u64 key = wide_key(d[u], j);
-            bool pass = j < n && d[u] == d[u] && key < thr;  // (a NaN distance never enters)
+            if (j0 + 64 * u >= hi) break;  // (wave-uniform)
+            bool pass = j < hi && key[u] < thr;
             u64 m = __ballot(pass);
             int np = __popcll(m);
             if (cnt + np > L) {
                 merge();
-                pass = pass && key < thr;
+                pass = pass && key[u] < thr;
                 m = __ballot(pass);
                 np = __popcll(m);
             }
-            if (pass) buf[cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = key;
+            if (pass) buf[cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = key[u];
             cnt += np;
         }
     }
     if (cnt > 0) merge();
 
-    int64_t *dst = a.out + ((size_t)smp * n + q) * k;
+    if (partial) {  // this slice's list, sorted, empty slots included
+        u64 *dst = plist + (size_t)blockIdx.y * L;
+#pragma unroll
+        for (int h = 0; h < R; h++) dst[lane + 64 * h] = list[h];
+        return;
+    }
+    const size_t o = ((size_t)smp * a.nqt + q) * k;
 #pragma unroll
     for (int h = 0; h < R; h++) {
         const int s = lane + 64 * h;
         if (s < k) {
             const unsigned j = (unsigned)list[h];
-            dst[s] = (int64_t)(j < (unsigned)n ? (int)j : n - 1);  // (an empty slot only when distances are NaN)
+            const bool real = j < (unsigned)n;  // (an empty slot only when distances are NaN)
+            a.out[o + s] = (int64_t)(real ? (int)j : n - 1);
+            if (a.dist) a.dist[o + s] = real ? wide_key_dist(list[h]) : __builtin_nanf("");
         }
     }
 }
 
-template <int L, bool DIFF>
+template <int L, int SRC>
 void launch_select(const WideSelArgs &a, hipStream_t st) {
     pcc::ProfScope prof("knn_wide_select_kernel", st);
-    hipLaunchKernelGGL((knn_wide_select_kernel<L, DIFF>), dim3(pcc::ceil_div(a.rows, kSelW)), dim3(64 * kSelW), 0, st, a);
+    hipLaunchKernelGGL((knn_wide_select_kernel<L, SRC>), dim3(pcc::ceil_div(a.rows, kSelW), SRC == kSrcKeys ? 1 : a.slices),
+                       dim3(64 * kSelW), 0, st, a);
 }
 
-template <bool DIFF>
+template <int SRC>
 void launch_select(const WideSelArgs &a, hipStream_t st) {
-    if (a.k <= 64) launch_select<64, DIFF>(a, st);
-    else launch_select<128, DIFF>(a, st);
+    if (a.k <= 64) launch_select<64, SRC>(a, st);
+    else launch_select<128, SRC>(a, st);
+}
+
+// Slices of the candidate axis for a launch of `rows` queries (pcc_knn_cross only; the self search never splits).  One wave
+// per query fills the chip from 8 waves per CU on (two per SIMD); below that, enough slices to get there, at most 64
+// (the query's wave then merges <= 64 lists) and none shorter than 2048 candidates.  0 CUs (query failed): no split.
+int cross_slices(int rows, int n) {
+    const int sw = pcc::tuning(PCC_TUNE_KNN_CROSS_SPLIT);  // measurement switch: S >= 1 forces S slices
+    if (sw >= 1) return std::min(sw, 4096);
+    const int target = 8 * pcc::device_cus();
+    if (rows >= target) return 1;
+    return std::max(1, std::min({pcc::ceil_div(target, rows), 64, n / 2048}));
+}
+
+// The selection of one launch: a.slices == 1 straight to the outputs, otherwise per slice to workspace and a second launch
+// that keeps the lowest k keys of each query's lists.
+template <int SRC>
+int select_rows(WideSelArgs a, int slices, hipStream_t st) {
+    // whole blocks of 256 candidates per slice (the loop's unit), no empty slice
+    a.slice_len = pcc::ceil_div(pcc::ceil_div(a.n, slices), 256) * 256;
+    a.slices = pcc::ceil_div(a.n, a.slice_len);
+    if (a.slices == 1) {
+        launch_select<SRC>(a, st);
+        return pcc::check_launch("knn(wide select)");
+    }
+    pcc::WsBlock part(st);
+    const int L = a.k <= 64 ? 64 : 128;
+    if (int rc = part.alloc((size_t)a.rows * a.slices * L * sizeof(u64), "knn: workspace allocation failed")) return rc;
+    a.part = static_cast<u64 *>(part.p);
+    launch_select<SRC>(a, st);
+    if (int rc = pcc::check_launch("knn(wide select)")) return rc;
+    launch_select<kSrcKeys>(a, st);
+    return pcc::check_launch("knn(wide merge)");
+}
+
+// The search behind pcc_knn's wide path (q = x, nqt = n, no distances, never split) and pcc_knn_cross.
+int wide_search(int b, int c, int nqt, int n, int k, const float *q, const float *x, int64_t *indices, float *dist, bool cross,
+                hipStream_t st) {
+    using namespace pcc;
+    WideSelArgs a{};
+    a.c = c; a.n = n; a.k = k; a.nqt = nqt; a.q = q; a.x = x; a.out = indices; a.dist = dist;
+    if (c <= 3) {
+        a.rows = b * nqt; a.nq = nqt; a.q0 = 0; a.s0 = 0;
+        return select_rows<kSrcDiff>(a, cross ? cross_slices(a.rows, n) : 1, st);
+    }
+    // distance rows per launch pair: whole samples while they fit, otherwise a multiple of 128 queries of one sample
+    const size_t cap = kWideRowsBytes / sizeof(float);
+    const size_t per_smp = (size_t)nqt * n;
+    int ns, nq;
+    if (per_smp <= cap) {
+        ns = (int)std::min<size_t>((size_t)b, cap / per_smp);
+        nq = nqt;
+    } else {
+        ns = 1;
+        nq = (int)std::min<size_t>((size_t)nqt, std::max<size_t>(kDT, cap / n / kDT * kDT));
+    }
+    const bool self = q == x && nqt == n;  // one norm row serves both operands
+    WsBlock sq(st), dw(st);
+    if (int rc = sq.alloc(((size_t)b * n + (self ? 0 : (size_t)b * nqt)) * sizeof(float), "knn: workspace allocation failed")) return rc;
+    if (int rc = dw.alloc((size_t)ns * nq * n * sizeof(float), "knn: workspace allocation failed")) return rc;
+    float *sqx = static_cast<float *>(sq.p), *sqq = self ? sqx : sqx + (size_t)b * n, *D = static_cast<float *>(dw.p);
+    launch_sqnorm(b, c, n, x, sqx, st);
+    if (!self) launch_sqnorm(b, c, nqt, q, sqq, st);
+    if (int rc = check_launch("knn(wide sqnorm)")) return rc;
+    a.D = D;
+    for (int s0 = 0; s0 < b; s0 += ns) {
+        const int cs = std::min(ns, b - s0);
+        for (int q0 = 0; q0 < nqt; q0 += nq) {
+            const int cq = std::min(nq, nqt - q0);
+            {
+                pcc::ProfScope prof("knn_wide_dist_kernel", st);
+                hipLaunchKernelGGL(knn_wide_dist_kernel, dim3(ceil_div(cq, kDT), ceil_div(n, kDT), cs), dim3(256), 0, st, c, n, nqt,
+                                   cq, q0, s0, q, x, sqq, sqx, D);
+            }
+            if (int rc = check_launch("knn(wide distances)")) return rc;
+            a.rows = cs * cq; a.nq = cq; a.q0 = q0; a.s0 = s0;
+            if (int rc = select_rows<kSrcRows>(a, cross ? cross_slices(a.rows, n) : 1, st)) return rc;
+        }
+    }
+    return PCC_OK;
 }
 
 }  // namespace
@@ -239,47 +366,21 @@ namespace pcc {
 
 // Sizes are validated by pcc_knn: 1 <= k <= min(n, 128), b <= 65535, non-null pointers.
 int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st) {
-    WideSelArgs a{};
-    a.c = c; a.n = n; a.k = k; a.x = x; a.out = indices;
-    if (c <= 3) {
-        a.rows = b * n; a.nq = n; a.q0 = 0; a.s0 = 0;
-        launch_select<true>(a, st);
-        return check_launch("knn(wide select)");
-    }
-    // distance rows per launch pair: whole samples while they fit, otherwise a multiple of 128 queries of one sample
-    const size_t cap = kWideRowsBytes / sizeof(float);
-    const size_t per_smp = (size_t)n * n;
-    int ns, nq;
-    if (per_smp <= cap) {
-        ns = (int)std::min<size_t>((size_t)b, cap / per_smp);
-        nq = n;
-    } else {
-        ns = 1;
-        nq = (int)std::min<size_t>((size_t)n, std::max<size_t>(kDT, cap / n / kDT * kDT));
-    }
-    WsBlock sq(st), dw(st);
-    if (int rc = sq.alloc((size_t)b * n * sizeof(float), "knn: workspace allocation failed")) return rc;
-    if (int rc = dw.alloc((size_t)ns * nq * n * sizeof(float), "knn: workspace allocation failed")) return rc;
-    float *sqp = static_cast<float *>(sq.p), *D = static_cast<float *>(dw.p);
-    launch_sqnorm(b, c, n, x, sqp, st);
-    if (int rc = check_launch("knn(wide sqnorm)")) return rc;
-    a.D = D;
-    for (int s0 = 0; s0 < b; s0 += ns) {
-        const int cs = std::min(ns, b - s0);
-        for (int q0 = 0; q0 < n; q0 += nq) {
-            const int cq = std::min(nq, n - q0);
-            {
-                pcc::ProfScope prof("knn_wide_dist_kernel", st);
-                hipLaunchKernelGGL(knn_wide_dist_kernel, dim3(ceil_div(cq, kDT), ceil_div(n, kDT), cs), dim3(256), 0, st, c, n, cq,
-                                   q0, s0, x, sqp, D);
-            }
-            if (int rc = check_launch("knn(wide distances)")) return rc;
-            a.rows = cs * cq; a.nq = cq; a.q0 = q0; a.s0 = s0;
-            launch_select<false>(a, st);
-            if (int rc = check_launch("knn(wide select)")) return rc;
-        }
-    }
-    return PCC_OK;
+    return wide_search(b, c, n, n, k, x, x, indices, nullptr, false, st);
 }
 
 }  // namespace pcc
+
+extern "C" int pcc_knn_cross(int b, int c, int nq, int n, int k, const float *q, const float *x, int64_t *indices, float *dist,
+                             pcc_stream_t stream) {
+    pcc::clear_error();
+    if (b < 0 || c < 1 || nq < 0 || n < 0 || k < 1) return pcc::invalid("knn_cross: bad size");
+    if (b == 0 || nq == 0) return PCC_OK;
+    if (k > n) return pcc::invalid("knn_cross: k exceeds the number of candidates (torch.topk raises too)");
+    if (k > 128) return pcc::invalid("knn_cross: k > 128 is not supported");
+    if (b > 65535) return pcc::invalid("knn_cross: batch too large");
+    if ((long long)b * nq > 0x7fffffffLL) return pcc::invalid("knn_cross: too many queries (b * nq >= 2^31)");
+    if (c >= 4 && n > 65535 * kDT) return pcc::invalid("knn_cross: too many candidates for c >= 4 (n > 65535 * 128)");
+    if (!q || !x || !indices) return pcc::invalid("knn_cross: null pointer");
+    return wide_search(b, c, nq, n, k, q, x, indices, dist, true, static_cast<hipStream_t>(stream));
+}

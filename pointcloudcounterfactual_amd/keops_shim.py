@@ -7,11 +7,12 @@ the reference, all on the lazy matrix ``D[b,i,j] = ((x_i - y_j) ** 2).sum(-1)`` 
 * ``D.argmin(axis=1)`` / ``D.argmin(axis=2)``  -- ``pykeops_chamfer`` (``src/train/metrics_and_losses.py:32-36``)
   and ``VectorQuantizer.quantize`` (``src/module/quantize.py:26-28``);
 * ``D.argKmin(k, dim=2)`` on a cloud against itself -- ``pykeops_knn`` (``neighbour_ops.py:77-82``);
+  between two different clouds (either axis) and ``D.Kmin`` are supported beyond what the reference uses;
 * ``D.sum(1)`` (differentiable)                  -- ``quantize.py:31``.
 
 ``LazyTensor`` below accepts exactly that expression shape -- ``LazyTensor(x[:, :, None, :])``,
 ``LazyTensor(y[:, None, :, :])``, ``-``, ``** 2``, ``.sum(-1)`` -- and maps the reductions onto
-``pcc_nndistance`` (3-D clouds, both argmins from one launch), ``pcc_knn``, ``pcc_pair_argmin`` and
+``pcc_nndistance`` (3-D clouds, both argmins from one launch), ``pcc_knn``, ``pcc_knn_cross``, ``pcc_pair_argmin`` and
 ``pcc_pair_sqdist_sum``.  Anything else raises ``NotImplementedError`` naming what is missing; nothing falls back to
 dense torch math.  Registered as the drop-in packages ``pykeops`` / ``pykeops.torch`` at the repo root, so the
 reference's ``src/utils/neighbour_ops.py`` imports it unchanged.  No PyKeOps output exists to compare against
@@ -181,19 +182,35 @@ class SquareDistance:
             return (d1 if ax == 2 else d2).unsqueeze(-1)
         return self._general(ax)[1].unsqueeze(-1)
 
-    def argKmin(self, K: int, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
-        """``[B,N,K]`` int64 nearest neighbours, ascending; implemented for a cloud against itself
-        (``pykeops_knn``, neighbour_ops.py:77-82), any feature width, ``K <= min(N, 128)``."""
-        ax = self._axis(axis, dim)
-        same = (self.rows.data_ptr() == self.cols.data_ptr() and self.rows.shape == self.cols.shape
+    def _is_self(self) -> bool:
+        return (self.rows.data_ptr() == self.cols.data_ptr() and self.rows.shape == self.cols.shape
                 and self.rows.stride() == self.cols.stride())
-        if not same:
-            raise NotImplementedError('LazyTensor shim: argKmin between two different clouds is not used by the reference')
-        del ax  # D is symmetric
+
+    def _cross(self, K: int, ax: int, return_distance: bool) -> Any:
+        """K nearest columns of every row (axis=2) or K nearest rows of every column (axis=1)."""
+        from pointcloudcounterfactual_amd.neighbour_ops import hip_knn_cross
+
+        rows, cols = self._prepared()
+        q, x = (rows, cols) if ax == 2 else (cols, rows)
+        return hip_knn_cross(q.detach().transpose(1, 2).contiguous(), x.detach().transpose(1, 2).contiguous(), int(K),
+                             return_distance)
+
+    def argKmin(self, K: int, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
+        """Int64 indices of the K nearest partners, ascending, ties by ascending index: ``[B,N,K]`` (axis=2: of every
+        row among the columns) or ``[B,M,K]`` (axis=1: of every column among the rows); any feature width,
+        ``K <= min(partners, 128)``.  A cloud against itself (``pykeops_knn``, neighbour_ops.py:77-82) is ``hip_knn``."""
+        ax = self._axis(axis, dim)
+        if not self._is_self():
+            return self._cross(K, ax, False)
         from pointcloudcounterfactual_amd.neighbour_ops import hip_knn
 
-        rows, _ = self._prepared()
+        rows, _ = self._prepared()  # (D is symmetric: either axis)
         return hip_knn(rows.detach().transpose(1, 2).contiguous(), int(K))
+
+    def Kmin(self, K: int, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
+        """The K smallest squared distances, ascending, ``[B,N,K]`` (axis=2) or ``[B,M,K]`` (axis=1); a constant of
+        the graph, like ``min``."""
+        return self._cross(K, self._axis(axis, dim), True)[1]
 
     def sum(self, axis: int | None = None, dim: int | None = None) -> torch.Tensor:
         """``sum_i D`` -> ``[B,M,1]`` (axis=1) or ``sum_j D`` -> ``[B,N,1]`` (axis=2); differentiable."""

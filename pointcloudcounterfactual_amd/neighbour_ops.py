@@ -108,6 +108,50 @@ def knn(x: torch.Tensor, k: int) -> torch.Tensor:
     return torch_knn(x, k)
 
 
+# ---- kNN between two clouds -------------------------------------------------------------------------------------
+
+
+def cross_square_distance(q: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """Expanded-form distances ``[B,Nq,N]`` of the queries ``q[B,C,Nq]`` to the candidates ``x[B,C,N]``:
+    ``self_square_distance`` written for two clouds; CPU path of ``knn_cross``."""
+    dist = torch.tensor(-2) * torch.matmul(q.transpose(-1, -2), x)
+    dist += torch.sum(x**2, -2, keepdim=True)
+    dist += torch.sum(q**2, -2, keepdim=True).transpose(-1, -2)
+    return dist
+
+
+def torch_knn_cross(q: torch.Tensor, x: torch.Tensor, k: int, return_distance: bool = False) -> Any:
+    """``torch_knn`` for two clouds: ``topk`` of the expanded-form distances."""
+    dist, idx = cross_square_distance(q, x).topk(k=k, largest=False)
+    return (idx, dist) if return_distance else idx
+
+
+def hip_knn_cross(q: torch.Tensor, x: torch.Tensor, k: int, return_distance: bool = False) -> Any:
+    """For every query of ``q[B,C,Nq]`` its ``k`` nearest candidates of ``x[B,C,N]``: ``indices[B,Nq,k]`` int64 into
+    ``x``, ascending distance, ties by ascending index; with ``return_distance`` also their squared distances
+    ``[B,Nq,k]`` float32 (``pcc_knn_cross``, include/pcc_neighbour.h).  Any channel count C >= 1, ``1 <= k <= min(N, 128)``;
+    ``hip_knn_cross(x, x, k)`` is ``hip_knn(x, k)``.  The inputs are detached; the outputs are constants of the graph."""
+    if q.dim() != 3 or x.dim() != 3 or q.shape[:2] != x.shape[:2]:
+        raise ValueError(f'knn_cross: expected q[B,C,Nq] and x[B,C,N], got {tuple(q.shape)} and {tuple(x.shape)}')
+    q, x = q.detach().contiguous(), x.detach().contiguous()
+    b, c, nq = q.shape
+    n = x.shape[2]
+    dev = q.device
+    qp, xp = ptr(q, 'q', F32, dev), ptr(x, 'x', F32, dev)  # (checked before anything is allocated on the device)
+    out = torch.empty((b, nq, k), dtype=torch.int64, device=dev)
+    dist = torch.empty((b, nq, k), dtype=torch.float32, device=dev) if return_distance else None
+    call(_L.pcc_knn_cross, 'knn_cross', dev, b, c, nq, n, k, qp, xp, ptr(out, 'indices', I64, dev), ptr(dist, 'dist', F32, dev))
+    return (out, dist) if return_distance else out
+
+
+def knn_cross(q: torch.Tensor, x: torch.Tensor, k: int, return_distance: bool = False) -> Any:
+    """k nearest candidates of ``x[B,C,N]`` for every query of ``q[B,C,Nq]`` (``knn`` for two clouds, same device
+    dispatch): the HIP search on the accelerator, the torch formula for CPU tensors."""
+    if q.device.type == 'cuda' or x.device.type == 'cuda':
+        return hip_knn_cross(q, x, k, return_distance)
+    return torch_knn_cross(q, x, k, return_distance)
+
+
 # ---- gather / edge features / max over k -------------------------------------------------------------------------
 
 
