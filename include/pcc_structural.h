@@ -107,6 +107,27 @@ int pcc_chamfer_emd_grad(int b, int n, const float *xyz1, int m, const float *xy
                          const float *emd_grad2, const float *grad_emd, int grad_emd_stride, float *grad_xyz1,
                          float *grad_xyz2, pcc_stream_t stream);
 
+/* ---- all-pairs Chamfer distances between two banks of clouds (extension) -------------------------------
+ * What scoring a generated SET needs (minimum matching distance, coverage, 1-NN accuracy): every cloud of one bank
+ * against every cloud of the other, where the entry points above pair sample b with sample b.
+ *   a[s,n,3], bank[r,m,3] -> d_ab[s,r] = mean_p min_q |a_i,p - bank_j,q|^2, d_ba[s,r] = mean_q min_p (same pairs);
+ *   mean != 0: divide by n / m; mean == 0: plain sums.  Either output may be NULL (both: nothing is enqueued).
+ * Distances: every point-pair distance is fmaf(dz,dz, fmaf(dx,dx, dy*dy)) on differences, the expression of
+ *   pcc_nndistance, so each minimum is bit-equal to pcc_nndistance's result / result2 for that pair of clouds.
+ * Reduction: an entry is a fixed-order float32 sum of those minima (no float atomics): it depends on a_i, bank_j, n, m
+ *   and `mean` only -- not on s, r, the position of the clouds in their banks or the launch geometry -- and is
+ *   bit-reproducible from run to run.
+ * Self mode: a == bank (the same pointer) with s == r and n == m evaluates i <= j only and mirrors the results,
+ *   d_ab[j,i] = d_ba[i,j]; the diagonal is exactly 0; the output equals, bit for bit, that of the general mode on
+ *   (a, a copy of a).  Exception: clouds of more than 2048 points (n > 2048) are evaluated for all s * s pairs, the
+ *   diagonal included, one direction per pair (the other is its mirror) -- no work is saved there; same bits.
+ * Sizes: any n, m >= 1 (up to 2^30); s == 0 or r == 0 enqueues nothing and returns PCC_OK; negative sizes, an empty
+ *   cloud or a null input return PCC_EINVAL.  Offsets are 64-bit.  No synchronisation, no allocation.
+ * Non-finite coordinates: specified for finite coordinates; a cloud holding a NaN or an infinite coordinate gives NaN in
+ *   every entry it takes part in (its row of both outputs for a cloud of a, its column for a cloud of bank). */
+int pcc_chamfer_matrix(int s, int n, const float *a, int r, int m, const float *bank, int mean, float *d_ab,
+                       float *d_ba, pcc_stream_t stream);
+
 /* ---- approximate EMD ---------------------------------------------------------------------------
  * Replaces `approxmatch` (reference approxmatch.cu:299-307; declared structural_loss.cpp:10).
  *   xyz1[b,n,3], xyz2[b,m,3] -> match[b,m,n] (query-major), temp[b,2(n+m)] =

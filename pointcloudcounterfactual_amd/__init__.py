@@ -4,7 +4,7 @@ Importing the package loads ``lib/libpcc_structural.so`` (hand-written HIP for g
 ``ImportError`` if the library has not been built -- there is no CPU / PyTorch fallback.
 """
 
-from pointcloudcounterfactual_amd import _lib, backend  # noqa: F401
+from pointcloudcounterfactual_amd import _lib, backend, set_metrics  # noqa: F401
 from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     MatchCostFunction,
     NNDistanceFunction,
@@ -16,4 +16,4 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
 )
 
 __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer', 'MatchCostFunction', 'NNDistanceFunction',
-           'backend']
+           'backend', 'set_metrics']
