@@ -18,12 +18,10 @@
 //                                                | registers, summing them in the reference's order
 //   exp via __expf(level*d2)                     | v_exp_f32((level*log2e)*d2): level is a power of 4, so
 //                                                | the single rounded product is the same real number
-//   matchcost / grad re-read match 3x            | materialising entry points: cost accumulated by the pass that
-//                                                | writes match, both gradients from ONE read; the Python-level
-//                                                | match_cost never stores match at all (am_pair_kernel: cost and
-//                                                | gradients straight from registers, pcc_match_cost)
+//   matchcost re-reads match                     | pcc_approxmatch_cost: cost accumulated by the pass that writes match
+//                                                | (stored match: matchcost.hip; never stored: am_pair.hip)
 //   every pass evaluates all n*m pairs           | only terms that are not EXACTLY zero in float32: both clouds are
-//                                                | Hilbert-sorted once per call (register bitonic sort); at the
+//                                                | Hilbert-sorted once per call (cloud_sort.hip); at the
 //                                                | fine levels (64-owner group, 16-candidate block) pairs whose box
 //                                                | distance makes every exp2(level*d2) underflow are skipped
 //                                                | (V_CULL), and points whose capacity is used up drop out as
@@ -31,12 +29,10 @@
 //   one stream, one block per sample             | a large batch runs as two half-batch lanes on two streams so
 //                                                | that the dependent launch chains fill each other's bubbles
 //
-// Rooflines: the 19 phase launches, am_pair_kernel and the materialise pass are f32-VALU /
-// transcendental bound; matchcost and the fused gradient kernel of the materialising path are HBM bound
-// (one read of match each).
-#include "pcc_common.hpp"
+// Rooflines: the 19 phase launches and the materialise pass are f32-VALU / transcendental bound.
+#include "approxmatch.hpp"
 #include "pcc_test_hooks.h"
-#include "wave_sort.hpp"
+#include "wave_ops.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -46,27 +42,7 @@
 namespace {
 
 using pcc::sq3;
-
-typedef float v4f __attribute__((ext_vector_type(4)));  // for __builtin_nontemporal_load/store
-
-constexpr int kLevels = 9;       // j = 7 .. -1, level = -4^j            (approxmatch.cu:24-25)
-constexpr float kLog2e = 1.44269504088896340736f;
-
-struct LevelConsts {
-    float c[kLevels];            // level_j * log2(e), exact scalings of fl(log2 e)
-};
-
-__host__ LevelConsts make_levels() {
-    LevelConsts lc;
-    float level = -16384.0f;     // -4^7
-    for (int i = 0; i < kLevels; i++) {
-        lc.c[i] = level * kLog2e;
-        level *= 0.25f;
-    }
-    return lc;
-}
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+using pcc::WsView;
 
 // ---------------------------------------------------------------------------------------------------
 // Phase kernels: for every owner point o, S_c(o) = sum over candidates q of exp2(c_c * |o-q|^2) * w_c[q].
@@ -94,11 +70,6 @@ __device__ __forceinline__ PassB pass_b(float remR, float sum) {
 }
 //   pass C: remainL = max(0, remainL - sum_l e * ratioL[k] * ratioR[l])
 __device__ __forceinline__ float pass_c_left(float remL, float ratioL, float sum) { return __builtin_fmaxf(0.0f, remL - ratioL * sum); }
-
-constexpr int kBox = 16;          // points per bounding-box block (sorted order)
-constexpr int kLiveRow = 16;      // ints per sample in the live-owner counters (one per level, padded)
-constexpr int kInfSlot = 13;      // live-counter row, slots 13 / 14: set1 / set2 of the sample holds an infinite coordinate
-constexpr float kZeroExp = 151.f; // exp2(x) == 0 exactly for x <= -150 (below the smallest f32 subnormal)
 
 struct PhaseArgs {
     int n_own, n_cand, tiles, batch;   // tiles = ceil(n_own / (64 R))
@@ -164,11 +135,6 @@ struct Sched {
 };
 
 inline int sched_phases() { return 2 * kLevels + 1; }
-
-inline int mask_words(int m4) { return (m4 + 31) / 32; }
-
-// squared radius beyond which every exp2(c * d2) of level constant c is exactly 0
-inline float zero_cut2(const LevelConsts &lc, int i) { return kZeroExp / -lc.c[i]; }
 
 inline PhaseArgs build_phase(const Sched &sc, int p, int *mode_out, int *var_out) {
     const long long nm4 = (long long)sc.n4 + sc.m4;
@@ -553,7 +519,6 @@ __device__ __forceinline__ void am_phase_body(const PhaseArgs &a, int smp, int t
     }
 }
 
-
 template <int MODE, int R, int S, int CH, int VAR, int G = 1>
 __global__ __launch_bounds__(64 * S) void am_phase_kernel(PhaseArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[PhaseLds<(MODE == PH_CA ? 2 : 1), R, S, CH>::floats];
@@ -600,17 +565,6 @@ constexpr int kFineS = 8;                // waves per workgroup
 constexpr int kFineOG = 16;              // owners per culling group (== kBox: the sort's 16-point boxes serve both sides)
 constexpr int kFineGroups = 64 / kFineOG;
 constexpr int kFineQ = 4;                // owners per lane
-
-// Sum over the 16 lanes of a DPP row, in every lane of the row: pairs, quads, half rows, rows -- the tree of the xor
-// butterfly (a + b and b + a are the same float), with cross-lane VALU operands instead of four trips through the LDS
-// crossbar (ds_bpermute) per value.
-__device__ __forceinline__ float row_sum16(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));  // row_mirror
-    return v;
-}
 
 // The steps of a fine-level pass, one copy for am_fine_kernel (one launch per pass) and am_fine_persist_kernel (levels
 // 0-2 in one launch).  The two kernels keep their own LDS layouts and hand in the row base pointers.  Thread
@@ -695,10 +649,11 @@ __device__ __forceinline__ void fine_walk(const FineRows &rows, const unsigned c
 // lane ends with the same sum); lane cl == 0 of each quad hands the four sums to red[exponential][cs][group-local owner]
 template <int NW>
 __device__ __forceinline__ void fine_reduce(float (&s0)[kFineQ], float (&s1)[kFineQ], float (*red)[2][64], int cs, int cl, int og, int quad) {
+    const auto add = [](float a, float b) { return a + b; };
 #pragma unroll
     for (int j = 0; j < kFineQ; j++) {
-        s0[j] = row_sum16(s0[j]);
-        if (NW == 2) s1[j] = row_sum16(s1[j]);
+        s0[j] = pcc::row_reduce16(s0[j], add);
+        if (NW == 2) s1[j] = pcc::row_reduce16(s1[j], add);
     }
     if (cl == 0) {
 #pragma unroll
@@ -872,8 +827,6 @@ __global__ __launch_bounds__(64 * kFineS, MODE == PH_CA ? 4 : 8) void am_fine_ke
 // ---------------------------------------------------------------------------------------------------
 constexpr int kFpPasses = 7;   // A0 B0 CA0 B1 CA1 B2 CA2
 constexpr int kFpCH = 2048;    // largest cloud the resident form takes
-constexpr int kBarSlot = 12;   // live-counter row: the sample's barrier counter (cleared by the sort kernel)
-constexpr int kErrSlot = 15;   // live-counter row: the sample's resident passes did not complete
 
 struct FinePersistArgs {
     int n, m, n4, m4, nb1, nb2, tiles;
@@ -1042,513 +995,6 @@ __global__ __launch_bounds__(64 * kFineS) void am_fine_persist_kernel(FinePersis
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Nearest neighbours on the sorted clouds (the Chamfer half of the reference's ChamferEMD loss, nndistance.cu:2-128, when
-// it is computed in the same call as the approximate EMD: pcc_chamfer_emd).  The exhaustive scan of nn_fwd_kernel
-// evaluates every pair; here the Hilbert-sorted points, the 16-point boxes and the permutations of THIS call's sort are
-// reused, and a group of 16 consecutive sorted queries only visits the candidate blocks that can still hold a nearest
-// neighbour:
-//   1. the candidate blocks of a window are ordered by the distance between their box and the group's box (a lower
-//      bound of every distance between the two boxes) and visited nearest first;
-//   2. the group's radius is the largest of its queries' best distances so far; the first block whose box is farther
-//      than the radius ends the walk (everything behind it is farther still): exact, nothing that could win -- or tie
-//      with a lower index -- is skipped.  On the bench clouds a group visits 11 of 128 blocks on average (43 at most);
-//   3. ties go to the lowest ORIGINAL candidate index (the reference's rule; the sorted order is not the original one):
-//      the best so far is one 64-bit key (distance bits : original index).  Distances are the oracle's fmaf chain:
-//      indices and distances carry the bits of nn_fwd_kernel / the oracle (tests/test_gpu_structural.py).
-// Measured: 42 us per half-batch launch at B=32, N=2048 -- on a par with the exhaustive kernel (the 16 x 16 tile steps cost
-// ~100 instructions each, 4x the exhaustive kernel's cost per pair, on 9 % of the pairs); what the fused call saves is
-// the separate loss-reduction launch (it rides in the finish launch) and the second read of the clouds.
-// ---------------------------------------------------------------------------------------------------
-struct NNSortedArgs {
-    int n_q, n_c, q_n4, c_n4, q_nb, c_nb, groups, batch;
-    const float *q_soa;            // [b][3][n4]
-    const float4 *c_aos;           // [b][n_c] (x, y, z, original index) per sorted candidate
-    const float *q_box, *c_box;    // [b][nb][8]
-    const int *q_perm;             // [b][n] sorted position -> original index
-    float *out_d;                  // [b][n_q] in the caller's query order
-    int *out_i;
-};
-
-// minimum over the 16 lanes of a DPP row, in every lane of the row: four cross-lane VALU operands (xor 1, xor 2, then the
-// two mirror steps) instead of four trips through the LDS crossbar (ds_bpermute)
-__device__ __forceinline__ float row_min16(float v) {
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));   // quad_perm [1,0,3,2]
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));   // quad_perm [2,3,0,1]
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)));  // row_half_mirror
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true)));  // row_mirror
-    return v;
-}
-
-// A WAVE owns one group of 16 consecutive sorted queries and works alone (no LDS, no barrier: thousands of independent
-// waves hide each other's latency): lane = (candidate slot cl of a 16-candidate block, query quad), four queries in
-// registers.  128 candidate blocks per window: every lane tests two of them against the group's box, the survivors are
-// two 64-bit ballots that the wave walks bit by bit; a lane loads ITS candidate of the block straight from the sorted
-// rows (L2-resident), the next block's loads are issued before the current one is consumed.
-constexpr int kNNWaves = 4;  // independent waves per workgroup
-
-__global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a0, NNSortedArgs a1, int waves0) {
-    const int lane = threadIdx.x & 63;
-    int gw = (int)blockIdx.x * kNNWaves + (int)(threadIdx.x >> 6);   // global wave = (direction, sample, group)
-    const bool second = gw >= waves0;
-    const NNSortedArgs &a = second ? a1 : a0;
-    if (second) gw -= waves0;
-    const int smp = gw / a.groups;
-    const int grp = gw - smp * a.groups;
-    if (smp >= a.batch) return;  // (whole wave)
-    const int cl = lane & (kBox - 1), quad = lane / kBox;
-    const float *Q = a.q_soa + (size_t)smp * 3 * a.q_n4;
-    const float4 *C = a.c_aos + (size_t)smp * a.n_c;
-
-    // best so far per query as ONE 64-bit key (distance bits : original candidate index): squared distances are
-    // non-negative floats, which order like unsigned integers, so a single 64-bit compare is the reference's rule
-    // "smaller distance, lowest index on ties"
-    float qx[kFineQ], qy[kFineQ], qz[kFineQ];
-    unsigned long long bk[kFineQ];
-#pragma unroll
-    for (int j = 0; j < kFineQ; j++) {
-        int q = grp * kBox + quad * kFineQ + j;
-        q = q < a.n_q ? q : a.n_q - 1;
-        qx[j] = Q[q];
-        qy[j] = Q[a.q_n4 + q];
-        qz[j] = Q[2 * a.q_n4 + q];
-        bk[j] = pcc::kKeyInf;
-    }
-    const float4 *gb = reinterpret_cast<const float4 *>(a.q_box + ((size_t)smp * a.q_nb + grp) * 8);
-    const float4 glo = gb[0], ghi = gb[1];
-
-    struct Cand {
-        float x, y, z;
-        int o;
-    };
-    auto load_block = [&](int blk) -> Cand {  // this lane's candidate of block `blk` (+inf / INT_MAX beyond the cloud)
-        // unconditional loads of a clamped index (a branch around them would serialise the software pipeline below),
-        // then the select
-        const int ci = blk * kBox + cl;
-        const bool real = ci < a.n_c;
-        const unsigned cc = (unsigned)(real ? ci : a.n_c - 1);
-        const float4 v = C[cc];  // one 16-byte load per lane and block
-        Cand c;
-        c.x = real ? v.x : __builtin_inff();
-        c.y = v.y;
-        c.z = v.z;
-        c.o = real ? __float_as_int(v.w) : 0x7fffffff;
-        return c;
-    };
-    auto scan = [&](const Cand &c) {
-#pragma unroll
-        for (int j = 0; j < kFineQ; j++) {
-            const float d = sq3(c.x - qx[j], c.y - qy[j], c.z - qz[j]);
-            const unsigned long long k = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)c.o;
-            bk[j] = k < bk[j] ? k : bk[j];
-        }
-    };
-    // the group's radius: every query's best so far over its 16 candidate lanes, the largest over the 16 queries
-    auto group_radius = [&]() -> float {
-        float r = 0.f;
-#pragma unroll
-        for (int j = 0; j < kFineQ; j++) {
-            const float m = row_min16(__uint_as_float((unsigned)(bk[j] >> 32)));
-            r = fmaxf(r, grp * kBox + quad * kFineQ + j < a.n_q ? m : 0.f);
-        }
-        // the four rows (query quads) meet through scalar reads
-        const int ri = __float_as_int(r);
-        const float r0 = __int_as_float(__builtin_amdgcn_readlane(ri, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(ri, 16));
-        const float r2 = __int_as_float(__builtin_amdgcn_readlane(ri, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(ri, 48));
-        return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-    };
-
-    float r = __builtin_inff();  // the group's radius: the largest of its queries' best distances so far
-    for (int b0 = 0; b0 < a.c_nb; b0 += 128) {  // windows of 128 candidate blocks (2048 candidates)
-        // every lane: two blocks of the window, keyed by the lower bound of every distance between the group's box and
-        // the block's box (the candidates' own chain); nearest boxes first
-        unsigned key[2];
-        pcc::sort_box_window(key, a.c_box, smp, a.c_nb, b0, glo, ghi, lane, sq3);
-        // walk the window nearest-first; a block farther than the radius ends it (everything behind is farther still):
-        // nothing that could win, or tie with a lower original index, is skipped.  Two blocks are in flight ahead.
-        // (branch-free: a branch around the look-ahead loads makes the compiler drain them before every use)
-        const int nwin = min(128, a.c_nb - b0);
-        // batches of four blocks: their sixteen loads are issued together, each block is consumed as soon as ITS loads
-        // have landed (straight-line code: the compiler counts the outstanding loads exactly), the radius is refreshed
-        // after every batch
-        bool done = false;
-        for (int p = 0; p < nwin && !done; p += 4) {
-            unsigned kk[4];
-            Cand cc[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                kk[u] = pcc::window_key(key, min(p + u, nwin - 1));  // (past the end: the last block again, never consumed)
-                cc[u] = load_block(b0 + (int)(kk[u] & 127u));
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (!done) {
-                    if (p + u >= nwin || __uint_as_float(kk[u] & ~127u) > r) done = true;
-                    else scan(cc[u]);
-                }
-            }
-            r = fminf(r, group_radius());
-        }
-    }
-    // every query: best over its 16 candidate lanes
-#pragma unroll
-    for (int j = 0; j < kFineQ; j++) {
-#pragma unroll
-        for (int off = 1; off < kBox; off <<= 1) {
-            const unsigned long long ok = pcc::shfl_xor_u64(bk[j], off);
-            bk[j] = ok < bk[j] ? ok : bk[j];
-        }
-    }
-    if (cl == 0) {
-#pragma unroll
-        for (int j = 0; j < kFineQ; j++) {
-            const int qs = grp * kBox + quad * kFineQ + j;
-            if (qs < a.n_q) {
-                const int orig = a.q_perm[(size_t)smp * a.n_q + qs];
-                a.out_d[(size_t)smp * a.n_q + orig] = __uint_as_float((unsigned)(bk[j] >> 32));
-                a.out_i[(size_t)smp * a.n_q + orig] = (int)(bk[j] & 0xffffffffu);
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Spatial sort: one workgroup per (sample, cloud) orders the points along a 30-bit Hilbert curve with a
-// bitonic sort of (code << 32 | index) keys in LDS and writes the sorted SoA coordinates, the inverse
-// permutation (rank) and one bounding box per 16 consecutive sorted points.  Clouds too large for the LDS
-// sort (> 16384 points) keep their original order: culling then simply finds little to skip.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned part1by2(unsigned v) {
-    v &= 0x3ff;
-    v = (v | (v << 16)) & 0x030000ff;
-    v = (v | (v << 8)) & 0x0300f00f;
-    v = (v | (v << 4)) & 0x030c30c3;
-    v = (v | (v << 2)) & 0x09249249;
-    return v;
-}
-
-// 30-bit Hilbert index of a 10-bit lattice point (Skilling's axes-to-transpose, then bit interleave).
-// Unlike the Morton order, every contiguous run of the Hilbert order is spatially compact, so all owner
-// tiles get similar, small bounding boxes (a Morton run that straddles an octant boundary spans the cloud).
-__device__ __forceinline__ unsigned hilbert3(unsigned x0, unsigned x1, unsigned x2) {
-    unsigned X[3] = {x0, x1, x2};
-    const unsigned M = 1u << 9;
-    for (unsigned Q = M; Q > 1; Q >>= 1) {
-        const unsigned P = Q - 1;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (X[i] & Q) {
-                X[0] ^= P;
-            } else {
-                const unsigned t = (X[0] ^ X[i]) & P;
-                X[0] ^= t;
-                X[i] ^= t;
-            }
-        }
-    }
-    X[1] ^= X[0];
-    X[2] ^= X[1];
-    unsigned t = 0;
-    for (unsigned Q = M; Q > 1; Q >>= 1)
-        if (X[2] & Q) t ^= Q - 1;
-    X[0] ^= t;
-    X[1] ^= t;
-    X[2] ^= t;
-    return (part1by2(X[0]) << 2) | (part1by2(X[1]) << 1) | part1by2(X[2]);
-}
-
-struct SortArgs {  // one entry per cloud; blockIdx.y selects it
-    int n[2], n4[2], nb[2], npad[2];
-    const float *xyz[2];
-    // input layout: coordinate c of point i of sample s sits at xyz[s*sstride + i*pstride + c*cstride]; channels
-    // >= nch read as 0 (the k-NN graph sorts channels-major clouds of 1..3 channels with the same kernel)
-    long long sstride[2], pstride[2], cstride[2];
-    int nch[2];
-    float *soa[2];
-    int *rank[2];
-    int *perm[2];      // sorted position -> original index (inverse of rank)
-    float4 *aos[2];    // optional [b][n]: (x, y, z, original index as bits) per sorted point (nn_sorted_kernel)
-    float *box[2];
-    // zero-fill riding along (replaces two memset launches): the two workgroups of a sample clear one region each
-    float *zero[2];
-    long long zero_stride[2], zero_count[2];  // per-sample stride and length in floats (multiples of 4)
-    int *live_cnt;                            // [b][kLiveRow] live-owner counters of the passes B, cleared here
-    unsigned *live_mask;                      // [b][kLevels][mask_words] live bits of set2: rows 4.. are preset to ones here
-    int mask_words;
-};
-
-// Bitonic sort of NPAD = kSortT*SLOTS 32-bit keys held in registers (element i = tid*SLOTS + slot) by an 8-wave
-// workgroup: strides < SLOTS are exchanges between a thread's registers, strides < 64*SLOTS between lanes (DPP where the
-// partner is a quad / row permutation), only the three longest strides go through LDS.  Fully unrolled so that every
-// register index is static.  A key is (truncated Hilbert code << idx_bits) | point index: keys are unique and
-// one v_min_u32 / v_max_u32 pair is a whole compare-exchange.
-constexpr int kSortT = 512;
-
-template <int SLOTS>
-__device__ __forceinline__ void bitonic_sort(unsigned (&key)[SLOTS], unsigned *lds, int tid) {
-    // element tid * SLOTS + s sits in slot s of thread tid (a thread's keys are neighbours): the SHORT strides -- the ones
-    // every merge repeats -- are exchanges between registers, the middle ones between lanes, and only the three longest
-    // strides (6 stages of the 66 at 2048 keys) cross waves through LDS.  (With element tid + 512 s the three strides 64 /
-    // 128 / 256 went through LDS, 12 stages with two barriers each: half of the sort's time, timed inside the kernel.)
-    constexpr int NPAD = kSortT * SLOTS;
-#pragma unroll
-    for (int kk = 2; kk <= NPAD; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            if (j < SLOTS) {
-#pragma unroll
-                for (int s = 0; s < SLOTS; s++) {
-                    const int sp = s ^ j;
-                    if (sp > s) {
-                        const bool asc = ((tid * SLOTS + s) & kk) == 0;
-                        const unsigned mn = min(key[s], key[sp]), mx = max(key[s], key[sp]);
-                        key[s] = asc ? mn : mx;
-                        key[sp] = asc ? mx : mn;
-                    }
-                }
-            } else {
-                const int L = j / SLOTS;  // the partner is slot s of thread tid ^ L
-                if (L >= 64) {
-                    __syncthreads();
-#pragma unroll
-                    for (int s = 0; s < SLOTS; s++) lds[tid + kSortT * s] = key[s];
-                    __syncthreads();
-                }
-#pragma unroll
-                for (int s = 0; s < SLOTS; s++) {
-                    // the partner lane ^ L: one DPP move for L = 1, 2 (quad permutations) and 8 (a rotation by 8 of the row
-                    // of 16 IS lane ^ 8), two rotations and a select for 4; the LDS crossbar (ds_bpermute) for 16 and 32
-                    unsigned other;
-                    if (L >= 64) other = lds[(tid ^ L) + kSortT * s];
-                    else if (L == 1) other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key[s], 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-                    else if (L == 2) other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key[s], 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-                    else if (L == 8) other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key[s], 0x128, 0xf, 0xf, false);  // row_ror:8
-                    else if (L == 4) {
-                        // (row_ror:n hands lane i the value of lane i - n of its row)
-                        const unsigned lo4 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key[s], 0x124, 0xf, 0xf, false);   // from lane - 4
-                        const unsigned hi4 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key[s], 0x12C, 0xf, 0xf, false);   // from lane - 12 = lane + 4
-                        other = (tid & 4) ? lo4 : hi4;
-                    } else other = (unsigned)__shfl_xor((int)key[s], L, 64);
-                    const bool take_min = ((tid & L) == 0) == (((tid * SLOTS + s) & kk) == 0);
-                    key[s] = take_min ? min(key[s], other) : max(key[s], other);
-                }
-            }
-        }
-    }
-}
-
-template <int SLOTS>
-__global__ __launch_bounds__(kSortT) void am_sort_kernel(SortArgs a) {
-    constexpr bool MIRROR = SLOTS <= 8;  // clouds of up to 4096 points keep their coordinates in LDS (48 KB) for the gather
-    __shared__ unsigned lds_keys[kSortT * SLOTS];
-    __shared__ float lds_xyz[MIRROR ? 3 * kSortT * SLOTS : 1];
-    __shared__ float red[6][16];
-    const int which = blockIdx.y;
-    const int n = a.n[which], n4 = a.n4[which], nb = a.nb[which], npad = a.npad[which];
-    const int smp = blockIdx.x, tid = threadIdx.x, T = kSortT;
-    if (a.live_cnt && which == 0 && (threadIdx.x < kInfSlot || threadIdx.x == kErrSlot))  // (kInfSlot.. are set below)
-        a.live_cnt[(size_t)blockIdx.x * kLiveRow + threadIdx.x] = 0;
-    if (a.live_mask && which == 1)  // (rows 4.. of the live masks start as all ones: PhaseArgs::mask_out)
-        for (int i = 4 * a.mask_words + threadIdx.x; i < kLevels * a.mask_words; i += kSortT)
-            a.live_mask[(size_t)blockIdx.x * kLevels * a.mask_words + i] = ~0u;
-    if (a.zero[which]) {  // fire-and-forget stores, hidden under the sort
-        float4 *z = reinterpret_cast<float4 *>(a.zero[which] + (size_t)smp * a.zero_stride[which]);
-        const long long cnt4 = a.zero_count[which] / 4;
-        for (long long i = tid; i < cnt4; i += T) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float *p = a.xyz[which] + (size_t)smp * a.sstride[which];
-    const long long ps = a.pstride[which], cs = a.cstride[which];
-    const int nch = a.nch[which];
-    auto coord = [&](int i, int c) -> float { return c < nch ? p[i * ps + c * cs] : 0.f; };
-    float *so = a.soa[which] ? a.soa[which] + (size_t)smp * 3 * n4 : nullptr;
-    int *rk = a.rank[which] ? a.rank[which] + (size_t)smp * n : nullptr;
-    int *pm = a.perm[which] + (size_t)smp * n;
-    float4 *ao = a.aos[which] ? a.aos[which] + (size_t)smp * n : nullptr;
-    float *bx = a.box[which] + (size_t)smp * nb * 8;
-    int idx_bits = 10;
-    while ((1 << idx_bits) < npad) idx_bits++;  // npad >= 1024
-    const unsigned idx_mask = (1u << idx_bits) - 1;
-    if (npad) {
-        const int code_shift = 30 - 3 * ((32 - idx_bits) / 3);  // keep the leading 3*floor((32-idx_bits)/3) code bits
-        // The thread's points: every load issued before anything consumes one (ONE round trip; read in a loop with the
-        // min/max next to each load, and again for the keys, the kernel waited out eight), kept in registers for the
-        // bounding box and the keys, and mirrored in LDS where the cloud fits, for the gather behind the sort.
-        // (up to 16 slots -- 8192 points -- stay in registers; larger clouds read their points twice, as they come)
-        constexpr bool KEEP = SLOTS <= 16;
-        constexpr int BATCH = SLOTS < 8 ? SLOTS : 8;
-        constexpr int NKEEP = KEEP ? SLOTS : BATCH;
-        float px[NKEEP], py[NKEEP], pz[NKEEP];
-        const int c1 = min(1, nch - 1), c2 = min(2, nch - 1);
-        const int k1 = -(int)(nch > 1), k2 = -(int)(nch > 2);  // channels >= nch read as 0
-        auto load_batch = [&](int s0, int r0) {  // slots s0 .. s0 + BATCH - 1 into registers r0 ..
-#pragma unroll
-            for (int u = 0; u < BATCH; u++) {
-                const long long i = min(tid * SLOTS + (s0 + u), n - 1);
-                px[r0 + u] = p[i * ps];
-                py[r0 + u] = p[i * ps + c1 * cs];
-                pz[r0 + u] = p[i * ps + c2 * cs];
-            }
-#pragma unroll
-            for (int u = 0; u < BATCH; u++) {
-                py[r0 + u] = __int_as_float(__float_as_int(py[r0 + u]) & k1);
-                pz[r0 + u] = __int_as_float(__float_as_int(pz[r0 + u]) & k2);
-            }
-        };
-        float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-        float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-        if (!KEEP) {
-            for (int i = tid; i < n; i += T)
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float v = coord(i, c);
-                    lo[c] = fminf(lo[c], v);
-                    hi[c] = fmaxf(hi[c], v);
-                }
-        }
-#pragma unroll
-        for (int s0 = 0; s0 < (KEEP ? SLOTS : 0); s0 += BATCH) {
-            const int r0 = s0;
-            load_batch(s0, r0);
-#pragma unroll
-            for (int u = 0; u < BATCH; u++) {  // (a slot past the cloud repeats the last point: no effect on the box)
-                lo[0] = fminf(lo[0], px[r0 + u]); hi[0] = fmaxf(hi[0], px[r0 + u]);
-                lo[1] = fminf(lo[1], py[r0 + u]); hi[1] = fmaxf(hi[1], py[r0 + u]);
-                lo[2] = fminf(lo[2], pz[r0 + u]); hi[2] = fmaxf(hi[2], pz[r0 + u]);
-                if (MIRROR) {
-                    lds_xyz[tid * SLOTS + (s0 + u)] = px[r0 + u];
-                    lds_xyz[kSortT * SLOTS + tid * SLOTS + (s0 + u)] = py[r0 + u];
-                    lds_xyz[2 * kSortT * SLOTS + tid * SLOTS + (s0 + u)] = pz[r0 + u];
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            // (inside the rows of 16 lanes by DPP rotations, across the four rows through the LDS crossbar)
-#define PCC_ROR(v, n) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n), 0xf, 0xf, false))
-            lo[c] = fminf(lo[c], PCC_ROR(lo[c], 8)); hi[c] = fmaxf(hi[c], PCC_ROR(hi[c], 8));
-            lo[c] = fminf(lo[c], PCC_ROR(lo[c], 4)); hi[c] = fmaxf(hi[c], PCC_ROR(hi[c], 4));
-            lo[c] = fminf(lo[c], PCC_ROR(lo[c], 2)); hi[c] = fmaxf(hi[c], PCC_ROR(hi[c], 2));
-            lo[c] = fminf(lo[c], PCC_ROR(lo[c], 1)); hi[c] = fmaxf(hi[c], PCC_ROR(hi[c], 1));
-#undef PCC_ROR
-#pragma unroll
-            for (int off = 16; off < 64; off <<= 1) {
-                lo[c] = fminf(lo[c], __shfl_xor(lo[c], off, 64));
-                hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], off, 64));
-            }
-            if ((tid & 63) == 0) {
-                red[c][tid >> 6] = lo[c];
-                red[3 + c][tid >> 6] = hi[c];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            float l = red[c][0], h = red[3 + c][0];
-            for (int i = 1; i < kSortT / 64; i++) {
-                l = fminf(l, red[c][i]);
-                h = fmaxf(h, red[3 + c][i]);
-            }
-            lo[c] = l;
-            hi[c] = h > l ? 1023.f / (h - l) : 0.f;  // scale
-        }
-        unsigned key[SLOTS];
-        if (!KEEP) {
-#pragma unroll
-            for (int s2 = 0; s2 < SLOTS; s2++) {
-                const int i = tid * SLOTS + s2;
-                key[s2] = ~0u;
-                if (i < n) {
-                    const unsigned qx = (unsigned)fminf(fmaxf((coord(i, 0) - lo[0]) * hi[0], 0.f), 1023.f);
-                    const unsigned qy = (unsigned)fminf(fmaxf((coord(i, 1) - lo[1]) * hi[1], 0.f), 1023.f);
-                    const unsigned qz = (unsigned)fminf(fmaxf((coord(i, 2) - lo[2]) * hi[2], 0.f), 1023.f);
-                    key[s2] = ((hilbert3(qx, qy, qz) >> code_shift) << idx_bits) | (unsigned)i;
-                }
-            }
-        }
-#pragma unroll
-        for (int s0 = 0; s0 < (KEEP ? SLOTS : 0); s0 += BATCH) {
-            const int r0 = s0;
-#pragma unroll
-            for (int u = 0; u < BATCH; u++) {
-                const int i = tid * SLOTS + (s0 + u);
-                const unsigned qx = (unsigned)fminf(fmaxf((px[r0 + u] - lo[0]) * hi[0], 0.f), 1023.f);
-                const unsigned qy = (unsigned)fminf(fmaxf((py[r0 + u] - lo[1]) * hi[1], 0.f), 1023.f);
-                const unsigned qz = (unsigned)fminf(fmaxf((pz[r0 + u] - lo[2]) * hi[2], 0.f), 1023.f);
-                const unsigned kv = ((hilbert3(qx, qy, qz) >> code_shift) << idx_bits) | (unsigned)i;
-                key[s0 + u] = i < n ? kv : ~0u;
-            }
-        }
-        bitonic_sort<SLOTS>(key, lds_keys, tid);
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < SLOTS; s++) lds_keys[tid * SLOTS + s] = key[s];
-        __syncthreads();
-    }
-    // sorted SoA rows + inverse permutation; the box of every 16 consecutive sorted points falls out of a
-    // 16-lane min/max butterfly on the coordinates the lanes already hold
-    const int span = ((max(n4, nb * kBox) + 63) / 64) * 64;
-    int has_inf = 0;
-    auto emit = [&](int s) {  // sorted position s: its point, its rows, its box
-        float x = 0.f, y = 0.f, z = 0.f;
-        const bool real = s < n;
-        if (real) {
-            const int orig = npad ? (int)(lds_keys[s] & idx_mask) : s;
-            if (MIRROR && npad) {
-                x = lds_xyz[orig];
-                y = lds_xyz[kSortT * SLOTS + orig];
-                z = lds_xyz[2 * kSortT * SLOTS + orig];
-            } else {
-                x = coord(orig, 0);
-                y = coord(orig, 1);
-                z = coord(orig, 2);
-            }
-            has_inf |= (__builtin_isinf(x) || __builtin_isinf(y) || __builtin_isinf(z)) ? 1 : 0;
-            if (rk) rk[orig] = s;
-            pm[s] = orig;
-            if (ao) ao[s] = make_float4(x, y, z, __int_as_float(orig));
-        }
-        if (so && s < n4) {
-            so[s] = x;
-            so[n4 + s] = y;
-            so[2 * n4 + s] = z;
-        }
-        float l0 = real ? x : __builtin_inff(), l1 = real ? y : __builtin_inff(), l2 = real ? z : __builtin_inff();
-        float h0 = real ? x : -__builtin_inff(), h1 = real ? y : -__builtin_inff(), h2 = real ? z : -__builtin_inff();
-        // (min / max over the 16 lanes of a DPP row, in every lane: four rotations of the row)
-        auto rot = [](float v, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xf, 0xf, false)); };
-        static_assert(kBox == 16, "a box is a DPP row");
-#define PCC_ROW16(op, v)                                                        \
-    v = op(v, rot(v, std::integral_constant<int, 0x128>{}));                    \
-    v = op(v, rot(v, std::integral_constant<int, 0x124>{}));                    \
-    v = op(v, rot(v, std::integral_constant<int, 0x122>{}));                    \
-    v = op(v, rot(v, std::integral_constant<int, 0x121>{}));
-        PCC_ROW16(fminf, l0) PCC_ROW16(fminf, l1) PCC_ROW16(fminf, l2)
-        PCC_ROW16(fmaxf, h0) PCC_ROW16(fmaxf, h1) PCC_ROW16(fmaxf, h2)
-#undef PCC_ROW16
-        const int bb = s / kBox;
-        if ((s & (kBox - 1)) == 0 && bb < nb) {
-            float4 *dst = reinterpret_cast<float4 *>(bx + (size_t)bb * 8);
-            dst[0] = make_float4(l0, l1, l2, 0.f);
-            dst[1] = make_float4(h0, h1, h2, 0.f);
-        }
-    };
-    if (npad && SLOTS <= 8) {  // (unrolled: the LDS reads of all of a thread's positions are in flight together)
-#pragma unroll
-        for (int k2 = 0; k2 < SLOTS; k2++)
-            if (tid + k2 * T < span) emit(tid + k2 * T);  // (span is a multiple of 64: whole waves take the branch)
-    } else {
-        for (int s = tid; s < span; s += T) emit(s);
-    }
-    // An infinite coordinate makes every pair of its point exp(-inf) = 0 -- skipped here as an exact zero -- while the
-    // reference goes on to multiply that 0 by sqrt(inf): its cost and gradients of the sample are NaN (approxmatch.cu:207,
-    // 247-248).  The sample is flagged and the finish kernel reports NaN.  (NaN coordinates need no flag: they reach the
-    // sums through the distances, as in the reference.)
-    if (a.live_cnt) {
-        const int any_inf = __syncthreads_or(has_inf);
-        if (tid == 0) a.live_cnt[(size_t)blockIdx.x * kLiveRow + kInfSlot + which] = any_inf ? 1 : 0;
-    }
-}
-
 // The phases run in Hilbert-sorted index space; this puts the nine (ratioL | ratioR) level vectors back into
 // the caller's point order for the materialise pass (contiguous loads there) and fills
 // temp = remainL | remainR | ratioL | ratioR of the last level (approxmatch.cu:4).  A sample whose resident fine-level
@@ -1679,597 +1125,13 @@ __global__ __launch_bounds__(256) void am_materialise_kernel(int n, int m, const
         }
     }
     if (COST) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) csum += __shfl_down(csum, off, 64);
+        csum = pcc::wave_sum_down(csum);
         if (lane == 0) lds_red[w] = csum;
         __syncthreads();
         if (tid == 0)
             cost_part[(size_t)smp * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x] =
                 ((lds_red[0] + lds_red[1]) + lds_red[2]) + lds_red[3];
     }
-}
-
-// out[b] = sum_p part[b][p] in index order (deterministic second stage of every cost reduction).
-__global__ __launch_bounds__(256) void reduce_rows_kernel(int parts, const float *__restrict__ part,
-                                                           float *__restrict__ out) {
-    __shared__ float red[256];
-    const int smp = blockIdx.x, tid = threadIdx.x;
-    float s = 0.f;
-    for (int i = tid; i < parts; i += 256) s += part[(size_t)smp * parts + i];
-    red[tid] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) red[tid] += red[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) out[smp] = red[0];
-}
-
-// ---------------------------------------------------------------------------------------------------
-// matchcost: "row" kernel.  A workgroup takes RT rows (query points l of set2) of one sample; set1 is
-// staged SoA in LDS chunk by chunk; each wave streams whole rows of match with coalesced float4 loads
-// (1 KiB per wave-instruction).  Cost partial = sum match * sqrt(d2)   (approxmatch.cu:200-209)
-// ---------------------------------------------------------------------------------------------------
-constexpr int kRowRT = 32;  // rows per workgroup -> 8 per wave
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void am_row_kernel(int n, int m, const float *__restrict__ xyz1,
-                                                      const float *__restrict__ xyz2,
-                                                      const float *__restrict__ match, float *__restrict__ out) {
-    constexpr int RPW = kRowRT / 4, CH = 2048;  // (set1 points staged per chunk)
-    __shared__ __attribute__((aligned(16))) float lds_p[3 * CH];
-    __shared__ float lds_red[4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int smp = blockIdx.y;
-    const int r0 = blockIdx.x * kRowRT;
-    const float *p1 = xyz1 + (size_t)smp * n * 3;
-    const float *p2 = xyz2 + (size_t)smp * m * 3;
-    const float4 *X4 = reinterpret_cast<const float4 *>(lds_p);
-    const float4 *Y4 = X4 + CH / 4;
-    const float4 *Z4 = Y4 + CH / 4;
-
-    float csum = 0.f;
-
-    for (int q0 = 0; q0 < n; q0 += CH) {
-        const int cnt = min(CH, n - q0);
-        if (q0) __syncthreads();
-        for (int i = tid; i < cnt * 3; i += 256) {
-            const float v = p1[(size_t)q0 * 3 + i];
-            const int p = i / 3;
-            lds_p[(i - p * 3) * CH + p] = v;
-        }
-        for (int i = cnt + tid; i < ((cnt + 3) & ~3); i += 256) lds_p[i] = lds_p[CH + i] = lds_p[2 * CH + i] = 0.f;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < RPW; i++) {
-            const int row = r0 + w + 4 * i;
-            const bool live = row < m;  // wave-uniform
-            const int rowc = live ? row : m - 1;
-            const float x2 = p2[rowc * 3 + 0], y2 = p2[rowc * 3 + 1], z2 = p2[rowc * 3 + 2];
-            const float *mrow = match + ((size_t)smp * m + rowc) * n + q0;
-            for (int k = lane * 4; live && k < cnt; k += 256) {
-                float mv[4];
-                if (VEC && k + 3 < cnt) {
-                    const v4f t4 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(mrow + k));
-                    const float4 t = make_float4(t4.x, t4.y, t4.z, t4.w);
-                    mv[0] = t.x; mv[1] = t.y; mv[2] = t.z; mv[3] = t.w;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; q++) mv[q] = (k + q < cnt) ? mrow[k + q] : 0.f;
-                }
-                const float4 xs = X4[k >> 2], ys = Y4[k >> 2], zs = Z4[k >> 2];
-                const float px[4] = {xs.x, xs.y, xs.z, xs.w};
-                const float py[4] = {ys.x, ys.y, ys.z, ys.w};
-                const float pz[4] = {zs.x, zs.y, zs.z, zs.w};
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const float dx = x2 - px[q], dy = y2 - py[q], dz = z2 - pz[q];
-                    csum = __builtin_fmaf(mv[q], __builtin_amdgcn_sqrtf(sq3(dx, dy, dz)), csum);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) csum += __shfl_down(csum, off, 64);
-    if (lane == 0) lds_red[w] = csum;
-    __syncthreads();
-    if (tid == 0) out[(size_t)smp * gridDim.x + blockIdx.x] = ((lds_red[0] + lds_red[1]) + lds_red[2]) + lds_red[3];
-}
-
-// ---------------------------------------------------------------------------------------------------
-// matchcostgrad, fused: ONE read of match produces both gradients (the reference reads it twice,
-// approxmatch.cu:319-320).  A workgroup takes RT rows (points k of set2) x a 2048-column slab (points l of set1);
-// a wave streams whole row segments with float4 loads; per element t = d * match * rsqrt(max(|d|^2,1e-20)):
-//   grad1[l] += t   (column sums: 4 columns x 3 components per lane per 256-column step, kept in registers,
-//                    merged over the 4 waves in LDS, written as one partial per row tile)
-//   grad2[k] -= t   (row sums: per-lane partials, wave butterfly at the end of the row segment)
-// Partials are combined in a fixed order by reduce_splits_kernel / the slab loop: deterministic.
-// ---------------------------------------------------------------------------------------------------
-constexpr int kGradRT = 64;     // rows per workgroup (16 per wave)
-constexpr int kGradSlab = 1024;  // columns per slab = 4 steps of 256 (48 column-sum registers per lane; 2048 -> 175 us, 1024 -> 129 us, 512 -> 134 us at B=32,N=2048)
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void am_grad_fused_kernel(int n, int m, int row_tiles,
-                                                             const float *__restrict__ xyz1,
-                                                             const float *__restrict__ xyz2,
-                                                             const float *__restrict__ match,
-                                                             float *__restrict__ part1,  // [b][row_tiles][n][3]
-                                                             float *__restrict__ part2,  // [b][slabs][m][3]
-                                                             const float *__restrict__ scale2)  // applied when part2 IS grad2
-{
-    constexpr int STEPS = kGradSlab / 256;
-    // set1 slab SoA (24 KiB); after the row loop the same bytes carry one wave's column sums at a time to wave 0
-    __shared__ __attribute__((aligned(16))) float lds_p[3 * kGradSlab > STEPS * 12 * 64 ? 3 * kGradSlab : STEPS * 12 * 64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int smp = blockIdx.z, slab = blockIdx.y, rt = blockIdx.x;
-    const int c0 = slab * kGradSlab;
-    const int cnt = min(kGradSlab, n - c0);
-    const float *p1 = xyz1 + ((size_t)smp * n + c0) * 3;
-    const float *p2 = xyz2 + (size_t)smp * m * 3;
-    for (int i = tid; i < cnt * 3; i += 256) {
-        const float v = p1[i];
-        const int p = i / 3;
-        lds_p[(i - p * 3) * kGradSlab + p] = v;
-    }
-    for (int i = cnt + tid; i < kGradSlab; i += 256) lds_p[i] = lds_p[kGradSlab + i] = lds_p[2 * kGradSlab + i] = 0.f;
-    __syncthreads();
-    const float4 *X4 = reinterpret_cast<const float4 *>(lds_p);
-    const float4 *Y4 = X4 + kGradSlab / 4;
-    const float4 *Z4 = Y4 + kGradSlab / 4;
-
-    float g1[STEPS][4][3];
-#pragma unroll
-    for (int st = 0; st < STEPS; st++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) g1[st][q][0] = g1[st][q][1] = g1[st][q][2] = 0.f;
-
-    const int r_begin = rt * kGradRT, r_end = min(r_begin + kGradRT, m);
-    const bool full = VEC && cnt == kGradSlab;  // whole slab, aligned: branch-free body, 8 row loads in flight
-    for (int row = r_begin + w; row < r_end; row += 4) {
-        const float x2 = p2[row * 3 + 0], y2 = p2[row * 3 + 1], z2 = p2[row * 3 + 2];
-        const float *mrow = match + ((size_t)smp * m + row) * n + c0;
-        float rx = 0.f, ry = 0.f, rz = 0.f;
-        float mv[STEPS][4];
-        if (full) {
-#pragma unroll
-            for (int st = 0; st < STEPS; st++) {
-                const v4f t4 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(mrow + st * 256 + lane * 4));
-                const float4 t = make_float4(t4.x, t4.y, t4.z, t4.w);  // read once: non-temporal (128 -> 119 us)
-                mv[st][0] = t.x; mv[st][1] = t.y; mv[st][2] = t.z; mv[st][3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int st = 0; st < STEPS; st++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int k = st * 256 + lane * 4 + q;
-                    mv[st][q] = k < cnt ? mrow[k] : 0.f;  // columns past the slab contribute exactly 0
-                }
-        }
-#pragma unroll
-        for (int st = 0; st < STEPS; st++) {
-            const int k = st * 256 + lane * 4;
-            const float4 xs = X4[k >> 2], ys = Y4[k >> 2], zs = Z4[k >> 2];
-            const float px[4] = {xs.x, xs.y, xs.z, xs.w};
-            const float py[4] = {ys.x, ys.y, ys.z, ys.w};
-            const float pz[4] = {zs.x, zs.y, zs.z, zs.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                // grad1 uses (p1 - p2) (approxmatch.cu:281-284); grad2 the negated vector (:240-246)
-                const float dx = px[q] - x2, dy = py[q] - y2, dz = pz[q] - z2;
-                const float f = mv[st][q] * __builtin_amdgcn_rsqf(__builtin_fmaxf(sq3(dx, dy, dz), 1e-20f));
-                const float tx = dx * f, ty = dy * f, tz = dz * f;
-                g1[st][q][0] += tx;
-                g1[st][q][1] += ty;
-                g1[st][q][2] += tz;
-                rx -= tx;
-                ry -= ty;
-                rz -= tz;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            rx += __shfl_down(rx, off, 64);
-            ry += __shfl_down(ry, off, 64);
-            rz += __shfl_down(rz, off, 64);
-        }
-        if (lane == 0) {
-            float *dst = part2 + (((size_t)smp * gridDim.y + slab) * m + row) * 3;
-            const float sc = scale2 ? scale2[smp] : 1.0f;
-            dst[0] = scale2 ? rx * sc : rx;
-            dst[1] = scale2 ? ry * sc : ry;
-            dst[2] = scale2 ? rz * sc : rz;
-        }
-    }
-    // column partials: waves 1, 2, 3 hand their sums to wave 0 one after the other (fixed order)
-    float *red = lds_p;
-    for (int src = 1; src < 4; src++) {
-        __syncthreads();
-        if (w == src) {
-#pragma unroll
-            for (int st = 0; st < STEPS; st++)
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) red[((st * 4 + q) * 3 + c) * 64 + lane] = g1[st][q][c];
-        }
-        __syncthreads();
-        if (w == 0) {
-#pragma unroll
-            for (int st = 0; st < STEPS; st++)
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) g1[st][q][c] += red[((st * 4 + q) * 3 + c) * 64 + lane];
-        }
-    }
-    if (w == 0) {
-        float *dst = part1 + (((size_t)smp * row_tiles + rt) * n + c0) * 3;
-#pragma unroll
-        for (int st = 0; st < STEPS; st++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int k = st * 256 + lane * 4 + q;
-                if (k < cnt) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) dst[(size_t)k * 3 + c] = g1[st][q][c];
-                }
-            }
-    }
-}
-
-// grad1[b][i] = sum_s part[b][s][i]  (i over n*3), fixed order.
-__global__ __launch_bounds__(256) void reduce_splits_kernel(int rs, size_t per_sample, const float *__restrict__ part,
-                                                             const float *__restrict__ scale, float *__restrict__ out) {
-    const int smp = blockIdx.y;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= per_sample) return;
-    const float *p = part + (size_t)smp * rs * per_sample + i;
-    float s = p[0];
-    for (int t = 1; t < rs; t++) s += p[t * per_sample];
-    out[(size_t)smp * per_sample + i] = scale ? s * scale[smp] : s;  // optional upstream gradient (match_cost.py:41-42)
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Implicit match ("pair" kernel): what the Python-level match_cost needs is cost[b] and, when the clouds require
-// gradients, grad1 / grad2 -- never the 512 MiB match tensor itself (reference match_cost.py:25-27,39-42 keeps it on
-// ctx only to feed MatchCostGrad, and the gradient treats match as a constant).  This kernel evaluates every match
-// element in registers exactly as am_materialise_kernel does (same level order, same rounding) and feeds it straight
-// into the cost sum (approxmatch.cu:207-208) and both gradient sums (:239-246, :277-285): no store, no re-read.
-// It runs in the Hilbert-sorted index space of the phase kernels, which buys two exact skips the materialising path
-// cannot have (match is laid out in the caller's order there):
-//   * a level whose exp2(c_i d2) underflows to 0 for every pair (row point, 64Q-column box) is skipped
-//     (wave-uniform; the same test as V_CULL, applied to all levels);
-//   * a row whose live levels are all skipped for this column box contributes exactly 0: no distance, no sqrt.
-// Mapping: workgroup = kPairRT rows (set2 points, sorted) x 64Q columns (set1 points, sorted); a lane owns Q
-// consecutive columns (coordinates, the nine ratioL values and the column sums stay in registers), the 4 waves deal
-// the rows round-robin, row data is broadcast from LDS.  Row sums: per-lane partials are parked in LDS and folded
-// eight rows at a time (48 lanes x 32 sequential adds + one shuffle), so the VALU never runs a 64-lane butterfly per
-// row.  All partials are combined in a fixed order by the second-stage kernels: deterministic.
-// ---------------------------------------------------------------------------------------------------
-constexpr int kPairRT = 128;  // rows per workgroup (32 per wave; 256: partials halve, 437 vs 432 us per call)
-constexpr int kPairRB = 8;    // rows per row-sum fold
-constexpr int kPairPad = 65;  // stash row pitch (floats): lanes of one fold hit distinct banks
-
-struct PairArgs {
-    int n, m, n4, m4;
-    const float *soa1, *soa2;   // [b][3][n4] / [b][3][m4] sorted coordinates
-    const float *lv;            // [b][9][n4 + m4] sorted level rows: ratioL | ratioR
-    LevelConsts lc;
-    float cut2[kLevels];        // a level is exactly 0 beyond this squared distance
-    float *cost_part;           // [b][gridDim.y * gridDim.x]
-    float *part1;               // [b][row_tiles][n4][3]   column sums (grad1, sorted space)
-    float *part2;               // [b][col_blocks][m4][3]  row sums    (grad2, sorted space)
-    int col_blocks, row_tiles, bc;  // 1-D grid of col_blocks * row_tiles * bc workgroups (see the kernel)
-};
-
-template <int Q, bool GRAD>
-__global__ __launch_bounds__(256) void am_pair_kernel(PairArgs a) {
-    __shared__ float4 lds_l[kPairRT][3];  // (x,y,z,rr0) (rr1..rr4) (rr5..rr8)
-    __shared__ int lds_mask[kPairRT];     // bit i: level i contributes to this row segment
-    __shared__ float stash[GRAD ? 4 * kPairRB * 3 * kPairPad : 4];
-    __shared__ float lds_red[4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Dispatch order = work order.  A workgroup's duration goes from ~0 (every row of the tile masked out for this column
-    // box) to the full 128 x 256 pairs on all live levels, and the heavy ones are the (row tile, column block) pairs that
-    // are CLOSE in space -- close along the two Hilbert orders.  In (x, y, z) grid order the last workgroups dispatched
-    // were as likely heavy as light and the chip idled 22 % of the kernel behind them (SQ_BUSY_CU_CYCLES).  The 1-D grid
-    // is read shift-major instead: for every shift 0, +1, -1, +2, ... of the row tile against the column block's own
-    // position along the curve, every column block, every sample -- near pairs first, far (short) ones last.
-    const int cbn = a.col_blocks, rtn = a.row_tiles;
-    const int item = (int)blockIdx.x / a.bc, smp = (int)blockIdx.x - item * a.bc;
-    const int shift_k = item / cbn, cblk = item - shift_k * cbn;
-    const int base_r = (int)(((long long)(2 * cblk + 1) * rtn) / (2 * cbn));
-    const int shift = ((shift_k + 1) >> 1) * ((shift_k & 1) ? 1 : -1);  // 0, +1, -1, +2, ... : a complete residue system mod rtn
-    const int rtile = ((base_r + shift) % rtn + rtn) % rtn;
-    const int l0 = rtile * kPairRT;
-    const int kb = cblk * 64 * Q;
-    const int k0 = kb + lane * Q;
-    const size_t nm4 = (size_t)a.n4 + a.m4;
-    const float *lvb = a.lv + (size_t)smp * kLevels * nm4;
-    const float *s1 = a.soa1 + (size_t)smp * 3 * a.n4;
-    const float *s2 = a.soa2 + (size_t)smp * 3 * a.m4;
-    const int lcnt = min(kPairRT, a.m - l0);
-
-    // this thread's row (the first lcnt threads finish one row each once the column box is known)
-    float rowx = 0.f, rowy = 0.f, rowz = 0.f, rowr[kLevels];
-#pragma unroll
-    for (int i = 0; i < kLevels; i++) rowr[i] = 0.f;
-    if (tid < lcnt) {
-        const int l = l0 + tid;
-        rowx = s2[l];
-        rowy = s2[a.m4 + l];
-        rowz = s2[2 * a.m4 + l];
-#pragma unroll
-        for (int i = 0; i < kLevels; i++) rowr[i] = lvb[(size_t)i * nm4 + a.n4 + l];
-    }
-    float x1[Q], y1[Q], z1[Q], rl[kLevels][Q];
-    float blo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float bhi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        const bool real = k0 + q < a.n;
-        const int k = real ? k0 + q : a.n - 1;
-        x1[q] = s1[k];
-        y1[q] = s1[a.n4 + k];
-        z1[q] = s1[2 * a.n4 + k];
-#pragma unroll
-        for (int i = 0; i < kLevels; i++) rl[i][q] = real ? lvb[(size_t)i * nm4 + k] : 0.f;  // a padded column weighs 0
-        blo[0] = fminf(blo[0], x1[q]); bhi[0] = fmaxf(bhi[0], x1[q]);
-        blo[1] = fminf(blo[1], y1[q]); bhi[1] = fmaxf(bhi[1], y1[q]);
-        blo[2] = fminf(blo[2], z1[q]); bhi[2] = fmaxf(bhi[2], z1[q]);
-    }
-    // bounding box of the 64Q columns of this workgroup (every wave holds the same columns)
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            blo[c] = fminf(blo[c], __shfl_xor(blo[c], off, 64));
-            bhi[c] = fmaxf(bhi[c], __shfl_xor(bhi[c], off, 64));
-        }
-    }
-    if (tid < lcnt) {
-        // level i adds exactly 0 to the whole row segment if ratioR_i == 0 (exhausted query point,
-        // approxmatch.cu:108-109) or if every exponential underflows: every pair (row, column of the box) has
-        // d2 >= bd2
-        const float bx = fmaxf(fmaxf(blo[0] - rowx, rowx - bhi[0]), 0.f);
-        const float by = fmaxf(fmaxf(blo[1] - rowy, rowy - bhi[1]), 0.f);
-        const float bz = fmaxf(fmaxf(blo[2] - rowz, rowz - bhi[2]), 0.f);
-        const float bd2 = bx * bx + by * by + bz * bz;
-        int mask = 0;
-#pragma unroll
-        for (int i = 0; i < kLevels; i++) mask |= (rowr[i] != 0.f && !(bd2 > a.cut2[i])) ? (1 << i) : 0;
-        lds_l[tid][0] = make_float4(rowx, rowy, rowz, rowr[0]);
-        lds_l[tid][1] = make_float4(rowr[1], rowr[2], rowr[3], rowr[4]);
-        lds_l[tid][2] = make_float4(rowr[5], rowr[6], rowr[7], rowr[8]);
-        lds_mask[tid] = mask;
-    }
-    float g1[Q][3];
-#pragma unroll
-    for (int q = 0; q < Q; q++) g1[q][0] = g1[q][1] = g1[q][2] = 0.f;
-    float csum = 0.f;
-    float *my_stash = stash + (GRAD ? w * kPairRB * 3 * kPairPad : 0);
-    __syncthreads();
-
-    // wave w takes rows w, w+4, ...; kPairRB of them per fold
-    for (int base = 0; base < lcnt; base += 4 * kPairRB) {
-#pragma unroll 1
-        for (int s = 0; s < kPairRB; s++) {
-            const int li = base + 4 * s + w;
-            float rx = 0.f, ry = 0.f, rz = 0.f;
-            const int mask = li < lcnt ? __builtin_amdgcn_readfirstlane(lds_mask[li]) : 0;
-            if (mask) {
-                const float4 A = lds_l[li][0], B = lds_l[li][1], Cc = lds_l[li][2];
-                const float rr[kLevels] = {A.w, B.x, B.y, B.z, B.w, Cc.x, Cc.y, Cc.z, Cc.w};
-                float ex[Q], ey[Q], ez[Q], d[Q], acc[Q];
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    ex[q] = A.x - x1[q];  // p2 - p1 (approxmatch.cu:148-150)
-                    ey[q] = A.y - y1[q];
-                    ez[q] = A.z - z1[q];
-                    d[q] = sq3(ex[q], ey[q], ez[q]);
-                    acc[q] = 0.f;
-                }
-#pragma unroll
-                for (int i = 0; i < kLevels; i++) {
-                    if (mask & (1 << i)) {
-                        // w = exp(level d2) ratioL ratioR; match += w (approxmatch.cu:153-155): the product is added
-                        // with one fma (the contraction a compiler applies to `match += a * b`); am_materialise_kernel
-                        // rounds the product first -- the two differ by half an ulp of the product
-#pragma unroll
-                        for (int q = 0; q < Q; q++)
-                            acc[q] = __builtin_fmaf(fast_exp2(a.lc.c[i] * d[q]) * rl[i][q], rr[i], acc[q]);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    if (GRAD) {
-                        // max(d2, 1e-20): d2 is never NaN, so the bare instruction (no canonicalising pre-pass)
-                        float dm;
-                        asm("v_max_f32 %0, %1, %2" : "=v"(dm) : "v"(d[q]), "v"(1e-20f));
-                        const float f = acc[q] * __builtin_amdgcn_rsqf(dm);
-                        // sqrt(d2) = d2 * rsqrt(d2): one transcendental serves both sums (d2 < 1e-20 moves the cost by < 1e-10)
-                        csum = __builtin_fmaf(f, d[q], csum);
-                        // t = (p2 - p1) match / |p1 - p2|: grad2 (rows) accumulates +t (approxmatch.cu:240-246), grad1
-                        // (columns) the negated vector (:281-284)
-                        g1[q][0] = __builtin_fmaf(-ex[q], f, g1[q][0]);
-                        g1[q][1] = __builtin_fmaf(-ey[q], f, g1[q][1]);
-                        g1[q][2] = __builtin_fmaf(-ez[q], f, g1[q][2]);
-                        rx = __builtin_fmaf(ex[q], f, rx);
-                        ry = __builtin_fmaf(ey[q], f, ry);
-                        rz = __builtin_fmaf(ez[q], f, rz);
-                    } else {
-                        csum = __builtin_fmaf(acc[q], __builtin_amdgcn_sqrtf(d[q]), csum);
-                    }
-                }
-            }
-            if (GRAD) {
-                my_stash[(s * 3 + 0) * kPairPad + lane] = rx;
-                my_stash[(s * 3 + 1) * kPairPad + lane] = ry;
-                my_stash[(s * 3 + 2) * kPairPad + lane] = rz;
-            }
-        }
-        if (GRAD) {
-            // fold the eight rows: lane (v, h) adds half h of vector v = (slot, component) in index order, the two
-            // halves meet through one shuffle.  The stash is private to the wave: no workgroup barrier.
-            const int v = lane % 24, h = lane / 24;
-            float t = 0.f;
-            __builtin_amdgcn_wave_barrier();  // LDS operations of one wave execute in order; keep the compiler to it
-            if (lane < 48) {
-                const float *src = my_stash + v * kPairPad + h * 32;
-#pragma unroll 8
-                for (int i = 0; i < 32; i++) t += src[i];
-            }
-            __builtin_amdgcn_wave_barrier();
-            const float hi = __shfl(t, lane + 24, 64);
-            const int sl = v / 3, c = v - sl * 3;
-            const int li = base + 4 * sl + w;
-            if (lane < 24 && li < lcnt)
-                a.part2[(((size_t)smp * cbn + cblk) * a.m4 + (l0 + li)) * 3 + c] = t + hi;
-        }
-    }
-    // cost partial of this workgroup
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) csum += __shfl_down(csum, off, 64);
-    if (lane == 0) lds_red[w] = csum;
-    __syncthreads();
-    if (tid == 0)
-        a.cost_part[(size_t)smp * cbn * rtn + rtile * cbn + cblk] =
-            ((lds_red[0] + lds_red[1]) + lds_red[2]) + lds_red[3];
-    if (GRAD) {
-        // column sums: waves 1..3 hand theirs to wave 0 one after the other (fixed order); the stash is free now
-        static_assert(Q * 3 * 64 <= 4 * kPairRB * 3 * kPairPad, "column merge reuses the stash");
-        for (int src = 1; src < 4; src++) {
-            __syncthreads();
-            if (w == src) {
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) stash[(q * 3 + c) * 64 + lane] = g1[q][c];
-            }
-            __syncthreads();
-            if (w == 0) {
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) g1[q][c] += stash[(q * 3 + c) * 64 + lane];
-            }
-        }
-        if (w == 0) {
-            float *dst = a.part1 + (((size_t)smp * rtn + rtile) * a.n4) * 3;
-#pragma unroll
-            for (int q = 0; q < Q; q++) {
-                if (k0 + q < a.n) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) dst[(size_t)(k0 + q) * 3 + c] = g1[q][c];
-                }
-            }
-        }
-    }
-}
-
-// Second stage of the implicit path: partials are added in index order (deterministic) and the gradients carried from
-// the sorted index space back to the caller's point order through `rank`.
-// The three second-stage reductions of the implicit path in ONE launch (blockIdx.z: 0 = grad1, 1 = grad2, 2 = cost).
-struct FinishArgs {
-    int parts[3], npts[2], pitch[2];
-    const float *part[3];
-    const int *perm[2];   // sorted position -> caller's point index
-    const float *scale;
-    float *out[3];
-    // the Chamfer half of a ChamferEMD call rides along (blockIdx.z == 3): loss[b] = sum / mean of the two distance rows
-    const float *ch_d1, *ch_d2;
-    float *ch_loss;
-    int ch_n, ch_m, ch_mean;
-    const int *flags;  // live-counter rows [b][kLiveRow] (slots kInfSlot, kInfSlot + 1), or null
-};
-__global__ __launch_bounds__(256) void pair_finish_kernel(FinishArgs f) {
-    __shared__ float red[256];
-    const int which = blockIdx.z, smp = blockIdx.y, tid = threadIdx.x;
-    if (which == 3) {  // the same fixed-order tree as chamfer_reduce_kernel (chamfer.hip): the same bits
-        if (blockIdx.x) return;
-        __shared__ float red2[256];
-        float s1 = 0.f, s2 = 0.f;
-        // (eight loads in flight, added in the same order: one at a time this slice was a chain of n / 256 round trips, the
-        // longest of the launch)
-        auto strided_sum = [&](const float *d, int cnt) -> float {
-            float acc = 0.f;
-            for (int i0 = tid; i0 < cnt; i0 += 8 * 256) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) v[u] = d[min(i0 + u * 256, cnt - 1)];
-#pragma unroll
-                for (int u = 0; u < 8; u++)
-                    if (i0 + u * 256 < cnt) acc += v[u];
-            }
-            return acc;
-        };
-        s1 = strided_sum(f.ch_d1 + (size_t)smp * f.ch_n, f.ch_n);
-        s2 = strided_sum(f.ch_d2 + (size_t)smp * f.ch_m, f.ch_m);
-        red[tid] = s1;
-        red2[tid] = s2;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (tid < off) {
-                red[tid] += red[tid + off];
-                red2[tid] += red2[tid + off];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) f.ch_loss[smp] = f.ch_mean ? red2[0] / (float)f.ch_m + red[0] / (float)f.ch_n : red[0] + red2[0];
-        return;
-    }
-    // a sample with an infinite coordinate: NaN cost and gradients (see am_sort_kernel)
-    // ... or whose resident fine-level passes did not complete (am_fine_persist_kernel: a sample barrier timed out)
-    const bool poisoned = f.flags && (f.flags[(size_t)smp * kLiveRow + kInfSlot] | f.flags[(size_t)smp * kLiveRow + kInfSlot + 1] |
-                                      f.flags[(size_t)smp * kLiveRow + kErrSlot]);
-    if (which == 2) {  // cost[b] = sum of the workgroup partials, fixed order
-        if (blockIdx.x) return;
-        const int parts = f.parts[2];
-        float s = 0.f;
-        for (int i = tid; i < parts; i += 256) s += f.part[2][(size_t)smp * parts + i];
-        red[tid] = s;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (tid < off) red[tid] += red[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) f.out[2][smp] = poisoned ? __builtin_nanf("") : red[0];
-        return;
-    }
-    if (!f.out[which]) return;
-    // a thread owns component c of SORTED position s: the partial rows are read as straight coalesced streams (they
-    // are the bulk: parts x npts x 12 bytes); only the 12-byte result is scattered to the caller's point order
-    const int npts = f.npts[which], pitch = f.pitch[which], parts = f.parts[which];
-    const int i = blockIdx.x * 256 + tid;
-    if (i >= npts * 3) return;
-    const int s = i / 3, c = i - s * 3;
-    const float *p = f.part[which] + (size_t)smp * parts * pitch * 3 + i;
-    const int pt = f.perm[which][(size_t)smp * npts + s];
-    // the partials in the fixed order t = 0, 1, 2 ..., eight loads in flight (one at a time, the fold is a chain of
-    // `parts` memory round trips: most of this kernel's time)
-    const size_t stride = (size_t)pitch * 3;
-    float acc = p[0];
-    int t = 1;
-    for (; t + 8 <= parts; t += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(size_t)(t + u) * stride];
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc += v[u];
-    }
-    {
-        float v[7];
-#pragma unroll
-        for (int u = 0; u < 7; u++) v[u] = p[(size_t)min(t + u, parts - 1) * stride];
-#pragma unroll
-        for (int u = 0; u < 7; u++)
-            if (t + u < parts) acc += v[u];
-    }
-    f.out[which][((size_t)smp * npts + pt) * 3 + c] = poisoned ? __builtin_nanf("") : f.scale ? acc * f.scale[smp] : acc;
 }
 
 // ---- host side -------------------------------------------------------------------------------------
@@ -2355,38 +1217,17 @@ int launch_phase(const PhaseArgs &a, int b, int var, hipStream_t st, const char 
     return launch_phase_rs<MODE, 1, 8>(a, b, var, st, what);
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 size_t cost_parts(int n, int m) { return (size_t)pcc::ceil_div(n, kMatKT) * pcc::ceil_div(m, kMatLT); }
-
-// Every workspace section offset to one sample (each is indexed [sample][...]): a lane of samples [s0, s0 + bc) runs
-// on the view at s0.  Sizes below are per sample.
-struct WsView {
-    float *soa1, *soa2;                // [3][n4] / [3][m4] Hilbert-sorted coordinates
-    int *rank1, *rank2, *perm1, *perm2;  // [n] / [m] caller's index -> sorted position, and back
-    float *box1, *box2;                // [nb][8] per 16 sorted points
-    float *rem;                        // sorted space: remainL (n4) | remainR ping (m4) | pong (m4)
-    float *lv;                         // [kLevels][n4 + m4] sorted space: ratioL | ratioR
-    float *lv_orig;                    // [kLevels][n + m] the level rows in the caller's order
-    float *cpart;                      // [cost_parts] cost partials of the materialise pass
-    float *clist;                      // [5][m4] dense candidate list handed from pass B to pass C/A
-    int *clist_cnt;                    // [1]
-    int *live_cnt;                     // [kLiveRow] live-owner counters and flags
-    unsigned *live_mask;               // [kLevels][mask_words] live bits of set2 per level (V_COWN)
-    float4 *aos1, *aos2;               // [n] / [m] packed sorted points for the nearest-neighbour search of pcc_chamfer_emd
-    float *pair_cost, *part1, *part2;  // implicit path only: am_pair_kernel's cost and gradient partials (PairArgs)
-};
 
 // Workspace carve (bytes, every section 16-byte aligned).  The implicit path (match_cost_implicit_impl) passes its
 // am_pair_kernel tiling: its three sections follow the others and are empty on the materialising path.
-struct WsLayout {
-    int b, n, m, n4, m4, nb1, nb2;
+struct WsLayout : pcc::AmDims {
+    int b;
     int col_blocks, row_tiles;
     bool grad;
     size_t total;
     WsLayout(int b_, int n_, int m_, int col_blocks_ = 0, int row_tiles_ = 0, bool grad_ = false)
-        : b(b_), n(n_), m(m_), n4((n_ + 3) & ~3), m4((m_ + 3) & ~3), nb1(pcc::ceil_div(n_, kBox)),
-          nb2(pcc::ceil_div(m_, kBox)), col_blocks(col_blocks_), row_tiles(row_tiles_), grad(grad_) {
+        : AmDims(n_, m_), b(b_), col_blocks(col_blocks_), row_tiles(row_tiles_), grad(grad_) {
         WsView unused;
         total = carve(0, 0, unused);
     }
@@ -2395,8 +1236,6 @@ struct WsLayout {
         carve(reinterpret_cast<uintptr_t>(base), (size_t)s, v);
         return v;
     }
-    size_t rem_floats() const { return (size_t)n4 + 2 * (size_t)m4; }   // per sample
-    size_t lv_floats() const { return kLevels * ((size_t)n4 + m4); }
 
   private:
     // The sections in order: points every pointer of `v` at sample s of the workspace at `base`; returns the end offset.
@@ -2431,51 +1270,6 @@ struct WsLayout {
         return o;
     }
 };
-
-void launch_sort(const SortArgs &a, int slots, dim3 grid, hipStream_t st) {
-    pcc::ProfScope prof("am_sort_kernel", st);
-    switch (slots) {
-    case 4: hipLaunchKernelGGL((am_sort_kernel<4>), grid, dim3(kSortT), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((am_sort_kernel<8>), grid, dim3(kSortT), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((am_sort_kernel<16>), grid, dim3(kSortT), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((am_sort_kernel<32>), grid, dim3(kSortT), 0, st, a); break;
-    default: hipLaunchKernelGGL((am_sort_kernel<64>), grid, dim3(kSortT), 0, st, a); break;
-    }
-}
-
-// Sorts the bc samples of the view `v` (xyz1 / xyz2: their first sample); `aos`: also write the packed rows aos1 / aos2.
-int sort_clouds(const WsLayout &L, const WsView &v, int bc, const float *xyz1, const float *xyz2, bool aos, hipStream_t st) {
-    SortArgs a{};
-    a.live_cnt = v.live_cnt;
-    a.live_mask = v.live_mask;
-    a.mask_words = mask_words(L.m4);
-    if (aos) { a.aos[0] = v.aos1; a.aos[1] = v.aos2; }
-    // the padded tails of the weight rows are staged as float4: they must be finite (their candidates sit at the
-    // origin with these weights), and V_COWN relies on zero-filled level arrays for the exhausted owners it never
-    // touches: remain rows are cleared by the workgroup sorting set1, level rows by the one sorting set2
-    a.zero[0] = v.rem; a.zero_stride[0] = a.zero_count[0] = (long long)L.rem_floats();
-    a.zero[1] = v.lv; a.zero_stride[1] = a.zero_count[1] = (long long)L.lv_floats();
-    const int nn[2] = {L.n, L.m};
-    int slots = 4;
-    for (int w = 0; w < 2; w++) {
-        int npad = 4 * kSortT;
-        while (npad < nn[w]) npad <<= 1;
-        if (npad > 64 * kSortT) npad = 0;  // > 16384 points: keep the original order (nothing is culled)
-        a.n[w] = nn[w];
-        a.npad[w] = npad;
-        slots = std::max(slots, npad / kSortT);
-    }
-    for (int w = 0; w < 2; w++)
-        if (a.npad[w]) a.npad[w] = kSortT * slots;  // one SLOTS instantiation serves both clouds
-    a.n4[0] = L.n4; a.n4[1] = L.m4; a.nb[0] = L.nb1; a.nb[1] = L.nb2;
-    a.xyz[0] = xyz1; a.xyz[1] = xyz2; a.soa[0] = v.soa1; a.soa[1] = v.soa2;
-    for (int w = 0; w < 2; w++) {
-        a.sstride[w] = (long long)nn[w] * 3; a.pstride[w] = 3; a.cstride[w] = 1; a.nch[w] = 3;
-    }
-    a.rank[0] = v.rank1; a.rank[1] = v.rank2; a.perm[0] = v.perm1; a.perm[1] = v.perm2; a.box[0] = v.box1; a.box[1] = v.box2;
-    launch_sort(a, slots, dim3(bc, 2), st);
-    return pcc::check_launch("approxmatch(sort)");
-}
 
 // One internal side stream per device: the second half of a large batch runs its 19 dependent phase launches there
 // while the first half runs on the caller's stream, so that one half's kernels fill the launch / drain bubbles of
@@ -2632,7 +1426,7 @@ int run_levels(const WsLayout &L, char *base, const float *xyz1, const float *xy
     auto enqueue_head = [&](int l) -> int {
         const Lane &ln = lanes[l];
         const size_t s0 = (size_t)ln.s0;
-        int r = sort_clouds(L, ln.v, ln.bc, xyz1 + s0 * L.n * 3, xyz2 + s0 * L.m * 3, (bool)after_sort, ln.st);
+        int r = pcc::sort_clouds(L, ln.v, ln.bc, xyz1 + s0 * L.n * 3, xyz2 + s0 * L.m * 3, (bool)after_sort, ln.st);
         // work that only needs the sorted clouds of this lane's samples (pcc_chamfer_emd: the nearest-neighbour search).
         // Even lanes run it here, odd lanes behind their passes: two searches at the same moment halve each other (each
         // wants every SIMD); against the other lane's pass chain a search costs less (chamfer_emd 447.7 -> 440.4 us, step
@@ -2709,7 +1503,7 @@ int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, 
         }
         rc = pcc::check_launch("approxmatch(materialise+cost)");
         if (rc) return rc;
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3(b), dim3(256), 0, st, (int)cost_parts(n, m), v.cpart, cost_out);
+        pcc::launch_reduce_rows(b, (int)cost_parts(n, m), v.cpart, cost_out, st);
         return pcc::check_launch("approxmatch(cost reduce)");
     }
     {
@@ -2720,103 +1514,24 @@ int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, 
     return pcc::check_launch("approxmatch(materialise)");
 }
 
-// cost[b] (and grad1 / grad2 when both are non-null) of the Python-level match_cost without materialising match.
-template <int Q>
-int launch_pair(const PairArgs &pa, dim3 grid, bool grad, hipStream_t st) {
-    pcc::ProfScope prof(grad ? "am_pair_kernel<grad>" : "am_pair_kernel<cost>", st);
-    if (grad) hipLaunchKernelGGL((am_pair_kernel<Q, true>), grid, dim3(256), 0, st, pa);
-    else hipLaunchKernelGGL((am_pair_kernel<Q, false>), grid, dim3(256), 0, st, pa);
-    return pcc::check_launch("match_cost(pair)");
-}
-
 int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost,
                              float *cost, float *grad1, float *grad2, hipStream_t st,
                              const pcc::ChamferOut *chamfer = nullptr) {
-    constexpr int q_cols = 4;  // columns per lane of am_pair_kernel (2 measured slower)
     const bool grad = grad1 && grad2;
-    const int col_blocks = pcc::ceil_div(n, 64 * q_cols), row_tiles = pcc::ceil_div(m, kPairRT);
+    const int col_blocks = pcc::ceil_div(n, 64 * kPairQ), row_tiles = pcc::ceil_div(m, kPairRT);
     const WsLayout L(b, n, m, col_blocks, row_tiles, grad);
     pcc::WsBlock ws(st);
     if (int rc = ws.alloc(L.total, "workspace allocation failed")) return rc;
     char *base = static_cast<char *>(ws.p);
     const LevelConsts lc = make_levels();
-    // pair + finish kernels of the samples [s0, s0 + bc) on `lst`
     auto tail = [&](int s0, int bc, hipStream_t lst) -> int {
-        const size_t o = (size_t)s0;
-        const WsView v = L.view(base, s0);
-        PairArgs pa{};
-        pa.n = n; pa.m = m; pa.n4 = L.n4; pa.m4 = L.m4;
-        pa.soa1 = v.soa1; pa.soa2 = v.soa2; pa.lv = v.lv;
-        pa.lc = lc;
-        for (int i = 0; i < kLevels; i++) pa.cut2[i] = zero_cut2(lc, i);
-        pa.cost_part = v.pair_cost;
-        pa.part1 = grad ? v.part1 : nullptr;
-        pa.part2 = grad ? v.part2 : nullptr;
-        pa.col_blocks = col_blocks; pa.row_tiles = row_tiles; pa.bc = bc;
-        if ((long long)col_blocks * row_tiles * bc > 0x7fffffffLL) return pcc::invalid("match_cost: grid too large");
-        const dim3 grid((unsigned)(col_blocks * row_tiles * bc));
-        if (int rc = launch_pair<q_cols>(pa, grid, grad, lst)) return rc;
-        FinishArgs f{};
-        f.parts[0] = row_tiles; f.parts[1] = col_blocks; f.parts[2] = col_blocks * row_tiles;
-        f.npts[0] = n; f.npts[1] = m; f.pitch[0] = L.n4; f.pitch[1] = L.m4;
-        f.part[0] = pa.part1; f.part[1] = pa.part2; f.part[2] = pa.cost_part;
-        f.perm[0] = v.perm1; f.perm[1] = v.perm2;
-        f.scale = grad_cost ? grad_cost + o : nullptr;
-        f.out[0] = grad ? grad1 + o * n * 3 : nullptr;
-        f.out[1] = grad ? grad2 + o * m * 3 : nullptr;
-        f.out[2] = cost + o;
-        f.flags = v.live_cnt;  // (written by this call's sort)
-        if (chamfer) {
-            f.ch_d1 = chamfer->dist1 + o * n; f.ch_d2 = chamfer->dist2 + o * m; f.ch_loss = chamfer->loss + o;
-            f.ch_n = n; f.ch_m = m; f.ch_mean = chamfer->mean;
-        }
-        {
-            pcc::ProfScope prof("pair_finish_kernel", lst);
-            const int blocks = grad ? pcc::ceil_div(std::max(n, m) * 3, 256) : 1;
-            hipLaunchKernelGGL(pair_finish_kernel, dim3(blocks, bc, chamfer ? 4 : 3), dim3(256), 0, lst, f);
-        }
-        return pcc::check_launch("match_cost(reduce)");
+        return pcc::launch_pair_finish(L, L.view(base, s0), s0, bc, col_blocks, row_tiles, grad_cost, cost, grad1, grad2, chamfer, lst);
     };
-    // the Chamfer half of a ChamferEMD call: nearest neighbours on the clouds this call has just sorted, both directions
-    // in one launch, then the loss reduction -- on the lane's stream, between the sort and the first pass
     auto nn_after_sort = [&](int s0, int bc, hipStream_t lst) -> int {
-        const size_t o = (size_t)s0;
-        const WsView v = L.view(base, s0);
-        NNSortedArgs q1{}, q2{};
-        q1.n_q = n; q1.n_c = m; q1.q_n4 = L.n4; q1.c_n4 = L.m4; q1.q_nb = L.nb1; q1.c_nb = L.nb2;
-        q1.groups = L.nb1; q1.batch = bc;
-        q1.q_soa = v.soa1; q1.c_aos = v.aos2; q1.q_box = v.box1; q1.c_box = v.box2; q1.q_perm = v.perm1;
-        q1.out_d = chamfer->dist1 + o * n; q1.out_i = chamfer->idx1 + o * n;
-        q2.n_q = m; q2.n_c = n; q2.q_n4 = L.m4; q2.c_n4 = L.n4; q2.q_nb = L.nb2; q2.c_nb = L.nb1;
-        q2.groups = L.nb2; q2.batch = bc;
-        q2.q_soa = v.soa2; q2.c_aos = v.aos1; q2.q_box = v.box2; q2.c_box = v.box1; q2.q_perm = v.perm2;
-        q2.out_d = chamfer->dist2 + o * m; q2.out_i = chamfer->idx2 + o * m;
-        const long long w0 = (long long)bc * q1.groups, w1 = (long long)bc * q2.groups;
-        const long long grid = (w0 + w1 + kNNWaves - 1) / kNNWaves;
-        if (w0 + w1 > 0x7fffffffLL) return pcc::invalid("chamfer_emd: grid too large");
-        {
-            pcc::ProfScope prof("nn_sorted_kernel", lst);
-            hipLaunchKernelGGL(nn_sorted_kernel, dim3((unsigned)grid), dim3(64 * kNNWaves), 0, lst, q1, q2, (int)w0);
-        }
-        return pcc::check_launch("chamfer_emd(nearest neighbours)");  // (the loss reduction rides in the finish launch)
+        return pcc::launch_nn_sorted(L, L.view(base, s0), s0, bc, chamfer, lst);
     };
     if (chamfer) return run_levels(L, base, xyz1, xyz2, lc, st, tail, nn_after_sort);
     return run_levels(L, base, xyz1, xyz2, lc, st, tail);
-}
-
-int check_sizes(const char *who, int b, int n, int m) {
-    if (b < 0 || n < 0 || m < 0) return pcc::invalid(who);
-    if ((long long)n * 3 > 0x7fffffffLL || (long long)m * 3 > 0x7fffffffLL) return pcc::invalid(who);
-    return PCC_OK;
-}
-
-// n == 0 or m == 0: the sums are empty, so cost[b] and the gradients that have elements are 0 (null: not requested)
-int zero_fill_empty(int b, int n, int m, float *cost, float *grad1, float *grad2, hipStream_t st, const char *what) {
-    hipError_t e = hipSuccess;
-    if (cost) e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st);
-    if (n && grad1 && e == hipSuccess) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(float), st);
-    if (m && grad2 && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(float), st);
-    return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, what), (int)e);
 }
 
 // pcc_approxmatch (with_cost false) and pcc_approxmatch_cost: the same checks, each under its own name
@@ -2844,19 +1559,6 @@ int match_cost_with_chamfer(int b, int n, int m, const float *xyz1, const float 
     return match_cost_implicit_impl(b, n, m, xyz1, xyz2, nullptr, cost, grad1, grad2, st, &chamfer);
 }
 
-// Hilbert sort of ONE channels-major cloud per sample (x[b][c][n], 1 <= c <= 3) for the k-NN graph (knn.hip): packed
-// sorted rows (x, y, z, original index), the 16-point boxes and the sorted -> original permutation.
-int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st) {
-    SortArgs a{};
-    int npad = 4 * kSortT;
-    while (npad < n) npad <<= 1;
-    if (npad > 64 * kSortT) npad = 0;  // > 16384 points: original order
-    a.n[0] = n; a.npad[0] = npad; a.n4[0] = (n + 3) & ~3; a.nb[0] = pcc::ceil_div(n, kBox);
-    a.xyz[0] = x; a.sstride[0] = (long long)c * n; a.pstride[0] = 1; a.cstride[0] = n; a.nch[0] = c;
-    a.aos[0] = aos; a.box[0] = box16; a.perm[0] = perm;
-    launch_sort(a, npad ? npad / kSortT : 4, dim3(b, 1), st);
-    return pcc::check_launch("knn(sort)");
-}
 }  // namespace pcc
 
 extern "C" {
@@ -2902,75 +1604,6 @@ int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, co
 void approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                  pcc_stream_t stream) {
     (void)pcc_approxmatch(b, n, m, xyz1, xyz2, match, temp, stream);
-}
-
-int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *out,
-                  pcc_stream_t stream) {
-    pcc::clear_error();
-    if (int rc = check_sizes("matchcost: bad size", b, n, m)) return rc;
-    if (b == 0) return PCC_OK;
-    if (!out) return pcc::invalid("matchcost: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) return zero_fill_empty(b, n, m, out, nullptr, nullptr, st, "matchcost: memset failed");
-    if (!xyz1 || !xyz2 || !match) return pcc::invalid("matchcost: null pointer");
-    const int tiles = pcc::ceil_div(m, kRowRT);
-    pcc::WsBlock ws(st);
-    if (int rc = ws.alloc((size_t)b * tiles * sizeof(float), "workspace allocation failed")) return rc;
-    float *part = static_cast<float *>(ws.p);
-    const bool vec = (n % 4 == 0) && aligned16(match);
-    {
-        pcc::ProfScope prof("am_row_kernel<cost>", st);
-        if (vec) hipLaunchKernelGGL((am_row_kernel<true>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
-        else hipLaunchKernelGGL((am_row_kernel<false>), dim3(tiles, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, part);
-    }
-    if (int rc = pcc::check_launch("matchcost")) return rc;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(b), dim3(256), 0, st, tiles, part, out);
-    return pcc::check_launch("matchcost(reduce)");
-}
-
-void matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *out,
-               pcc_stream_t stream) {
-    (void)pcc_matchcost(b, n, m, xyz1, xyz2, match, out, stream);
-}
-
-int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
-                             const float *grad_cost, float *grad1, float *grad2, pcc_stream_t stream) {
-    pcc::clear_error();
-    if (int rc = check_sizes("matchcostgrad: bad size", b, n, m)) return rc;
-    if (b == 0) return PCC_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0 || m == 0) return zero_fill_empty(b, n, m, nullptr, grad1, grad2, st, "matchcostgrad: memset failed");
-    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2) return pcc::invalid("matchcostgrad: null pointer");
-    const bool vec = (n % 4 == 0) && aligned16(match);
-    const int row_tiles = pcc::ceil_div(m, kGradRT), slabs = pcc::ceil_div(n, kGradSlab);
-    pcc::WsBlock ws(st);
-    const size_t p1_elems = (size_t)b * row_tiles * n * 3, p2_elems = slabs > 1 ? (size_t)b * slabs * m * 3 : 0;
-    if (int rc = ws.alloc((p1_elems + p2_elems) * sizeof(float), "workspace allocation failed")) return rc;
-    float *part1 = static_cast<float *>(ws.p);
-    float *part2 = slabs > 1 ? part1 + p1_elems : grad2;  // a single slab writes grad2 directly
-    {
-        pcc::ProfScope prof("am_grad_fused_kernel", st);
-        const dim3 grid(row_tiles, slabs, b);
-        const float *sc2 = slabs > 1 ? nullptr : grad_cost;
-        if (vec) hipLaunchKernelGGL((am_grad_fused_kernel<true>), grid, dim3(256), 0, st, n, m, row_tiles, xyz1, xyz2, match, part1, part2, sc2);
-        else hipLaunchKernelGGL((am_grad_fused_kernel<false>), grid, dim3(256), 0, st, n, m, row_tiles, xyz1, xyz2, match, part1, part2, sc2);
-    }
-    if (int rc = pcc::check_launch("matchcostgrad(fused)")) return rc;
-    const size_t per1 = (size_t)n * 3, per2 = (size_t)m * 3;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)((per1 + 255) / 256), b), dim3(256), 0, st, row_tiles, per1, part1, grad_cost, grad1);
-    if (slabs > 1)
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)((per2 + 255) / 256), b), dim3(256), 0, st, slabs, per2, part2, grad_cost, grad2);
-    return pcc::check_launch("matchcostgrad(reduce)");
-}
-
-int pcc_matchcostgrad(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *grad1,
-                      float *grad2, pcc_stream_t stream) {
-    return pcc_matchcostgrad_scaled(b, n, m, xyz1, xyz2, match, nullptr, grad1, grad2, stream);
-}
-
-void matchcostgrad(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *grad1,
-                   float *grad2, pcc_stream_t stream) {
-    (void)pcc_matchcostgrad(b, n, m, xyz1, xyz2, match, grad1, grad2, stream);
 }
 
 }  // extern "C"

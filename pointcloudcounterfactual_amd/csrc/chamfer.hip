@@ -429,7 +429,7 @@ int pcc_chamfer_loss_grad(int b, int n, const float *xyz1, int m, const float *x
 
 // Forward of the reference's ChamferEMD reconstruction loss (metrics_and_losses.py:70-79) in one call.  The two losses
 // work on the same pair of clouds, and the approximate EMD starts by Hilbert-sorting both: the nearest-neighbour search
-// runs on those sorted clouds with box culling (nn_sorted_kernel, approxmatch.hip) instead of the exhaustive scan --
+// runs on those sorted clouds with box culling (nn_sorted_kernel, nn_sorted.hip) instead of the exhaustive scan --
 // same indices, same distances, bit for bit (tests/test_gpu_structural.py).
 // (Measured and rejected: the exhaustive search on a side stream "in the shadow" of the EMD's launch chain -- at any
 // starting pass, with or without raised wave priority for the chain -- never beat the serial order: the chain's kernels

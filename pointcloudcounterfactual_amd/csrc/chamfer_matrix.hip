@@ -26,6 +26,7 @@
 //     two-direction kernel needs the streamed cloud to fit one block.  The host stages whichever bank lets it; when both
 //     clouds are larger, each direction runs as a rows-only launch (the cost of the paired composition).
 #include "pcc_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -58,11 +59,9 @@ __device__ __forceinline__ f32x2 sq3x2(f32x2 x, f32x2 y, f32x2 z) {
 // The bits of the minimum of a distance over the 8 lanes that share lane bits 3-5 (quad_perm [1,0,3,2], quad_perm
 // [2,3,0,1], row_half_mirror).  Distances are >= +0, so their bit patterns order as unsigned integers.
 template <int CTRL>
-__device__ __forceinline__ unsigned dpp_min(unsigned v) {
-    return min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false));
-}
+__device__ __forceinline__ unsigned dpp_min(unsigned v) { return min(v, pcc::dpp<CTRL>(v, v)); }
 __device__ __forceinline__ unsigned min_over_lq(float d) {
-    return dpp_min<0x141>(dpp_min<0x4e>(dpp_min<0xb1>(__builtin_bit_cast(unsigned, d))));
+    return dpp_min<pcc::kRowHalfMirror>(dpp_min<pcc::kQuadXor2>(dpp_min<pcc::kQuadXor1>(__builtin_bit_cast(unsigned, d))));
 }
 
 // Sum of the floats whose bits are v[0 .. len) (len <= kCH), valid in thread 0: thread t adds v[t], v[t + 256], ... in
@@ -71,8 +70,7 @@ __device__ __forceinline__ float block_sum(const unsigned *v, int len, float *pa
     const int tid = threadIdx.x;
     float s = 0.f;
     for (int k = tid; k < len; k += kT) s += __builtin_bit_cast(float, v[k]);
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
+    s = pcc::wave_sum_xor(s);
     if ((tid & 63) == 0) part[tid >> 6] = s;
     __syncthreads();
     const float total = (part[0] + part[1]) + (part[2] + part[3]);

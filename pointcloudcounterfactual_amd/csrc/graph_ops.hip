@@ -6,6 +6,7 @@
 // load for all channels of a block; the backward scatter accumulates into per-workgroup LDS bins (no global
 // atomics).
 #include "pcc_common.hpp"
+#include "wave_ops.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -415,11 +416,6 @@ __host__ __device__ inline int es_run_len(int cnt) {  // entries one wave walks:
     return ((cnt + kEsWaves - 1) / kEsWaves + 63) & ~63;
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float es_dpp(float v) {  // the DPP-selected partner's value (0 where the lane has none)
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-
 __device__ __forceinline__ float es_keep(float u, unsigned f, int bit) {  // u if bit `bit` of f is set, +0 otherwise
     return __int_as_float(__float_as_int(u) & -(int)((f >> bit) & 1u));
 }
@@ -605,12 +601,12 @@ __global__ __launch_bounds__(kEsT, 8) void edge_stream_bwd_kernel(int c, int n, 
                         // select, the compiler moves the DPP move under the flag's exec mask, and a lane whose own flag is
                         // clear then is an inactive -- invalid -- source for its neighbour)
                         float x = v[cc];
-                        x += es_keep(es_dpp<0x111, 0xf>(x), f, 0);
-                        x += es_keep(es_dpp<0x112, 0xf>(x), f, 1);
-                        x += es_keep(es_dpp<0x114, 0xf>(x), f, 2);
-                        x += es_keep(es_dpp<0x118, 0xf>(x), f, 3);
-                        x += es_keep(es_dpp<0x142, 0xa>(x), f, 4);
-                        x += es_keep(es_dpp<0x143, 0xc>(x), f, 5);
+                        x += es_keep(pcc::dpp<pcc::kRowShr + 1>(x), f, 0);
+                        x += es_keep(pcc::dpp<pcc::kRowShr + 2>(x), f, 1);
+                        x += es_keep(pcc::dpp<pcc::kRowShr + 4>(x), f, 2);
+                        x += es_keep(pcc::dpp<pcc::kRowShr + 8>(x), f, 3);
+                        x += es_keep(pcc::dpp<pcc::kRowBcast15, 0xa>(x), f, 4);
+                        x += es_keep(pcc::dpp<pcc::kRowBcast31, 0xc>(x), f, 5);
                         v[cc] = x;
                     }
                     // the segment left open by the previous group of this run continues at the head of this one

@@ -31,7 +31,6 @@ namespace {
 
 constexpr int kCap = 16;     // FIFO slots per lane
 constexpr int kCH = 2048;    // candidates staged per chunk (small-c kernel)
-constexpr int kSortBoxK = pcc::kSortBox;
 constexpr int kTT128 = 1;  // tiles per stage of the 128-channel MFMA instantiation
 constexpr int kSortedMaxN = 16384;  // the sort kernel orders up to 16384 points per cloud
 
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(64 * S) void knn_small_kernel(int c, int n, int k, 
 // The exhaustive kernel above spends > 90 % of its time in the top-K insertion chains: candidates arrive in index
 // order, so a lane's K-th distance keeps improving all through the scan (K(1 + ln(N/K)) insertions per list, four lists
 // per query).  Here the cloud is first put in Hilbert order with one bounding box per 16 consecutive points (the sort
-// kernel of the approximate EMD, approxmatch.hip).  A WAVE owns one box of 16 consecutive sorted queries and works
+// kernel of the approximate EMD, cloud_sort.hip).  A WAVE owns one box of 16 consecutive sorted queries and works
 // alone: lane = (query, candidate slice), the four slices of a query take four candidates each of every 16-candidate
 // block and keep their own sorted K-list.
 //   * the candidate blocks of a window are ordered by the distance between their box and the queries' box and visited
@@ -288,12 +287,12 @@ __global__ __launch_bounds__(64 * kSW, (K == 16 ? 3 : K <= 25 ? 4 : 1)) void knn
         };
         unsigned bk = pcc::window_key(bkey, 0);
         float4 cur[4], nxt[4];
-        load4(cur, (b0 + (int)(bk & 127u)) * kSortBoxK);
+        load4(cur, (b0 + (int)(bk & 127u)) * pcc::kBox);
         for (int p = 0; p < nwin; p++) {
             if (__uint_as_float(bk & ~127u) > r) break;  // everything behind is farther still
-            const int c0 = (b0 + (int)(bk & 127u)) * kSortBoxK;
+            const int c0 = (b0 + (int)(bk & 127u)) * pcc::kBox;
             const unsigned bk_next = pcc::window_key(bkey, min(p + 1, nwin - 1));
-            load4(nxt, (b0 + (int)(bk_next & 127u)) * kSortBoxK);
+            load4(nxt, (b0 + (int)(bk_next & 127u)) * pcc::kBox);
             if (__any(cnt > kCap - 4)) flush();
             const int left = n - c0 - cs * 4;  // real candidates from cur[0] on
 #pragma unroll
@@ -587,12 +586,12 @@ inline size_t split_log_bytes(int b, int n) { return (size_t)b * pcc::ceil_div(n
 
 // Largest value of a non-negative int over the wave (wave-uniform result).
 __device__ __forceinline__ int wave_max_nonneg(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));  // row_bcast:31
+    v = max(v, pcc::dpp<pcc::kRowShr + 1>(v));
+    v = max(v, pcc::dpp<pcc::kRowShr + 2>(v));
+    v = max(v, pcc::dpp<pcc::kRowShr + 4>(v));
+    v = max(v, pcc::dpp<pcc::kRowShr + 8>(v));
+    v = max(v, pcc::dpp<pcc::kRowBcast15, 0xa>(v));  // (rows 1 and 3)
+    v = max(v, pcc::dpp<pcc::kRowBcast31, 0xc>(v));  // (rows 2 and 3)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
@@ -975,7 +974,7 @@ extern "C" int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indi
     if (k > 32 || c > 128 || pcc::tuning(PCC_TUNE_KNN_WIDE) == 1) return pcc::knn_wide(b, c, n, k, x, indices, st);
     if (c <= 3 && n <= kSortedMaxN) {
         // sorted search: workspace = packed sorted rows | boxes | permutation
-        const int nb = pcc::ceil_div(n, kSortBoxK);
+        const int nb = pcc::ceil_div(n, pcc::kBox);
         // (+256: the search loads whole 16-row blocks; the last block of the last sample may run past the cloud)
         const size_t aos_b = (size_t)b * n * 16 + 256, box_b = (size_t)b * nb * 32;
         pcc::WsBlock ws(st);

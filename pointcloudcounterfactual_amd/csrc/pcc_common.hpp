@@ -104,7 +104,7 @@ hipError_t allow_lds(size_t bytes) {
 }
 
 // The Chamfer half of pcc_chamfer_emd: computed inside the approximate-EMD call, on the clouds that call sorts
-// (approxmatch.hip); the loss reduction rides in that call's finish launch.
+// (approxmatch.hip, nn_sorted.hip); the loss reduction rides in that call's finish launch (am_pair.hip).
 struct ChamferOut {
     int mean;
     float *loss, *dist1, *dist2;
@@ -122,9 +122,9 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
 }
 
-// Hilbert sort of one channels-major cloud per sample (approxmatch.hip's sort kernel) for the k-NN graph: aos [b][n]
-// (x, y, z, original index as bits), box16 [b][ceil(n/16)][8] (lo xyz, pad, hi xyz, pad), perm [b][n] sorted -> original.
-constexpr int kSortBox = 16;
+// Hilbert sort of one channels-major cloud per sample (cloud_sort.hip's am_sort_kernel) for the k-NN graph: aos [b][n]
+// (x, y, z, original index as bits), box16 [b][ceil(n/kBox)][8] (lo xyz, pad, hi xyz, pad), perm [b][n] sorted -> original.
+constexpr int kBox = 16;  // points per bounding-box block (sorted order)
 int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st);
 
 // k-NN graph outside the range of knn.hip's kernels (knn_wide.hip): any c >= 1, 1 <= k <= min(n, 128); sizes and

@@ -1,0 +1,70 @@
+// Cross-lane idioms of the kernels, gfx950 wave64: DPP moves under their names, reductions over a row of 16 lanes and
+// over the wave.  A DPP operand is a cross-lane VALU read: no trip through the LDS crossbar (ds_bpermute, what __shfl_*
+// compiles to).  A row is 16 consecutive lanes, a quad 4.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace pcc {
+
+// dpp_ctrl words: which lane a lane reads.
+enum DppCtrl : int {
+    kQuadXor1 = 0xB1,       // quad_perm:[1,0,3,2]: lane ^ 1
+    kQuadXor2 = 0x4E,       // quad_perm:[2,3,0,1]: lane ^ 2
+    kRowShr = 0x110,        // + n, 1..15: row_shr:n, lane i - n of the row (the first n lanes of a row have no source)
+    kRowRor = 0x120,        // + n, 1..15: row_ror:n, lane i - n of the row, rotating (n = 8: lane ^ 8)
+    kRowMirror = 0x140,     // row_mirror: lane 15 - i of the row
+    kRowHalfMirror = 0x141, // row_half_mirror: lane 7 - i of the half row
+    kRowBcast15 = 0x142,    // row_bcast:15: lane 15 of the row before (rows without one: none)
+    kRowBcast31 = 0x143,    // row_bcast:31: lane 31, for rows 2 and 3
+};
+
+// The value of the lane CTRL selects.  A lane without a source, or in a row outside ROW_MASK (bit r: row r), gets `old`
+// (BOUND_CTRL: 0 instead of `old` for a missing source).
+template <int CTRL, int ROW_MASK = 0xf, bool BOUND_CTRL = false>
+__device__ __forceinline__ int dpp(int v, int old = 0) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, BOUND_CTRL); }
+template <int CTRL, int ROW_MASK = 0xf, bool BOUND_CTRL = false>
+__device__ __forceinline__ unsigned dpp(unsigned v, unsigned old = 0) { return (unsigned)dpp<CTRL, ROW_MASK, BOUND_CTRL>((int)v, (int)old); }
+template <int CTRL, int ROW_MASK = 0xf, bool BOUND_CTRL = false>
+__device__ __forceinline__ float dpp(float v, float old = 0.f) { return __int_as_float(dpp<CTRL, ROW_MASK, BOUND_CTRL>(__float_as_int(v), __float_as_int(old))); }
+template <int N, class T>
+__device__ __forceinline__ T row_ror(T v) { return dpp<kRowRor + N>(v); }
+
+// op (commutative) over the 16 lanes of a row, in every lane: pairs, quads, half rows, rows -- the xor butterfly's tree:
+template <class Op>
+__device__ __forceinline__ float row_reduce16(float v, Op op) {
+    v = op(v, dpp<kQuadXor1, 0xf, true>(v));
+    v = op(v, dpp<kQuadXor2, 0xf, true>(v));
+    v = op(v, dpp<kRowHalfMirror, 0xf, true>(v));
+    return op(v, dpp<kRowMirror, 0xf, true>(v));
+}
+// ... and by four rotations of the row (another tree: not the same bits for a sum):
+template <class Op>
+__device__ __forceinline__ float row_reduce16_ror(float v, Op op) {
+    v = op(v, row_ror<8>(v));
+    v = op(v, row_ror<4>(v));
+    v = op(v, row_ror<2>(v));
+    return op(v, row_ror<1>(v));
+}
+
+// Sums over the 64 lanes.  `down` (offsets 32 .. 1) leaves the result in lane 0 only; `xor` (offsets 1 .. 32) in every
+// lane.  The two trees differ: for a float sum they are not the same bits, so a site keeps its form.
+__device__ __forceinline__ float wave_sum_down(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+    const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
+    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+}  // namespace pcc

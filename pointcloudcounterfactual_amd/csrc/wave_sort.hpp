@@ -1,22 +1,12 @@
-// Wave-level helpers of the k-NN and nearest-neighbour searches (knn.hip, knn_wide.hip, approxmatch.hip), gfx950 wave64.
+// Wave-level helpers of the k-NN and nearest-neighbour searches (knn.hip, knn_wide.hip, nn_sorted.hip), gfx950 wave64.
 #pragma once
 #include "pcc_common.hpp"
+#include "wave_ops.hpp"
 
 namespace pcc {
 
 // 64-bit key (distance bits : index) above every real candidate: +inf distance, index INT_MAX
 constexpr unsigned long long kKeyInf = ((unsigned long long)0x7f800000u << 32) | 0x7fffffffull;
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
-    const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
-    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
-}
 
 // Ascending bitonic sort of the wave's 64 E keys (unsigned or unsigned long long), element e = lane + 64 h in v[h].
 template <class T, int E>
