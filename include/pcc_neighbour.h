@@ -49,6 +49,29 @@ int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_st
 int pcc_knn_cross(int b, int c, int nq, int n, int k, const float *q, const float *x, int64_t *indices, float *dist,
                   pcc_stream_t stream);
 
+/* Farthest point sampling: m points of every cloud xyz[b, n, 3] (point-major, the layout of the losses and of the
+ * set-metric banks), each the point farthest from the ones selected before it: idx[b, m] into the cloud and, when dist is
+ * non-null, dist[b, m].  No counterpart in the reference, whose readers draw random subsets on the host.
+ *   start     idx[b,0] = start[b], or 0 when start is NULL; a start outside [0, n-1] is clamped into it by the kernel.
+ *   mind      every point j has a running minimum mind[j], initially +inf.
+ *   update    after selecting s = idx[b,t-1] every j computes d and then `if (d < mind[j]) mind[j] = d`; d is pcc_knn's
+ *             c <= 3 form: df = x[j] - x[s] per coordinate, acc = df0 * df0, acc = fmaf(df1, df1, acc),
+ *             acc = fmaf(df2, df2, acc).  A NaN d lowers nothing.
+ *   select    idx[b,t] = argmax_j mind[j], the lowest index among equal maxima.
+ *   dist      dist[b,t] = mind of the selected point at the moment it was selected: the squared coverage radius after t
+ *             picks, non-increasing in t, dist[b,0] = +inf.
+ *   excluded  a point with a non-finite coordinate is excluded: it is never selected while a point that is not excluded
+ *             exists (not even one whose mind is 0); as a start it is written to idx[b,0] as asked and updates nothing;
+ *             dist of a selected excluded point (a start included) is NaN; a cloud of excluded points only returns its
+ *             start and then index 0 throughout.
+ *   equal points need no rule: once every remaining mind is 0 the lowest index with the maximum is returned again.
+ * Requires n >= 1, 1 <= m <= n, b <= 65535, non-null xyz and idx (PCC_EINVAL otherwise); b = 0 enqueues nothing and
+ * returns PCC_OK.  64-bit offsets throughout; workspace (clouds of more than 16384 points only: b * n floats) comes from
+ * the library's private pool.  One workgroup runs the whole chain of a cloud, so a batch of one cloud uses one compute
+ * unit.  A cloud's result depends on that cloud, m and its start only: not on b, on the cloud's position in the batch or
+ * on the kernel variant that ran. */
+int pcc_fps(int b, int n, int m, const float *xyz, const int32_t *start, int64_t *idx, float *dist, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

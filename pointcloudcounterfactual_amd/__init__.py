@@ -14,6 +14,7 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     nn_distance,
     torch_chamfer,
 )
+from pointcloudcounterfactual_amd.neighbour_ops import farthest_point_sample  # noqa: F401
 
 __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer', 'MatchCostFunction', 'NNDistanceFunction',
-           'backend', 'set_metrics']
+           'backend', 'set_metrics', 'farthest_point_sample']

@@ -67,4 +67,23 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
     return ((unsigned long long)hi << 32) | lo;
 }
+
+// Maximum of a 64-bit key: over the 16 lanes of a row in every lane of the row (the tree of row_reduce16, both halves of
+// the key through DPP), and over the wave as a wave-uniform value (the four row results read back with v_readlane).
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+    const unsigned lo = dpp<CTRL, 0xf, true>((unsigned)v), hi = dpp<CTRL, 0xf, true>((unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned long long row_max16_u64(unsigned long long v) {
+    v = max_u64(v, dpp_u64<kQuadXor1>(v));
+    v = max_u64(v, dpp_u64<kQuadXor2>(v));
+    v = max_u64(v, dpp_u64<kRowHalfMirror>(v));
+    return max_u64(v, dpp_u64<kRowMirror>(v));
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    v = row_max16_u64(v);
+    return max_u64(max_u64(readlane_u64(v, 0), readlane_u64(v, 16)), max_u64(readlane_u64(v, 32), readlane_u64(v, 48)));
+}
 }  // namespace pcc

@@ -152,6 +152,85 @@ def knn_cross(q: torch.Tensor, x: torch.Tensor, k: int, return_distance: bool = 
     return torch_knn_cross(q, x, k, return_distance)
 
 
+# ---- farthest point sampling ---------------------------------------------------------------------------------------
+
+
+def _fps_args(xyz: torch.Tensor, m: int, start: Any) -> tuple[torch.Tensor, int, torch.Tensor | None]:
+    """The checks ``farthest_point_sample`` makes before anything runs: ``(xyz detached, m, start as a tensor or None)``."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f'farthest_point_sample: expected xyz[B,N,3], got {tuple(xyz.shape)}')
+    if xyz.dtype != F32:
+        raise RuntimeError(f'xyz must be {F32}, found {xyz.dtype}')
+    b, n = xyz.shape[:2]
+    if isinstance(m, bool) or not isinstance(m, int) or m < 1 or m > n:
+        raise ValueError(f'farthest_point_sample: m must be an int in [1, N = {n}], got {m!r}')
+    if start is None or isinstance(start, torch.Tensor):
+        if start is not None:
+            if start.dim() != 1 or start.shape[0] != b or start.dtype not in (I32, I64, torch.int16, torch.int8, torch.uint8):
+                raise ValueError(f'farthest_point_sample: start must be an int tensor [B = {b}], got {tuple(start.shape)} {start.dtype}')
+            if start.device != xyz.device:
+                if xyz.device.type == 'cuda' and start.device.type != 'cuda':
+                    raise RuntimeError('start must be a CUDA tensor')
+                raise RuntimeError(f'start is on {start.device}, expected {xyz.device}')
+    elif isinstance(start, int) and not isinstance(start, bool):
+        start = torch.full((b,), min(max(start, 0), n - 1), dtype=I32, device=xyz.device) if b else None
+    else:
+        raise ValueError(f'farthest_point_sample: start must be None, an int or an int tensor [B], got {type(start).__name__}')
+    return xyz.detach(), m, start
+
+
+def torch_farthest_point_sample(xyz: torch.Tensor, m: int, start: torch.Tensor | None, return_distance: bool = False) -> Any:
+    """The rule of ``pcc_fps`` (include/pcc_neighbour.h) as a torch loop; CPU path of ``farthest_point_sample``."""
+    b, n, _ = xyz.shape
+    rows = torch.arange(b, device=xyz.device)
+    # mind of an excluded point is -1: below every real minimum, and no distance is below it
+    mind = torch.full((b, n), float('inf'), dtype=F32, device=xyz.device).masked_fill_(~torch.isfinite(xyz).all(-1), -1.0)
+    idx = torch.zeros((b, m), dtype=I64, device=xyz.device)
+    dist = torch.zeros((b, m), dtype=F32, device=xyz.device)
+    sel = torch.zeros(b, dtype=I64, device=xyz.device) if start is None else start.to(I64).clamp(0, n - 1)
+    for t in range(m):
+        if t:
+            sel = mind.argmax(1)  # (the first of equal maxima)
+        idx[:, t] = sel
+        at = mind[rows, sel]
+        dist[:, t] = torch.where(at < 0, torch.full_like(at, float('nan')), at)
+        df = xyz - xyz[rows, sel][:, None, :]
+        d = df[..., 0] * df[..., 0]
+        d = d + df[..., 1] * df[..., 1]
+        d = d + df[..., 2] * df[..., 2]
+        mind = torch.where(d < mind, d, mind)
+    return (idx, dist) if return_distance else idx
+
+
+def hip_farthest_point_sample(xyz: torch.Tensor, m: int, start: torch.Tensor | None, return_distance: bool = False) -> Any:
+    """``pcc_fps`` on checked arguments (``_fps_args``)."""
+    dev = xyz.device
+    xyz = xyz.contiguous()
+    b, n, _ = xyz.shape
+    xp = ptr(xyz, 'xyz', F32, dev)  # (checked before anything is allocated on the device)
+    if start is not None and start.dtype != I32:
+        start = start.clamp(0, n - 1).to(I32)
+    sp = ptr(None if start is None else start.contiguous(), 'start', I32, dev)
+    idx = torch.empty((b, m), dtype=I64, device=dev)
+    dist = torch.empty((b, m), dtype=F32, device=dev) if return_distance else None
+    call(_L.pcc_fps, 'fps', dev, b, n, m, xp, sp, ptr(idx, 'idx', I64, dev), ptr(dist, 'dist', F32, dev))
+    return (idx, dist) if return_distance else idx
+
+
+def farthest_point_sample(xyz: torch.Tensor, m: int, start: Any = None, return_distance: bool = False) -> Any:
+    """Farthest point sampling of ``xyz[B,N,3]`` float32: ``idx[B,m]`` int64, each entry the point farthest (squared
+    distance, lowest index among equals) from the ones before it, starting from ``start`` (``None``: point 0; an int; an int
+    tensor ``[B]``; clamped into ``[0, N-1]``).  With ``return_distance`` also ``dist[B,m]`` float32: the squared distance
+    of each selected point to the ones selected before it (``dist[:,0] = inf``), i.e. the squared coverage radius after
+    ``t`` picks.  Points with a non-finite coordinate are never selected while another point is left.  The full contract is
+    ``pcc_fps``'s (include/pcc_neighbour.h); ``1 <= m <= N``.  The HIP kernel on the accelerator (one workgroup per
+    cloud), the same rule as a torch loop for CPU tensors.  The inputs are detached; the outputs are constants of the graph."""
+    xyz, m, start = _fps_args(xyz, m, start)
+    if xyz.device.type == 'cuda':
+        return hip_farthest_point_sample(xyz, m, start, return_distance)
+    return torch_farthest_point_sample(xyz, m, start, return_distance)
+
+
 # ---- gather / edge features / max over k -------------------------------------------------------------------------
 
 

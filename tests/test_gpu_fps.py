@@ -1,0 +1,176 @@
+"""GPU tests of farthest point sampling (``pcc_fps`` through ``neighbour_ops.farthest_point_sample``) against the float64
+greedy reference of tests/fps_reference.py: bit equality where float32 is exact (lattice clouds), validity along the
+GPU's own selection sequence elsewhere (bounds derived in ``fps_reference.check_validity``), every kernel variant against
+the product's choice, batch independence, non-finite input and the argument checks."""
+
+import numpy as np
+import pytest
+import torch
+
+from tests.fps_reference import GENERIC_KINDS, check_validity, fps_reference, generic_cloud, lattice_cloud
+
+pytestmark = pytest.mark.gpu
+
+# fps_path values (include/pcc_test_hooks.h) -> points the variant holds (7: the memory path, any n)
+CAPACITY = {1: 256, 2: 1024, 3: 2048, 4: 4096, 5: 8192, 6: 16384, 7: None}
+
+
+def _fps(x, m, cuda, start=None):
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+
+    x = x if isinstance(x, torch.Tensor) else torch.from_numpy(x)
+    if isinstance(start, (list, np.ndarray)):
+        start = torch.as_tensor(start, dtype=torch.int64).to(cuda)
+    idx, dist = ops.farthest_point_sample(x.to(cuda), m, start=start, return_distance=True)
+    assert idx.dtype == torch.int64 and dist.dtype == torch.float32 and idx.shape == dist.shape == (x.shape[0], m)
+    only = ops.farthest_point_sample(x.to(cuda), m, start=start)
+    assert torch.equal(only, idx)  # (the call without the distance output)
+    return idx.cpu().numpy(), dist.cpu().numpy()
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+def _ms(n):
+    return sorted({1, min(2, n), max(1, n // 3), n})
+
+
+@pytest.mark.parametrize('n', [1, 2, 63, 64, 65, 257, 1023, 1024, 1025, 2049, 5000])
+def test_exact_on_lattices(cuda, n):
+    """Coordinates k/16: float32 is exact, so indices and distances equal the float64 reference bit for bit.  The 4^3
+    lattice is ties and duplicate points everywhere."""
+    for levels in (4, 16):
+        x = lattice_cloud(1000 * levels + n, 3, n, levels)
+        given = np.array([n - 1, n // 2, 0])
+        for start in (None, given):
+            ref_idx, ref_dist = fps_reference(x, n, start)  # (once: the selection for m is a prefix of it)
+            for b in (1, 3):
+                for m in _ms(n):
+                    idx, dist = _fps(x[:b], m, cuda, None if start is None else start[:b])
+                    assert np.array_equal(idx, ref_idx[:b, :m]), (levels, b, m)
+                    assert _same_bits(dist, ref_dist[:b, :m]), (levels, b, m)
+                    assert np.isposinf(dist[:, 0]).all()
+
+
+BOUNDARIES = sorted({65, 1025, 2049} | {c + d for c in CAPACITY.values() if c for d in (-1, 0, 1)})
+
+
+@pytest.mark.parametrize('n', BOUNDARIES)
+def test_every_path_gives_the_same_bits(cuda, n):
+    """Every (block, P) variant that holds n and the memory path against the product's choice, at the sizes just below, at
+    and above every capacity of the table; the product's choice itself against the reference."""
+    from pointcloudcounterfactual_amd import _lib
+
+    for levels in (4, 16):
+        x = lattice_cloud(77 * levels + n, 2, n, levels)
+        start = np.array([n - 1, n // 2])
+        for m in sorted({min(2, n), min(n, 200), n // 3}):
+            base = _fps(x, m, cuda, start)
+            if m <= 200:
+                ref_idx, ref_dist = fps_reference(x, m, start)
+                assert np.array_equal(base[0], ref_idx) and _same_bits(base[1], ref_dist)
+            for path, cap in CAPACITY.items():
+                if cap is not None and cap < n:
+                    continue
+                try:
+                    _lib.set_tuning('fps_path', path)
+                    got = _fps(x, m, cuda, start)
+                finally:
+                    _lib.set_tuning('fps_path', 0)
+                assert np.array_equal(got[0], base[0]) and _same_bits(got[1], base[1]), (levels, m, path)
+
+
+@pytest.mark.parametrize('kind', GENERIC_KINDS)
+def test_valid_on_generic_clouds(cuda, kind):
+    for b, n, m in ((2, 300, 300), (3, 2048, 512), (2, 4100, 1000)):
+        x = generic_cloud(11, b, n, kind)
+        idx, dist = _fps(x, m, cuda)
+        check_validity(x, idx, dist)
+
+
+def test_valid_at_the_workload_cloud_size(cuda):
+    x = generic_cloud(12, 4, 15000, 'gauss')
+    idx, dist = _fps(x, 2048, cuda, [0, 14999, 7, 5000])
+    assert idx[:, 0].tolist() == [0, 14999, 7, 5000]
+    check_validity(x, idx, dist)
+
+
+def test_batch_independence(cuda):
+    n, m = 1025, 400
+    x = generic_cloud(13, 5, n, 'gauss')
+    start = np.array([3, 1, 4, 1, 5])
+    idx, dist = _fps(x, m, cuda, start)
+    again = _fps(x, m, cuda, start)
+    assert np.array_equal(idx, again[0]) and _same_bits(dist, again[1])
+    alone = _fps(x[2:3], m, cuda, start[2:3])
+    assert np.array_equal(alone[0][0], idx[2]) and _same_bits(alone[1][0], dist[2])
+    order = [2, 4, 0, 3, 1]  # cloud 2 in slot 0, and every other cloud in another slot too
+    moved = _fps(x[order], m, cuda, start[order])
+    assert np.array_equal(moved[0], idx[order]) and _same_bits(moved[1], dist[order])
+
+
+def test_non_finite_points_are_excluded(cuda):
+    n, m = 257, 120
+    x = lattice_cloud(14, 3, n, 16)
+    bad = [0, 5, 63, 64, 128, 200, 256]
+    x[0, bad] = [[np.nan, 0, 0], [0, np.inf, 0], [1, 1, -np.inf], [np.nan] * 3, [np.inf, -np.inf, 0], [0, 0, np.nan], [np.inf] * 3]
+    x[1] = np.nan
+    healthy = x[2].copy()
+    # cloud 0 from a NaN start (written as given, updates nothing), the all-NaN cloud 1, the healthy cloud 2 beside them
+    start = np.array([64, 9, 100])
+    idx, dist = _fps(x, m, cuda, start)
+    ref_idx, ref_dist = fps_reference(x, m, start)
+    assert np.array_equal(idx, ref_idx) and _same_bits(dist, ref_dist)
+    assert idx[0, 0] == 64 and np.isnan(dist[0, 0]) and np.isposinf(dist[0, 1])
+    assert not np.isin(idx[0, 1:], bad).any()
+    assert idx[1].tolist() == [9] + [0] * (m - 1) and np.isnan(dist[1]).all()
+    alone = _fps(healthy[None], m, cuda, start[2:])
+    assert np.array_equal(alone[0][0], idx[2]) and _same_bits(alone[1][0], dist[2])
+    # the finite sub-cloud selects what the reference selects on it alone (start at a finite point)
+    keep = np.setdiff1d(np.arange(n), bad)
+    idx, dist = _fps(x[:1], m, cuda, [1])
+    sub_idx, sub_dist = fps_reference(x[:1, keep], m, [0])  # (point 1 is point 0 of the sub-cloud)
+    assert np.array_equal(idx, keep[sub_idx]) and _same_bits(dist, sub_dist)
+    # every variant keeps them out
+    from pointcloudcounterfactual_amd import _lib
+
+    for path in CAPACITY:
+        try:
+            _lib.set_tuning('fps_path', path)
+            got = _fps(x, m, cuda, start)
+        finally:
+            _lib.set_tuning('fps_path', 0)
+        assert np.array_equal(got[0], ref_idx) and _same_bits(got[1], ref_dist), path
+
+
+def test_arguments(cuda):
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+
+    n = 300
+    x = torch.from_numpy(generic_cloud(15, 2, n, 'uniform')).to(cuda)
+    for m in (0, n + 1):
+        with pytest.raises(ValueError):
+            ops.farthest_point_sample(x, m)
+    with pytest.raises(ValueError):
+        ops.farthest_point_sample(x.transpose(1, 2).contiguous(), 4)  # [B,3,N]
+    with pytest.raises(RuntimeError):
+        ops.farthest_point_sample(x.double(), 4)
+    with pytest.raises(RuntimeError, match='must be a CUDA tensor'):
+        ops.farthest_point_sample(x, 4, start=torch.zeros(2, dtype=torch.int64))
+    empty = ops.farthest_point_sample(x[:0], 4, return_distance=True)
+    assert empty[0].shape == (0, 4) and empty[0].dtype == torch.int64 and empty[0].device == x.device and empty[1].shape == (0, 4)
+    big = torch.from_numpy(generic_cloud(16, 2, 2 * n, 'gauss')).to(cuda)
+    view = big[:, ::2, :]
+    assert not view.is_contiguous()
+    assert torch.equal(ops.farthest_point_sample(view, 100), ops.farthest_point_sample(view.contiguous(), 100))
+    # a start outside the cloud is clamped by the kernel (int32 tensors reach it as they are)
+    for dtype in (torch.int32, torch.int64):
+        out = ops.farthest_point_sample(x, 50, start=torch.tensor([-1, n], dtype=dtype, device=cuda))
+        assert out.min() >= 0 and out.max() < n
+        assert torch.equal(out, ops.farthest_point_sample(x, 50, start=torch.tensor([0, n - 1], device=cuda)))
+    assert torch.equal(ops.farthest_point_sample(x, 50, start=n + 7), ops.farthest_point_sample(x, 50, start=n - 1))
+    # the CPU path and the kernel follow one rule
+    cpu = ops.farthest_point_sample(torch.from_numpy(lattice_cloud(17, 2, n, 16)), 60, start=5, return_distance=True)
+    gpu = ops.farthest_point_sample(torch.from_numpy(lattice_cloud(17, 2, n, 16)).to(cuda), 60, start=5, return_distance=True)
+    assert torch.equal(cpu[0], gpu[0].cpu()) and torch.equal(cpu[1], gpu[1].cpu())
