@@ -27,11 +27,8 @@ reference's (``Conv2d(2C, C', 1, bias=False)`` + ``BatchNorm2d(C')``), so state 
 
 from __future__ import annotations
 
-from typing import Any
-
 import torch
 from torch import nn
-from torch.autograd import Function
 
 from pointcloudcounterfactual_amd import _lib
 from pointcloudcounterfactual_amd import neighbour_ops as ops
@@ -41,36 +38,13 @@ _L = _lib.lib
 F32, I64 = torch.float32, torch.int64
 
 
-class _NeighbourSum(Function):
-    """``S[b,c,n] = sum_j y[b,c,idx[b,n,j]]``; backward scatters ``g[b,c,n]`` along every edge."""
-
-    @staticmethod
-    def forward(ctx: Any, y: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-        y = y.contiguous()
-        b, c, n = y.shape
-        k = idx.shape[2]
-        dev = y.device
-        out = torch.empty_like(y)
-        call(_L.pcc_neighbour_sum, 'neighbour_sum', dev, b, c, n, k, ptr(y, 'y', F32, dev), ptr(idx, 'idx', I64, dev),
-             ptr(out, 'out', F32, dev))
-        ctx.save_for_backward(idx)
-        return out
-
-    @staticmethod
-    def backward(ctx: Any, grad: torch.Tensor) -> tuple[torch.Tensor, None]:
-        (idx,) = ctx.saved_tensors
-        grad = grad.contiguous()
-        b, c, n = grad.shape
-        dev = grad.device
-        gy = torch.empty_like(grad)
-        call(_L.pcc_neighbour_sum_bwd, 'neighbour_sum_bwd', dev, b, c, n, idx.shape[2], ptr(idx, 'idx', I64, dev),
-             ptr(grad, 'grad', F32, dev), ptr(gy, 'grad_y', F32, dev))
-        return gy, None
+# ``S[b,c,n] = sum_j y[b,c,idx[b,n,j]]``; backward scatters ``g[b,c,n]`` along every edge
+NEIGHBOUR_SUM = ops.IndexedOp('neighbour_sum', lambda b, c, n, k: (b, c, n), names=('y', 'idx'))
 
 
 def neighbour_sum(y: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if y.device.type == 'cuda':
-        return _NeighbourSum.apply(y, idx.contiguous())
+        return ops.Indexed.apply(NEIGHBOUR_SUM, y, idx.contiguous())
     return ops.get_neighbours(y, idx, idx.shape[2])[1].sum(-1)
 
 

@@ -12,7 +12,7 @@ Layouts are the reference's: ``x[B,C,N]`` float32, ``indices[B,N,k]`` int64 (an 
 
 from __future__ import annotations
 
-from typing import Any
+from typing import Any, Callable, NamedTuple
 
 import torch
 from torch.autograd import Function
@@ -234,86 +234,48 @@ def farthest_point_sample(xyz: torch.Tensor, m: int, start: Any = None, return_d
 # ---- gather / edge features / max over k -------------------------------------------------------------------------
 
 
-class _Gather(Function):
+class IndexedOp(NamedTuple):
+    """One op of ``include/pcc_neighbour.h`` that reads ``x[B,C,N]`` along ``indices[B,N,k]`` and has a backward."""
+
+    what: str  # the C pair is pcc_<what> / pcc_<what>_bwd; also the prefix of their error messages
+    out_shape: Callable[[int, int, int, int], tuple[int, ...]]  # of (b, c, n, k)
+    argmax: bool = False  # an int32 argmax [B,C,N] is produced, saved and handed to the backward
+    names: tuple[str, str] = ('x', 'indices')  # what the pointer checks call the two inputs
+
+
+GATHER = IndexedOp('gather_neighbours', lambda b, c, n, k: (b, c, n, k))
+GRAPH_FEATURES = IndexedOp('graph_features', lambda b, c, n, k: (b, 2 * c, n, k))
+GRAPH_MAX_POOL = IndexedOp('graph_max_pool', lambda b, c, n, k: (b, c, n), argmax=True)
+
+
+class Indexed(Function):
+    """``op`` of ``x`` along ``indices`` on the accelerator, differentiable in ``x``: ``Indexed.apply(op, x, indices)``."""
+
     @staticmethod
-    def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
+    def forward(ctx: Any, op: IndexedOp, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         indices = indices.contiguous()
         b, c, n = x.shape
         k = indices.shape[2]
         dev = x.device
-        out = torch.empty((b, c, n, k), dtype=torch.float32, device=dev)
-        call(_L.pcc_gather_neighbours, 'gather_neighbours', dev, b, c, n, k, ptr(x, 'x', F32, dev),
-             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev))
-        ctx.save_for_backward(indices)
-        ctx.shape = (b, c, n, k)
+        out = torch.empty(op.out_shape(b, c, n, k), dtype=torch.float32, device=dev)
+        arg = (torch.empty((b, c, n), dtype=torch.int32, device=dev),) if op.argmax else ()
+        call(getattr(_L, 'pcc_' + op.what), op.what, dev, b, c, n, k, ptr(x, op.names[0], F32, dev),
+             ptr(indices, op.names[1], I64, dev), ptr(out, 'out', F32, dev), *(ptr(a, 'arg', I32, dev) for a in arg))
+        ctx.save_for_backward(indices, *arg)
+        ctx.op, ctx.shape = op, (b, c, n, k)
         return out
 
     @staticmethod
-    def backward(ctx: Any, grad: torch.Tensor) -> tuple[torch.Tensor, None]:
-        (indices,) = ctx.saved_tensors
-        b, c, n, k = ctx.shape
+    def backward(ctx: Any, grad: torch.Tensor) -> tuple[None, torch.Tensor, None]:
+        indices, *arg = ctx.saved_tensors
+        op, (b, c, n, k) = ctx.op, ctx.shape
         grad = grad.contiguous()
         dev = grad.device
         gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
-        call(_L.pcc_gather_neighbours_bwd, 'gather_neighbours_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
-             ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
-        return gx, None
-
-
-class _GraphFeatures(Function):
-    @staticmethod
-    def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
-        x = x.contiguous()
-        indices = indices.contiguous()
-        b, c, n = x.shape
-        k = indices.shape[2]
-        dev = x.device
-        out = torch.empty((b, 2 * c, n, k), dtype=torch.float32, device=dev)
-        call(_L.pcc_graph_features, 'graph_features', dev, b, c, n, k, ptr(x, 'x', F32, dev),
-             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev))
-        ctx.save_for_backward(indices)
-        ctx.shape = (b, c, n, k)
-        return out
-
-    @staticmethod
-    def backward(ctx: Any, grad: torch.Tensor) -> tuple[torch.Tensor, None]:
-        (indices,) = ctx.saved_tensors
-        b, c, n, k = ctx.shape
-        grad = grad.contiguous()
-        dev = grad.device
-        gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
-        call(_L.pcc_graph_features_bwd, 'graph_features_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
-             ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
-        return gx, None
-
-
-class _GraphMaxPool(Function):
-    @staticmethod
-    def forward(ctx: Any, x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
-        x = x.contiguous()
-        indices = indices.contiguous()
-        b, c, n = x.shape
-        k = indices.shape[2]
-        dev = x.device
-        out = torch.empty((b, c, n), dtype=torch.float32, device=dev)
-        arg = torch.empty((b, c, n), dtype=torch.int32, device=dev)
-        call(_L.pcc_graph_max_pool, 'graph_max_pool', dev, b, c, n, k, ptr(x, 'x', F32, dev),
-             ptr(indices, 'indices', I64, dev), ptr(out, 'out', F32, dev), ptr(arg, 'arg', I32, dev))
-        ctx.save_for_backward(indices, arg)
-        ctx.shape = (b, c, n, k)
-        return out
-
-    @staticmethod
-    def backward(ctx: Any, grad: torch.Tensor) -> tuple[torch.Tensor, None]:
-        indices, arg = ctx.saved_tensors
-        b, c, n, k = ctx.shape
-        grad = grad.contiguous()
-        dev = grad.device
-        gx = torch.empty((b, c, n), dtype=torch.float32, device=dev)
-        call(_L.pcc_graph_max_pool_bwd, 'graph_max_pool_bwd', dev, b, c, n, k, ptr(indices, 'indices', I64, dev),
-             ptr(arg, 'arg', I32, dev), ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_x', F32, dev))
-        return gx, None
+        call(getattr(_L, f'pcc_{op.what}_bwd'), op.what + '_bwd', dev, b, c, n, k, ptr(indices, op.names[1], I64, dev),
+             *(ptr(a, 'arg', I32, dev) for a in arg), ptr(grad, 'grad', F32, dev), ptr(gx, 'grad_' + op.names[0], F32, dev))
+        return None, gx, None
 
 
 class _GlobalMaxPool(Function):
@@ -348,7 +310,7 @@ def get_neighbours(x: torch.Tensor, indices: torch.Tensor, k: int) -> tuple[torc
     if not indices.numel():
         indices = knn(x, k)
     if _on_gpu(x):
-        return indices, _Gather.apply(x, indices.to(x.device))
+        return indices, Indexed.apply(GATHER, x, indices.to(x.device))
     indices_expanded = indices.contiguous().view(batch, 1, k * n_points).expand(-1, n_feat, -1)
     neighbours = torch.gather(x, 2, indices_expanded).view(batch, n_feat, n_points, k)
     return indices, neighbours
@@ -367,7 +329,7 @@ def graph_max_pooling(x: torch.Tensor, indices: torch.Tensor, k: int = 16) -> to
     if _on_gpu(x):
         if not indices.numel():
             indices = knn(x, k)
-        return _GraphMaxPool.apply(x, indices.to(x.device))
+        return Indexed.apply(GRAPH_MAX_POOL, x, indices.to(x.device))
     neighbours = get_neighbours(x, indices, k)[1]
     return torch.max(neighbours, dim=-1)[0]
 
@@ -377,7 +339,7 @@ def get_graph_features(x: torch.Tensor, indices: torch.Tensor, k: int = 20) -> t
     if _on_gpu(x):
         if not indices.numel():
             indices = knn(x, k)
-        return indices, _GraphFeatures.apply(x, indices.to(x.device))
+        return indices, Indexed.apply(GRAPH_FEATURES, x, indices.to(x.device))
     indices_out, neighbours = get_neighbours(x, indices, k)
     xe = x.unsqueeze(3).expand(-1, -1, -1, k)
     return indices_out, torch.cat([neighbours - xe, xe], dim=1).contiguous()
@@ -409,13 +371,8 @@ def global_max_mean_pool(x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         b, c, n = x.shape
         dev = x.device
-        out = torch.empty((b, 2 * c), dtype=torch.float32, device=dev)
-        mx = out[:, :c]
-        mean = torch.empty((b, c), dtype=torch.float32, device=dev)
-        mxc = torch.empty((b, c), dtype=torch.float32, device=dev)
-        call(_L.pcc_global_pool, 'global_pool', dev, b, c, n, ptr(x, 'x', F32, dev), ptr(mxc, 'max', F32, dev), None,
-             ptr(mean, 'mean', F32, dev))
-        mx.copy_(mxc)
-        out[:, c:] = mean
-        return out
+        both = torch.empty((2, b, c), dtype=torch.float32, device=dev)  # max | mean: each the [B,C] block the kernel writes
+        call(_L.pcc_global_pool, 'global_pool', dev, b, c, n, ptr(x, 'x', F32, dev), ptr(both[0], 'max', F32, dev), None,
+             ptr(both[1], 'mean', F32, dev))
+        return both.transpose(0, 1).reshape(b, 2 * c)
     return torch.cat((global_max_pool(x), x.mean(dim=2)), 1)

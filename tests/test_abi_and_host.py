@@ -267,3 +267,46 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     assert cmd[cmd.index('--master-addr') + 1] == '127.0.0.1'
     assert cmd[-6:] == ['--gpus', '4', '--steps', '3', '--warmup', '1'] and cmd[-7].endswith('bench.py')
     assert seen['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
+
+
+# The (b, c, n, k) graph entry points of include/pcc_neighbour.h: name -> (number of REQUIRED pointers, which come first,
+# number of optional ones behind them).
+GRAPH_ENTRIES = {
+    'gather_neighbours': (3, 0), 'graph_features': (3, 0), 'graph_max_pool': (3, 1), 'neighbour_sum': (3, 0),
+    'neighbour_minmax_target': (3, 0), 'gather_neighbours_bwd': (3, 0), 'graph_features_bwd': (3, 0),
+    'graph_max_pool_bwd': (4, 0), 'neighbour_sum_bwd': (3, 0),
+}
+PCC_OK, PCC_EINVAL = 0, -22
+
+
+def test_graph_entry_points_check_sizes_and_pointers_before_any_launch():
+    """Every graph entry point refuses bad sizes and a NULL required pointer with ``PCC_EINVAL`` and its own message,
+    and accepts an empty batch or cloud, before it touches the device (all of these return ahead of the first HIP call,
+    so the pointers may be dummies).  The optional pointers (``argmax`` of ``pcc_graph_max_pool``, the three outputs of
+    ``pcc_global_pool``) are NULL throughout and never the reason for a refusal."""
+    from pointcloudcounterfactual_amd import _lib
+
+    L = _lib.lib
+    dummy = 0x1000  # never dereferenced
+
+    def status_and_error(fn, *args):
+        rc = fn(*args, None)  # (default stream)
+        return rc, L.pcc_last_error().decode()
+
+    for name, (required, optional) in GRAPH_ENTRIES.items():
+        fn = getattr(L, 'pcc_' + name)
+        ptrs = [dummy] * required + [None] * optional
+        for b, c, n, k in ((1, 0, 4, 2), (70000, 1, 4, 2), (1, 1, 65536, 32768)):
+            assert status_and_error(fn, b, c, n, k, *ptrs) == (PCC_EINVAL, f'{name}: bad size'), (name, b, c, n, k)
+        for missing in range(required):
+            args = [None if i == missing else p for i, p in enumerate(ptrs)]
+            assert status_and_error(fn, 1, 1, 4, 2, *args) == (PCC_EINVAL, f'{name}: null pointer'), (name, missing)
+        for b, n in ((0, 4), (1, 0)):
+            assert status_and_error(fn, b, 1, n, 2, *ptrs) == (PCC_OK, ''), (name, b, n)
+            assert status_and_error(fn, b, 1, n, 2, *[None] * len(ptrs)) == (PCC_OK, ''), (name, b, n)
+
+    pool = L.pcc_global_pool
+    assert status_and_error(pool, 1, 1, 0, dummy, None, None, None) == (PCC_EINVAL, 'global_pool: bad size')
+    assert status_and_error(pool, 1, 1, 4, None, None, None, None) == (PCC_EINVAL, 'global_pool: null pointer')
+    assert status_and_error(pool, 0, 1, 4, dummy, None, None, None)[0] == PCC_OK
+    assert status_and_error(pool, 1, 0, 4, dummy, None, None, None)[0] == PCC_OK
