@@ -1,6 +1,6 @@
 // Spatial sort of the point clouds for gfx950 (MI355X), wave64: Hilbert key, register bitonic sort, sorted rows, the
 // inverse permutation and one bounding box per 16 sorted points.  Both clouds of an approximate-EMD call are sorted once
-// per call (approxmatch.hip skips exact zeros box by box); the k-NN graph sorts its clouds with the same kernel (knn.hip).
+// per call (approxmatch.hip skips exact zeros box by box); the k-NN graph sorts its clouds with the same kernel (knn_lowdim.hip).
 #include "approxmatch.hpp"
 #include "wave_ops.hpp"
 
@@ -386,7 +386,7 @@ int sort_clouds(const AmDims &L, const WsView &v, int bc, const float *xyz1, con
     return pcc::check_launch("approxmatch(sort)");
 }
 
-// Hilbert sort of ONE channels-major cloud per sample (x[b][c][n], 1 <= c <= 3) for the k-NN graph (knn.hip): packed
+// Hilbert sort of ONE channels-major cloud per sample (x[b][c][n], 1 <= c <= 3) for the k-NN graph (knn_lowdim.hip): packed
 // sorted rows (x, y, z, original index), the 16-point boxes and the sorted -> original permutation.
 int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st) {
     SortArgs a{};

@@ -1,6 +1,6 @@
-// k-NN graph for the calls outside the box of knn.hip's kernels (k > 32, or c > 128), gfx950, wave64.
+// k-NN graph for the calls outside the box of the kernels of knn_lowdim.hip and knn_mfma.hip (k > 32, or c > 128), gfx950, wave64.
 //
-// Same formulas, same rounding and the same ordering contract as knn.hip (include/pcc_neighbour.h):
+// Same formulas, same rounding and the same ordering contract as those kernels (include/pcc_neighbour.h):
 //   * c <= 3: difference form sum_c (x_j - x_i)^2 as an fma chain over the channels, computed inside the selection
 //     kernel (exhaustive scan);
 //   * c >= 4: expanded form (-2*dot + |x_j|^2) + |x_i|^2.  knn_wide_dist_kernel computes the inner products of a block of
@@ -23,7 +23,7 @@
 // (distance bits : candidate index), so the result does not depend on the number of slices.
 #include <algorithm>
 
-#include "pcc_common.hpp"
+#include "knn.hpp"
 #include "pcc_neighbour.h"
 #include "pcc_test_hooks.h"
 #include "wave_sort.hpp"
@@ -31,7 +31,6 @@
 namespace {
 
 typedef unsigned long long u64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr u64 kWideKeyMax = ~0ull;                          // empty slot: above every key of a real candidate
 constexpr size_t kWideRowsBytes = (size_t)256 << 20;        // distance workspace per launch pair
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(256) void knn_wide_dist_kernel(int c, int n, int nq
 
     f32x16 acc[4];
 #pragma unroll
-    for (int u = 0; u < 4; u++) acc[u] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < 4; u++) acc[u] = zero16();
     fetch(0);
     commit(0, 0);
     __syncthreads();
@@ -148,6 +147,7 @@ struct WideSelArgs {
 };
 
 constexpr int kSelW = 4;  // waves (= queries) per selection workgroup
+constexpr int wide_slots(int k) { return k <= 64 ? 64 : 128; }  // list slots L of the selection instantiation for k
 
 // L = list slots (64 or 128, >= k).  One wave per query (per query and slice when the candidate axis is cut, with the
 // list going to a.part instead of the outputs); kSrcKeys selects among the keys of a query's slice lists.  See the file
@@ -277,7 +277,7 @@ void launch_select(const WideSelArgs &a, hipStream_t st) {
 
 template <int SRC>
 void launch_select(const WideSelArgs &a, hipStream_t st) {
-    if (a.k <= 64) launch_select<64, SRC>(a, st);
+    if (wide_slots(a.k) == 64) launch_select<64, SRC>(a, st);
     else launch_select<128, SRC>(a, st);
 }
 
@@ -304,8 +304,7 @@ int select_rows(WideSelArgs a, int slices, hipStream_t st) {
         return pcc::check_launch("knn(wide select)");
     }
     pcc::WsBlock part(st);
-    const int L = a.k <= 64 ? 64 : 128;
-    if (int rc = part.alloc((size_t)a.rows * a.slices * L * sizeof(u64), "knn: workspace allocation failed")) return rc;
+    if (int rc = part.alloc((size_t)a.rows * a.slices * wide_slots(a.k) * sizeof(u64), "knn: workspace allocation failed")) return rc;
     a.part = static_cast<u64 *>(part.p);
     launch_select<SRC>(a, st);
     if (int rc = pcc::check_launch("knn(wide select)")) return rc;
@@ -374,11 +373,8 @@ int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipSt
 extern "C" int pcc_knn_cross(int b, int c, int nq, int n, int k, const float *q, const float *x, int64_t *indices, float *dist,
                              pcc_stream_t stream) {
     pcc::clear_error();
-    if (b < 0 || c < 1 || nq < 0 || n < 0 || k < 1) return pcc::invalid("knn_cross: bad size");
-    if (b == 0 || nq == 0) return PCC_OK;
-    if (k > n) return pcc::invalid("knn_cross: k exceeds the number of candidates (torch.topk raises too)");
-    if (k > 128) return pcc::invalid("knn_cross: k > 128 is not supported");
-    if (b > 65535) return pcc::invalid("knn_cross: batch too large");
+    bool empty;
+    if (int rc = knn_check_sizes("knn_cross", "candidates", b, c, nq, n, k, &empty); rc || empty) return rc;
     if ((long long)b * nq > 0x7fffffffLL) return pcc::invalid("knn_cross: too many queries (b * nq >= 2^31)");
     if (c >= 4 && n > 65535 * kDT) return pcc::invalid("knn_cross: too many candidates for c >= 4 (n > 65535 * 128)");
     if (!q || !x || !indices) return pcc::invalid("knn_cross: null pointer");

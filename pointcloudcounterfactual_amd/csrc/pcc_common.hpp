@@ -122,17 +122,11 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
 }
 
-// Hilbert sort of one channels-major cloud per sample (cloud_sort.hip's am_sort_kernel) for the k-NN graph: aos [b][n]
+// Hilbert sort of one channels-major cloud per sample (cloud_sort.hip's am_sort_kernel) for the k-NN graph
+// (knn_lowdim.hip; the other declarations the k-NN files share are in knn.hpp): aos [b][n]
 // (x, y, z, original index as bits), box16 [b][ceil(n/kBox)][8] (lo xyz, pad, hi xyz, pad), perm [b][n] sorted -> original.
 constexpr int kBox = 16;  // points per bounding-box block (sorted order)
 int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *box16, int *perm, hipStream_t st);
-
-// k-NN graph outside the range of knn.hip's kernels (knn_wide.hip): any c >= 1, 1 <= k <= min(n, 128); sizes and
-// pointers already validated by pcc_knn.
-int knn_wide(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st);
-
-// sq[b][n] = sum_c x[b][c][n]^2 as one fma chain in channel order (the oracle's |x_j|^2; knn.hip's sqnorm_kernel)
-void launch_sqnorm(int b, int c, int n, const float *x, float *sq, hipStream_t st);
 
 // true while `st` is being captured into a graph (a failed query counts as not capturing)
 bool capturing(hipStream_t st);

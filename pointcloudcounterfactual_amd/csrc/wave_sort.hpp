@@ -1,4 +1,4 @@
-// Wave-level helpers of the k-NN and nearest-neighbour searches (knn.hip, knn_wide.hip, nn_sorted.hip), gfx950 wave64.
+// Wave-level helpers of the k-NN and nearest-neighbour searches (knn_lowdim.hip, knn_wide.hip, nn_sorted.hip), gfx950 wave64.
 #pragma once
 #include "pcc_common.hpp"
 #include "wave_ops.hpp"

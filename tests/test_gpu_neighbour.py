@@ -166,6 +166,25 @@ def test_knn_mfma_vs_oracle(cuda, oracle_mod, b, c, n, k, kernel):
     assert np.array_equal(idx, exp)
 
 
+@pytest.mark.parametrize('c,k', [(4, 1), (8, 4), (9, 5), (16, 8), (17, 9), (32, 16), (33, 17), (64, 20), (65, 21), (128, 25),
+                                 (5, 26), (128, 32)])
+@pytest.mark.parametrize('kernel', [1, 2])
+def test_knn_mfma_instantiation_choice(cuda, oracle_mod, c, k, kernel):
+    """Which instantiation the host picks: both sides of every padded-channel class (8 | 16 | 32 | 64 | 128; the role-split
+    kernel starts at 16) and of every list-slot boundary (4 | 8 | 16 | 20 | 25 | 32), in both kernels.  n = 130: two
+    128-query workgroups, the second nearly empty; one 256-query workgroup, half padding; five 32-candidate stages, the
+    last partial."""
+    from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
+
+    x = _x(c * 131 + k, 2, c, 130)
+    _lib.set_tuning('knn_nosplit', kernel)
+    try:
+        idx = ops.knn(x.to(cuda), k).cpu().numpy()
+    finally:
+        _lib.set_tuning('knn_nosplit', 0)
+    assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), k))
+
+
 def test_knn_mfma_many_small_clouds_take_the_role_split_kernel(cuda, oracle_mod):
     """A batch of many small clouds fills the chip with 256-query workgroups that are mostly padding (40 of 256 queries,
     two stages): the product's own dispatch, no switch."""
