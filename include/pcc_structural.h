@@ -128,6 +128,36 @@ int pcc_chamfer_emd_grad(int b, int n, const float *xyz1, int m, const float *xy
 int pcc_chamfer_matrix(int s, int n, const float *a, int r, int m, const float *bank, int mean, float *d_ab,
                        float *d_ba, pcc_stream_t stream);
 
+/* ---- voxel occupancy counts of a bank of clouds (extension) ------------------------------------------
+ * What the Jensen-Shannon divergence between two SETS of clouds is computed from (the fourth number of the MMD / COV /
+ * 1-NNA table), and per cloud what voxel IoU and density checks need.
+ *   xyz[s,n,3] -> counts[res^3] (per_cloud == 0: the whole bank in one histogram) or counts[s,res^3] (per_cloud != 0);
+ *   counts[cell] = the number of points whose cell it is.  counts is overwritten: the call zeroes what it must, on `stream`.
+ * Grid: res points per axis on [lo, lo + extent]^3; grid point (i,j,k) sits at lo + i extent / (res - 1) on each axis and
+ *   has the flat index (i res + j) res + k.
+ * Cell of a finite point, full grid (in_sphere == 0): per axis, in float32 with exactly these roundings,
+ *   t = (x - lo) * inv with inv = (float)(res - 1) / extent computed once on the host (subtract and multiply are two
+ *   roundings: the library is built with -ffp-contract=off), i = (int)fminf(fmaxf(floorf(t + 0.5f), 0.f), (float)(res - 1)).
+ *   The clamp is applied to floats, before the conversion.  This is the nearest grid point up to one rounding at a cell
+ *   border (a midpoint goes up); a point outside the cube lands in a border cell, as a nearest-neighbour query puts it.
+ * in_sphere != 0: only grid points inside the inscribed sphere count, tested in integers:
+ *   (2i - (res-1))^2 + (2j - (res-1))^2 + (2k - (res-1))^2 <= (res-1)^2.  A point whose separable cell passes keeps it.  Any
+ *   other point goes to its nearest in-sphere grid point, found column by column: for each (i,j) whose in-sphere interval
+ *   [klo, khi] is not empty the candidate is k = the point's separable k clamped into the interval (the distance is convex
+ *   in k), at distance pcc::sq3(px - gx, py - gy, pz - gz) = fmaf(dz,dz, fmaf(dx,dx, dy*dy)) with g = (float)index * step +
+ *   lo (two roundings) and step = extent / (float)(res - 1); the lowest float32 distance wins, the lowest flat index among
+ *   equal distances.
+ * Non-finite points: a point with a NaN or infinite coordinate is counted nowhere; the counts sum to the number of finite
+ *   points.
+ * Determinism: integer adds only, so the counts are identical for every launch geometry, from run to run, and between
+ *   the library's two paths (a workgroup-private histogram in LDS for res <= 32, one global atomic per point above).
+ * Sizes: s >= 0 (s == 0 enqueues nothing), n >= 1, 2 <= res <= 128 (res >= 3 with in_sphere: at res 2 no grid point
+ *   qualifies), extent finite and > 0, lo finite, s n <= INT_MAX, per_cloud: s res^3 <= INT_MAX; otherwise PCC_EINVAL, before
+ *   anything is enqueued.  No host synchronisation; may be captured into a graph; with in_sphere the call takes
+ *   4 (s n + 4) bytes of stream-ordered workspace (PCC_ENOMEM if that fails). */
+int pcc_occupancy_grid(int s, int n, const float *xyz, int res, float lo, float extent, int in_sphere, int per_cloud,
+                       int32_t *counts, pcc_stream_t stream);
+
 /* ---- approximate EMD ---------------------------------------------------------------------------
  * Replaces `approxmatch` (reference approxmatch.cu:299-307; declared structural_loss.cpp:10).
  *   xyz1[b,n,3], xyz2[b,m,3] -> match[b,m,n] (query-major), temp[b,2(n+m)] =

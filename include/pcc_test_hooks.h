@@ -33,8 +33,11 @@ enum {
     PCC_TUNE_KNN_NOSPLIT = 8,      /* c >= 4 k-NN: 1 = the 128-query kernel everywhere, 2 = the role-split kernel everywhere */
     PCC_TUNE_KNN_WIDE = 9,         /* k-NN: 1 = every call through the wide path (knn_wide.hip), also where k <= 32, c <= 128 */
     PCC_TUNE_KNN_CROSS_SPLIT = 10, /* pcc_knn_cross: S >= 1 = the candidate axis in S slices (1 = one wave per query); 0 = by the row count */
-    PCC_TUNE_FPS_PATH = 11         /* pcc_fps: 1..6 = the register variant (block, P) = (64,4) (256,4) (256,8) (512,8) (1024,8) (1024,16), 7 = the
+    PCC_TUNE_FPS_PATH = 11,        /* pcc_fps: 1..6 = the register variant (block, P) = (64,4) (256,4) (256,8) (512,8) (1024,8) (1024,16), 7 = the
                                       memory path; a variant that cannot hold n is ignored */
+    PCC_TUNE_OCCUPANCY_PATH = 12,  /* pcc_occupancy_grid: 1 = the global-atomic path everywhere, 2 = the LDS-histogram path (ignored where
+                                      res^3 counters do not fit the workgroup's LDS, res > 32) */
+    PCC_TUNE_KEYS = 16             /* keys are 0 .. PCC_TUNE_KEYS - 1 */
 };
 int pcc_test_set_tuning(int key, int value);
 

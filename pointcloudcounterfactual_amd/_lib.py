@@ -40,6 +40,7 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_chamfer_emd': (_int, [_int, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_chamfer_emd_grad': (_int, [_int, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     'pcc_chamfer_matrix': (_int, [_int, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    'pcc_occupancy_grid': (_int, [_int, _int, _vp, _int, ctypes.c_float, ctypes.c_float, _int, _int, _vp, _vp]),
     'approxmatch': (None, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_approxmatch': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_approxmatch_workspace_bytes': (ctypes.c_size_t, [_int, _int, _int]),
@@ -132,7 +133,7 @@ def call(fn: Any, what: str, device: torch.device, *args: Any) -> None:
 
 # include/pcc_test_hooks.h: measurement / bit-identity switches (inert unless PCC_TEST_HOOKS=1 is in the environment)
 TUNING = {'am_nocull': 2, 'am_nosplit': 3, 'am_noresident': 4, 'edge_scatter': 5, 'nbrsum_scatter': 6,
-          'auction_cluster': 7, 'knn_nosplit': 8, 'knn_wide': 9, 'knn_cross_split': 10, 'fps_path': 11}
+          'auction_cluster': 7, 'knn_nosplit': 8, 'knn_wide': 9, 'knn_cross_split': 10, 'fps_path': 11, 'occupancy_path': 12}
 
 
 def set_tuning(name: str, value: int) -> None:

@@ -13,8 +13,10 @@ thread_local int t_status = 0;
 thread_local char t_msg[320] = "";
 }  // namespace
 
+#include "pcc_test_hooks.h"
 namespace {
-int g_tuning[16] = {};
+int g_tuning[PCC_TUNE_KEYS] = {};
+static_assert(PCC_TUNE_OCCUPANCY_PATH < PCC_TUNE_KEYS, "a tuning key outside the table");
 }
 
 namespace pcc {
@@ -34,7 +36,7 @@ int device_cus() {
     return v;
 }
 
-int tuning(int key) { return key >= 0 && key < 16 ? __atomic_load_n(&g_tuning[key], __ATOMIC_RELAXED) : 0; }
+int tuning(int key) { return key >= 0 && key < PCC_TUNE_KEYS ? __atomic_load_n(&g_tuning[key], __ATOMIC_RELAXED) : 0; }
 void set_error(int status, const char *what) {
     t_status = status;
     std::strncpy(t_msg, what ? what : "", sizeof t_msg - 1);
@@ -235,7 +237,7 @@ static bool hooks_armed() {
     return armed;
 }
 extern "C" int pcc_test_set_tuning(int key, int value) {
-    if (!hooks_armed() || key < 0 || key >= 16) return 0;
+    if (!hooks_armed() || key < 0 || key >= PCC_TUNE_KEYS) return 0;
     __atomic_store_n(&g_tuning[key], value, __ATOMIC_RELAXED);
     return 1;
 }

@@ -1,6 +1,7 @@
 """Scoring a generated SET of clouds against a reference set: all-pairs Chamfer / approximate-EMD matrices and the
 three set metrics built on them -- minimum matching distance (MMD), coverage (COV) and leave-one-out 1-nearest-neighbour
-accuracy (1-NNA).
+accuracy (1-NNA) -- and the one set metric that needs no distance matrix: the Jensen-Shannon divergence (JSD) between the
+voxel-occupancy distributions of the two sets (``occupancy_grid``, ``jsd_between_sets``).
 
 The losses in ``losses`` are paired (sample ``b`` against sample ``b``); these metrics need the distance between EVERY
 generated cloud and EVERY reference cloud.  ``pairwise_chamfer`` computes that ``[S,R]`` matrix with one kernel
@@ -13,6 +14,8 @@ columns, so ties are real, and ``torch.min`` on the GPU does not promise which i
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 from pointcloudcounterfactual_amd import _lib, backend
@@ -20,6 +23,8 @@ from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
 F32 = torch.float32
+I32 = torch.int32
+I64 = torch.int64
 
 # pcc_match_cost numbers the samples of a call in the 12 bits its failure report has for them, and launches its finish
 # kernel with the batch on grid.y: pair batches stay at or below 4095.
@@ -176,11 +181,155 @@ def one_nn_accuracy(d_ss: torch.Tensor, d_sr: torch.Tensor, d_rr: torch.Tensor) 
     return {'acc': (tp + tn).to(full.dtype) / (s + r), 'tp': tp, 'fp': fp, 'fn': fn, 'tn': tn}
 
 
-def compute_all_metrics(sample: torch.Tensor, ref: torch.Tensor,
-                        pairs_per_call: int = DEFAULT_PAIRS_PER_CALL) -> dict[str, torch.Tensor]:
+# ---- voxel occupancy and the Jensen-Shannon divergence between two sets ---------------------------------------------
+
+MAX_RESOLUTION = 128  # pcc_occupancy_grid's range
+
+
+def _grid_args(resolution: int, in_sphere: bool, lo: float, extent: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The checks ``pcc_occupancy_grid`` makes on the grid, before anything is enqueued -> the float32 scalars of the
+    rule ``(lo, inv, step)``, rounded as the library rounds them."""
+    if isinstance(resolution, bool) or not isinstance(resolution, int) or not 2 <= resolution <= MAX_RESOLUTION:
+        raise ValueError(f'resolution must be an int in [2, {MAX_RESOLUTION}], got {resolution!r}')
+    if in_sphere and resolution < 3:
+        raise ValueError('in_sphere needs resolution >= 3: at resolution 2 no grid point lies inside the sphere')
+    lo32, extent32 = torch.tensor(float(lo), dtype=F32), torch.tensor(float(extent), dtype=F32)
+    top = torch.tensor(float(resolution - 1), dtype=F32)
+    inv, step = top / extent32, extent32 / top
+    if not (math.isfinite(extent32.item()) and extent32.item() > 0 and math.isfinite(inv.item()) and inv.item() > 0 and step.item() > 0):
+        raise ValueError(f'extent must be finite and > 0, got {extent!r}')
+    if not math.isfinite(lo32.item()):
+        raise ValueError(f'lo must be finite, got {lo!r}')
+    return lo32, inv, step
+
+
+def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """``fmaf(a, b, c)`` of float32 tensors with ``a b >= 0`` and ``c >= 0``, exactly.  The product is exact in float64; the
+    float64 sum is rounded TO ODD (its rounding error comes from the two-sum), after which the rounding to float32 is the
+    one rounding of the fused operation -- a plain float64 sum would round twice."""
+    p, c = a.double() * b.double(), c.double()
+    s = p + c
+    t = s - p
+    err = (p - (s - t)) + (c - t)  # the exact sum is s + err
+    bits = s.view(I64)
+    odd = (torch.where(err < 0, bits - 1, bits) | 1).view(torch.float64)  # truncate towards 0 (s > 0 here), then the sticky bit
+    return torch.where(torch.isfinite(s) & (err != 0), odd, s).float()
+
+
+def _in_sphere_columns(res: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The columns ``(i, j)`` that hold an in-sphere grid point, in flat order -> ``(i, j, klo)``; the interval of a
+    column is ``[klo, res - 1 - klo]``.  Integers only."""
+    r1 = res - 1
+    a = 2 * torch.arange(res, dtype=I64) - r1
+    rem = r1 * r1 - a[:, None] ** 2 - a[None, :] ** 2  # (2k - r1)^2 <= rem
+    m = rem.clamp(min=0).double().sqrt().floor().to(I64)
+    m = m - (m * m > rem).to(I64)
+    m = m + ((m + 1) * (m + 1) <= rem).to(I64)  # floor(sqrt(rem)), settled in integers
+    klo = (res - m) >> 1  # ceil((r1 - m) / 2)
+    ci, cj = ((rem >= 0) & (klo <= r1 - klo)).nonzero(as_tuple=True)
+    return ci, cj, klo[ci, cj]
+
+
+def _nearest_in_sphere(points: torch.Tensor, ks: torch.Tensor, res: int, lo32: torch.Tensor, step: torch.Tensor) -> torch.Tensor:
+    """The column rule of ``pcc_occupancy_grid`` for ``points[P,3]`` with separable ``k`` index ``ks[P]`` -> flat cells."""
+    ci, cj, klo = _in_sphere_columns(res)
+    grid = torch.arange(res, dtype=F32) * step + lo32  # g = (float)index * step + lo: two roundings
+    out = torch.empty(points.size(0), dtype=I64)
+    for p0 in range(0, points.size(0), 2048):
+        p = points[p0:p0 + 2048]
+        k = torch.minimum(torch.maximum(ks[p0:p0 + 2048, None], klo[None, :]), (res - 1 - klo)[None, :])
+        dx, dy, dz = p[:, 0:1] - grid[ci][None, :], p[:, 1:2] - grid[cj][None, :], p[:, 2:3] - grid[k]
+        d = _fma32(dz, dz, _fma32(dx, dx, dy * dy))  # pcc::sq3
+        flat = ((ci * res + cj) * res)[None, :] + k
+        nearest = d == d.min(1, keepdim=True).values
+        out[p0:p0 + 2048] = torch.where(nearest, flat, res ** 3).min(1).values  # lowest index among equal distances
+    return out
+
+
+def _occupancy_host(clouds: torch.Tensor, res: int, in_sphere: bool, per_cloud: bool, lo32: torch.Tensor, inv: torch.Tensor,
+                    step: torch.Tensor) -> torch.Tensor:
+    """The rule of ``pcc_occupancy_grid`` in torch: the same float32 operations in the same order, then ``bincount``."""
+    s, n = clouds.shape[:2]
+    bins = res ** 3
+    points = clouds.reshape(-1, 3)
+    finite = torch.isfinite(points).all(1)
+    cloud = torch.arange(s).repeat_interleave(n)[finite]
+    points = points[finite]
+    ijk = torch.floor((points - lo32) * inv + 0.5).clamp(0.0, float(res - 1)).to(I64)
+    flat = (ijk[:, 0] * res + ijk[:, 1]) * res + ijk[:, 2]
+    if in_sphere:
+        outside = ((2 * ijk - (res - 1)) ** 2).sum(1) > (res - 1) ** 2
+        flat[outside] = _nearest_in_sphere(points[outside], ijk[outside, 2], res, lo32, step)
+    if per_cloud:
+        return torch.bincount(cloud * bins + flat, minlength=s * bins).view(s, res, res, res)
+    return torch.bincount(flat, minlength=bins).view(res, res, res)
+
+
+def occupancy_grid(clouds: torch.Tensor, resolution: int = 28, in_sphere: bool = False, per_cloud: bool = False,
+                   lo: float = -0.5, extent: float = 1.0) -> torch.Tensor:
+    """Voxel occupancy counts of the clouds ``clouds[S,N,3]`` float32 on the grid of ``resolution`` points per axis over
+    ``[lo, lo + extent]^3`` (the defaults: PointFlow's 28^3 grid on the unit cube) -> int64 ``[res,res,res]``, the number
+    of points of the whole bank nearest to each grid point, or with ``per_cloud`` ``[S,res,res,res]``, one histogram per
+    cloud.  ``in_sphere``: only the grid points inside the inscribed sphere count and every point goes to the nearest of
+    those.  A point outside the cube lands in a border cell; a point with a NaN or infinite coordinate is counted nowhere,
+    so the counts sum to the number of finite points.
+
+    The rule, rounding by rounding, is ``pcc_occupancy_grid``'s (include/pcc_structural.h).  GPU tensors run that
+    kernel; CPU tensors the same float32 operations in torch, so both give the same integers.  Integer adds only: the
+    result does not depend on the schedule or on the order of clouds and points."""
+    _check_bank(clouds, 'clouds')
+    lo32, inv, step = _grid_args(resolution, in_sphere, lo, extent)
+    if clouds.dtype != F32:
+        raise RuntimeError(f'clouds must be {F32}, found {clouds.dtype}')
+    clouds = clouds.detach()
+    s, n, res = clouds.size(0), clouds.size(1), resolution
+    shape = (s, res, res, res) if per_cloud else (res, res, res)
+    if s == 0:
+        return torch.zeros(shape, dtype=I64, device=clouds.device)
+    if clouds.device.type != 'cuda':
+        return _occupancy_host(clouds, res, bool(in_sphere), bool(per_cloud), lo32, inv, step)
+    dev = clouds.device
+    clouds = clouds.contiguous()
+    xp = ptr(clouds, 'clouds', F32, dev)
+    counts = torch.empty(shape, dtype=I32, device=dev)
+    call(_L.pcc_occupancy_grid, 'occupancy_grid', dev, s, n, xp, res, float(lo), float(extent), int(bool(in_sphere)),
+         int(bool(per_cloud)), ptr(counts, 'counts', I32, dev))
+    return counts.to(I64)
+
+
+def _entropy_bits(p: torch.Tensor) -> torch.Tensor:
+    positive = p > 0
+    return -torch.where(positive, p * torch.log2(torch.where(positive, p, torch.ones_like(p))), torch.zeros_like(p)).sum()
+
+
+def jsd_from_counts(p_counts: torch.Tensor, q_counts: torch.Tensor) -> torch.Tensor:
+    """Jensen-Shannon divergence, base 2, between the distributions ``P``, ``Q`` two count tensors of one shape stand for:
+    ``H(M) - (H(P) + H(Q)) / 2`` with ``M = (P + Q) / 2`` and ``0 log 0 = 0``, in float64 on the counts' device, in
+    ``[0, 1]``.  ``ValueError`` for counts that sum to 0."""
+    if p_counts.shape != q_counts.shape:
+        raise ValueError(f'the count tensors differ in shape: {tuple(p_counts.shape)} and {tuple(q_counts.shape)}')
+    totals = p_counts.sum().item(), q_counts.sum().item()
+    if min(totals) <= 0:
+        raise ValueError('a set without a finite point has no occupancy distribution')
+    p, q = p_counts.reshape(-1).double() / totals[0], q_counts.reshape(-1).double() / totals[1]
+    jsd = _entropy_bits((p + q) / 2) - (_entropy_bits(p) + _entropy_bits(q)) / 2
+    return jsd.clamp(0.0, 1.0)
+
+
+def jsd_between_sets(sample: torch.Tensor, ref: torch.Tensor, resolution: int = 28, in_sphere: bool = True) -> torch.Tensor:
+    """Jensen-Shannon divergence between the voxel-occupancy distributions of the generated clouds ``sample[S,N,3]`` and
+    the reference clouds ``ref[R,M,3]`` on the unit-cube grid of ``occupancy_grid`` (Achlioptas et al. / PointFlow:
+    28^3 grid points, those inside the inscribed sphere) -> a float64 scalar tensor in ``[0, 1]``: 0 for equal
+    distributions, 1 for sets that share no cell.  One pass over the points; no distance matrix.  Symmetric, and
+    invariant to the order of clouds and points, bit for bit.  ``ValueError`` if a set has no finite point."""
+    return jsd_from_counts(occupancy_grid(sample, resolution, in_sphere), occupancy_grid(ref, resolution, in_sphere))
+
+
+def compute_all_metrics(sample: torch.Tensor, ref: torch.Tensor, pairs_per_call: int = DEFAULT_PAIRS_PER_CALL,
+                        with_jsd: bool = False) -> dict[str, torch.Tensor]:
     """``sample[S,N,3]`` generated clouds, ``ref[R,M,3]`` reference clouds (GPU) -> ``MMD-CD``, ``COV-CD``,
     ``1-NNA-CD``, ``MMD-EMD``, ``COV-EMD``, ``1-NNA-EMD`` from the six distance matrices (the two Chamfer self matrices
-    through the self mode of ``pairwise_chamfer``)."""
+    through the self mode of ``pairwise_chamfer``); ``with_jsd`` adds ``JSD`` = ``jsd_between_sets(sample, ref)``."""
     def emd(x: torch.Tensor, y: torch.Tensor | None = None) -> torch.Tensor:
         return pairwise_emd(x, y, pairs_per_call=pairs_per_call)
 
@@ -191,4 +340,6 @@ def compute_all_metrics(sample: torch.Tensor, ref: torch.Tensor,
         out[f'MMD-{tag}'] = scores['mmd']
         out[f'COV-{tag}'] = scores['cov']
         out[f'1-NNA-{tag}'] = one_nn_accuracy(pairwise(sample), d_sr, pairwise(ref))['acc']
+    if with_jsd:
+        out['JSD'] = jsd_between_sets(sample, ref)
     return out
