@@ -72,6 +72,30 @@ int pcc_knn_cross(int b, int c, int nq, int n, int k, const float *q, const floa
  * on the kernel variant that ran. */
 int pcc_fps(int b, int n, int m, const float *xyz, const int32_t *start, int64_t *idx, float *dist, pcc_stream_t stream);
 
+/* Ball query: for every centre centres[b, i] (centres[b, m, 3], point-major float32 like xyz and like pcc_fps; centres may
+ * alias xyz) the points of xyz[b, n, 3] inside the open ball of `radius` around it, capped at nsample: idx[b, m, nsample]
+ * into xyz and, when cnt is non-null, cnt[b, m].  No counterpart in the reference; the query between pcc_fps and a gather
+ * in a sampling-and-grouping pipeline.
+ *   distance    d is pcc_knn's c <= 3 form with the centre as the query: df = xyz[j] - centres[i] per coordinate,
+ *               acc = df0 * df0, acc = fmaf(df1, df1, acc), acc = fmaf(df2, df2, acc).
+ *   membership  r2 = radius * radius, one float32 multiplication; point j is inside iff d < r2.  The comparison is strict
+ *               (a point on the sphere is outside), so a NaN d is never inside, and neither is a d of +inf: a point or a
+ *               centre with a non-finite coordinate has no neighbours and is nobody's neighbour.
+ *   selection   the first nsample inside points in ascending index order; cnt[b,i] = min(number inside, nsample): counting
+ *               stops at nsample, and so may the scan.
+ *   padding     of the slots s >= cnt[b,i]: pad = PCC_BALL_PAD_FIRST: idx[b,i,s] = idx[b,i,0], and index 0 when the ball
+ *               is empty (the set-abstraction convention: every slot is an in-range index and can be gathered without a
+ *               mask); pad = PCC_BALL_PAD_NONE: -1.
+ * Requires n >= 1, nsample >= 1 (it may exceed n), radius > 0 (NaN, 0 and negative: PCC_EINVAL; +inf is allowed: every
+ * point at a finite distance is inside, and so is every radius whose square overflows), pad 0 or 1, b <= 65535,
+ * b * m < 2^31, non-null xyz, centres and idx (PCC_EINVAL otherwise); b = 0 or m = 0 enqueues nothing and returns PCC_OK.
+ * 64-bit offsets throughout, no workspace.  A query's row depends on its cloud, its centre, radius, nsample and pad only:
+ * not on b, m, its position in the batch or the kernel variant that ran.  A gather of xyz[b, :, idx[b, i, :]] for m != n is
+ * left to the caller (torch.gather): pcc_gather_neighbours takes one index row per point of the cloud it reads. */
+enum { PCC_BALL_PAD_FIRST = 0, PCC_BALL_PAD_NONE = 1 };
+int pcc_ball_query(int b, int n, int m, int nsample, float radius, int pad, const float *xyz, const float *centres,
+                   int64_t *idx, int32_t *cnt, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

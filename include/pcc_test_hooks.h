@@ -37,6 +37,8 @@ enum {
                                       memory path; a variant that cannot hold n is ignored */
     PCC_TUNE_OCCUPANCY_PATH = 12,  /* pcc_occupancy_grid: 1 = the global-atomic path everywhere, 2 = the LDS-histogram path (ignored where
                                       res^3 counters do not fit the workgroup's LDS, res > 32) */
+    PCC_TUNE_BALL_PATH = 13,       /* pcc_ball_query: 1, 2 = candidates from global memory, 4 / 16 queries per workgroup; 3, 4 = candidates
+                                      staged through LDS, 4 queries x tiles of 1024 / 16 queries x tiles of 4096 (the product's choice) */
     PCC_TUNE_KEYS = 16             /* keys are 0 .. PCC_TUNE_KEYS - 1 */
 };
 int pcc_test_set_tuning(int key, int value);

@@ -40,11 +40,7 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return (__float_as_uint(x) & e) != e && (__float_as_uint(y) & e) != e && (__float_as_uint(z) & e) != e;
 }
 
-// pcc_knn's c <= 3 distance of x_j to the selected point (include/pcc_neighbour.h)
-__device__ __forceinline__ float sqdist(float x, float y, float z, float sx, float sy, float sz) {
-    const float d0 = x - sx, d1 = y - sy, d2 = z - sz;
-    return __builtin_fmaf(d2, d2, __builtin_fmaf(d1, d1, d0 * d0));
-}
+using pcc::sqdist;  // pcc_knn's c <= 3 distance of x_j to the selected point (include/pcc_neighbour.h)
 
 __device__ __forceinline__ u64 fps_key(float mind, unsigned j) {
     if (mind == kPad) return 0;

@@ -43,6 +43,13 @@ __device__ __forceinline__ float sq3(float x, float y, float z) {
     return __builtin_fmaf(z, z, __builtin_fmaf(x, x, y * y));
 }
 
+// pcc_knn's c <= 3 distance of the point (x, y, z) to (sx, sy, sz): df = x - s per coordinate, acc = df0 * df0, then
+// fmaf(df, df, acc) in coordinate order (include/pcc_neighbour.h: pcc_knn, pcc_fps, pcc_ball_query).
+__device__ __forceinline__ float sqdist(float x, float y, float z, float sx, float sy, float sz) {
+    const float d0 = x - sx, d1 = y - sy, d2 = z - sz;
+    return __builtin_fmaf(d2, d2, __builtin_fmaf(d1, d1, d0 * d0));
+}
+
 // A/B switches for measurements inside ONE process (include/pcc_test_hooks.h: pcc_test_set_tuning; inert without
 // PCC_TEST_HOOKS=1): the value of switch `key` (0 = the product's behaviour).
 int tuning(int key);

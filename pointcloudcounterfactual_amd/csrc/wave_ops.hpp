@@ -68,6 +68,12 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
     return ((unsigned long long)hi << 32) | lo;
 }
 
+// How many lanes below this one have their bit set in `mask` (a __ballot): the slot of a lane that appends to a list
+// the wave fills in lane order (v_mbcnt_lo / v_mbcnt_hi).
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
 // Maximum of a 64-bit key: over the 16 lanes of a row in every lane of the row (the tree of row_reduce16, both halves of
 // the key through DPP), and over the wave as a wave-uniform value (the four row results read back with v_readlane).
 template <int CTRL>

@@ -12,12 +12,14 @@ Layouts are the reference's: ``x[B,C,N]`` float32, ``indices[B,N,k]`` int64 (an 
 
 from __future__ import annotations
 
+import numbers
 from typing import Any, Callable, NamedTuple
 
 import torch
 from torch.autograd import Function
 
 from pointcloudcounterfactual_amd import _lib
+from pointcloudcounterfactual_amd._float32 import fma32
 from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
@@ -229,6 +231,94 @@ def farthest_point_sample(xyz: torch.Tensor, m: int, start: Any = None, return_d
     if xyz.device.type == 'cuda':
         return hip_farthest_point_sample(xyz, m, start, return_distance)
     return torch_farthest_point_sample(xyz, m, start, return_distance)
+
+
+# ---- ball query -------------------------------------------------------------------------------------------------------
+
+BALL_PAD = {'first': 0, 'none': 1}  # PCC_BALL_PAD_FIRST / PCC_BALL_PAD_NONE (include/pcc_neighbour.h)
+
+
+def _ball_args(xyz: torch.Tensor, centres: torch.Tensor, radius: Any, nsample: int, pad: str) -> tuple[torch.Tensor, torch.Tensor, float, int]:
+    """The checks ``ball_query`` makes before anything runs: ``(xyz detached, centres detached, radius as the float32 the
+    library receives, pad as the C constant)``."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < 1:
+        raise ValueError(f'ball_query: expected xyz[B,N,3] with N >= 1, got {tuple(xyz.shape)}')
+    if centres.dim() != 3 or centres.shape[2] != 3 or centres.shape[0] != xyz.shape[0]:
+        raise ValueError(f'ball_query: expected centres[B = {xyz.shape[0]},M,3], got {tuple(centres.shape)}')
+    for name, t in (('xyz', xyz), ('centres', centres)):
+        if t.dtype != F32:
+            raise RuntimeError(f'{name} must be {F32}, found {t.dtype}')
+    if centres.device != xyz.device:
+        if xyz.device.type == 'cuda' and centres.device.type != 'cuda':
+            raise RuntimeError('centres must be a CUDA tensor')
+        raise RuntimeError(f'centres is on {centres.device}, expected {xyz.device}')
+    if isinstance(nsample, bool) or not isinstance(nsample, int) or nsample < 1:
+        raise ValueError(f'ball_query: nsample must be an int >= 1, got {nsample!r}')
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+        raise ValueError(f'ball_query: radius must be a real number > 0, got {radius!r}')
+    r32 = torch.tensor(float(radius), dtype=F32).item()  # (what the C ABI's float parameter receives)
+    if not r32 > 0:
+        raise ValueError(f'ball_query: radius must be > 0 (as a float32), got {radius!r}')
+    if not isinstance(pad, str) or pad not in BALL_PAD:
+        raise ValueError(f"ball_query: pad must be 'first' or 'none', got {pad!r}")
+    return xyz.detach(), centres.detach(), r32, BALL_PAD[pad]
+
+
+def torch_ball_query(xyz: torch.Tensor, centres: torch.Tensor, radius: float, nsample: int, pad: int = 0,
+                     return_count: bool = False) -> Any:
+    """The rule of ``pcc_ball_query`` (include/pcc_neighbour.h) in torch, roundings included (``fma32`` is the kernel's
+    ``fmaf``); CPU path of ``ball_query``.  ``pad`` is the C constant."""
+    b, n, _ = xyz.shape
+    m = centres.shape[1]
+    dev = xyz.device
+    r32 = torch.tensor(radius, dtype=F32, device=dev)
+    r2 = r32 * r32  # one float32 multiplication
+    idx = torch.zeros((b, m, nsample), dtype=I64, device=dev)
+    cnt = torch.zeros((b, m), dtype=I32, device=dev)
+    step = max(1, (1 << 21) // max(1, b * n))  # queries per block: about 2M distances at a time
+    for m0 in range(0, m, step):
+        df = xyz[:, None, :, :] - centres[:, m0:m0 + step, None, :]
+        d = df[..., 0] * df[..., 0]
+        d = fma32(df[..., 1], df[..., 1], d)
+        d = fma32(df[..., 2], df[..., 2], d)
+        inside = d < r2  # (false for a NaN distance)
+        rank = inside.cumsum(-1)
+        bb, ii, jj = (inside & (rank <= nsample)).nonzero(as_tuple=True)
+        idx[bb, m0 + ii, rank[bb, ii, jj] - 1] = jj  # (ascending j along a row)
+        cnt[:, m0:m0 + step] = rank[..., -1].clamp(max=nsample).to(I32)
+    fill = idx[..., :1] if pad == BALL_PAD['first'] else torch.full((b, m, 1), -1, dtype=I64, device=dev)
+    idx = torch.where(torch.arange(nsample, device=dev) < cnt[..., None], idx, fill)
+    return (idx, cnt) if return_count else idx
+
+
+def hip_ball_query(xyz: torch.Tensor, centres: torch.Tensor, radius: float, nsample: int, pad: int = 0,
+                   return_count: bool = False) -> Any:
+    """``pcc_ball_query`` on checked arguments (``_ball_args``)."""
+    dev = xyz.device
+    xyz, centres = xyz.contiguous(), centres.contiguous()
+    b, n, _ = xyz.shape
+    m = centres.shape[1]
+    xp, cp = ptr(xyz, 'xyz', F32, dev), ptr(centres, 'centres', F32, dev)  # (checked before anything is allocated on the device)
+    idx = torch.empty((b, m, nsample), dtype=I64, device=dev)
+    cnt = torch.empty((b, m), dtype=I32, device=dev) if return_count else None
+    call(_L.pcc_ball_query, 'ball_query', dev, b, n, m, nsample, radius, pad, xp, cp, ptr(idx, 'idx', I64, dev),
+         ptr(cnt, 'cnt', I32, dev))
+    return (idx, cnt) if return_count else idx
+
+
+def ball_query(xyz: torch.Tensor, centres: torch.Tensor, radius: float, nsample: int, pad: str = 'first',
+               return_count: bool = False) -> Any:
+    """For every centre of ``centres[B,M,3]`` the first ``nsample`` points (ascending index) of ``xyz[B,N,3]`` strictly
+    inside the ball of ``radius`` around it: ``idx[B,M,nsample]`` int64 into ``xyz`` and, with ``return_count``,
+    ``cnt[B,M]`` int32 = min(points inside, nsample).  Slots past ``cnt`` repeat the row's first index (``pad='first'``;
+    index 0 for an empty ball: every slot can be gathered without a mask) or hold -1 (``pad='none'``).  Both tensors are
+    float32; ``centres`` may be ``xyz``.  The full contract is ``pcc_ball_query``'s (include/pcc_neighbour.h).  The HIP
+    kernel on the accelerator (one wave per centre, stops as soon as the row is full), the same float32 rule in torch for
+    CPU tensors: the two agree word for word.  The inputs are detached; the outputs are constants of the graph."""
+    xyz, centres, radius, pad_c = _ball_args(xyz, centres, radius, nsample, pad)
+    if xyz.device.type == 'cuda':
+        return hip_ball_query(xyz, centres, radius, nsample, pad_c, return_count)
+    return torch_ball_query(xyz, centres, radius, nsample, pad_c, return_count)
 
 
 # ---- gather / edge features / max over k -------------------------------------------------------------------------

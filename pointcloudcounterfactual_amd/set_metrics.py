@@ -19,6 +19,7 @@ import math
 import torch
 
 from pointcloudcounterfactual_amd import _lib, backend
+from pointcloudcounterfactual_amd._float32 import fma32 as _fma32
 from pointcloudcounterfactual_amd._lib import call, ptr
 
 _L = _lib.lib
@@ -201,19 +202,6 @@ def _grid_args(resolution: int, in_sphere: bool, lo: float, extent: float) -> tu
     if not math.isfinite(lo32.item()):
         raise ValueError(f'lo must be finite, got {lo!r}')
     return lo32, inv, step
-
-
-def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
-    """``fmaf(a, b, c)`` of float32 tensors with ``a b >= 0`` and ``c >= 0``, exactly.  The product is exact in float64; the
-    float64 sum is rounded TO ODD (its rounding error comes from the two-sum), after which the rounding to float32 is the
-    one rounding of the fused operation -- a plain float64 sum would round twice."""
-    p, c = a.double() * b.double(), c.double()
-    s = p + c
-    t = s - p
-    err = (p - (s - t)) + (c - t)  # the exact sum is s + err
-    bits = s.view(I64)
-    odd = (torch.where(err < 0, bits - 1, bits) | 1).view(torch.float64)  # truncate towards 0 (s > 0 here), then the sticky bit
-    return torch.where(torch.isfinite(s) & (err != 0), odd, s).float()
 
 
 def _in_sphere_columns(res: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
