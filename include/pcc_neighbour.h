@@ -90,11 +90,40 @@ int pcc_fps(int b, int n, int m, const float *xyz, const int32_t *start, int64_t
  * point at a finite distance is inside, and so is every radius whose square overflows), pad 0 or 1, b <= 65535,
  * b * m < 2^31, non-null xyz, centres and idx (PCC_EINVAL otherwise); b = 0 or m = 0 enqueues nothing and returns PCC_OK.
  * 64-bit offsets throughout, no workspace.  A query's row depends on its cloud, its centre, radius, nsample and pad only:
- * not on b, m, its position in the batch or the kernel variant that ran.  A gather of xyz[b, :, idx[b, i, :]] for m != n is
- * left to the caller (torch.gather): pcc_gather_neighbours takes one index row per point of the cloud it reads. */
+ * not on b, m, its position in the batch or the kernel variant that ran.  pcc_group_points gathers along the list, either
+ * pad included (pcc_gather_neighbours cannot: it takes one index row per point of the cloud it reads). */
 enum { PCC_BALL_PAD_FIRST = 0, PCC_BALL_PAD_NONE = 1 };
 int pcc_ball_query(int b, int n, int m, int nsample, float radius, int pad, const float *xyz, const float *centres,
                    int64_t *idx, int32_t *cnt, pcc_stream_t stream);
+
+/* Grouping: the gather along an index list that belongs to another point set, idx[b, m, k] int64 into a cloud of n points
+ * (m != n allowed): the lists of pcc_ball_query around the centres of pcc_fps, or of pcc_knn_cross.  No counterpart in the
+ * reference; what a user writes in torch instead is an expanded index tensor, a gather per input, a subtraction and a cat.
+ *   layouts     point_major = 0: x[b, c, n], centre[b, c, m], grad_x[b, c, n], grad_centre[b, c, m] (the feature layout of
+ *               the graph ops); point_major = 1: x[b, n, c], centre[b, m, c] and the gradients alike (the xyz layout of
+ *               pcc_fps, pcc_ball_query and the losses).  out and grad_out are always channels-major [b, out_c, m, k], and a
+ *               call touches their channels out_c0 .. out_c0 + c - 1 only: two calls fill one [b, 3 + C, m, k] tensor
+ *               without a cat, and the backward reads its slice of the gradient in place.
+ *   forward     out[b, out_c0 + ch, i, j] = x[b, ch, idx[b, i, j]], a copy of the float's bits (NaN payloads included); with
+ *               a non-null centre x[b, ch, idx[b, i, j]] - centre[b, ch, i], one float32 subtraction.  A slot whose index
+ *               is outside [0, n) (the -1 of PCC_BALL_PAD_NONE) is +0.0 in both modes.
+ *   backward    grad_x[b, ch, t] = sum of grad_out[b, out_c0 + ch, i, j] over the slots with idx[b, i, j] == t; every
+ *               element of grad_x is written, +0.0 where nothing points.  grad_centre[b, ch, i] = -(sum over the in-range
+ *               slots j of grad_out[b, out_c0 + ch, i, j]), summed in a fixed order.  A slot outside [0, n) carries no
+ *               gradient to either.  Either gradient pointer may be null; with both null nothing is enqueued.  grad_x is
+ *               accumulated with float atomics (LDS bins, or global memory where a cloud's bins do not fit LDS) after the
+ *               runs of equal consecutive indices have been summed inside a wave: like pcc_gather_neighbours_bwd and
+ *               torch's scatter_add, the float summation order of grad_x is not fixed.
+ * Requires c >= 1, n >= 1, k >= 1, m >= 0, 0 <= out_c0, out_c0 + c <= out_c, point_major 0 or 1, b <= 65535,
+ * m * k < 2^31 and non-null x, idx, out / idx, grad_out (PCC_EINVAL otherwise, under "group_points:" /
+ * "group_points_bwd:"); centre may be null.  b = 0 enqueues nothing and returns PCC_OK; m = 0: the forward enqueues nothing,
+ * the backward zero-fills grad_x.  64-bit offsets throughout, no workspace, and no n is refused: where not even one channel
+ * row of a cloud fits a workgroup's LDS (n > 40960) the gathers and the atomics go to global memory.  A row of the output
+ * depends on its cloud, its index row and its centre only: not on b, m, its position in the batch or the variant that ran. */
+int pcc_group_points(int b, int c, int n, int m, int k, int point_major, const float *x, const int64_t *idx,
+                     const float *centre, float *out, int out_c, int out_c0, pcc_stream_t stream);
+int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, const int64_t *idx, const float *grad_out,
+                         int out_c, int out_c0, float *grad_x, float *grad_centre, pcc_stream_t stream);
 
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,

@@ -39,7 +39,9 @@ enum {
                                       res^3 counters do not fit the workgroup's LDS, res > 32) */
     PCC_TUNE_BALL_PATH = 13,       /* pcc_ball_query: 1, 2 = candidates from global memory, 4 / 16 queries per workgroup; 3, 4 = candidates
                                       staged through LDS, 4 queries x tiles of 1024 / 16 queries x tiles of 4096 (the product's choice) */
-    PCC_TUNE_KEYS = 16             /* keys are 0 .. PCC_TUNE_KEYS - 1 */
+    PCC_TUNE_GROUP_PATH = 14,      /* pcc_group_points / _bwd: 1 = the LDS path (ignored where not one channel row of n points fits a
+                                      workgroup's LDS), 2 = the direct path (global gathers, global float atomics) */
+    PCC_TUNE_KEYS = 16            /* keys are 0 .. PCC_TUNE_KEYS - 1 */
 };
 int pcc_test_set_tuning(int key, int value);
 

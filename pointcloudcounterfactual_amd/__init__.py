@@ -14,8 +14,14 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     nn_distance,
     torch_chamfer,
 )
-from pointcloudcounterfactual_amd.neighbour_ops import ball_query, farthest_point_sample  # noqa: F401
+from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
+    ball_query,
+    farthest_point_sample,
+    group_points,
+    sample_and_group,
+)
 from pointcloudcounterfactual_amd.set_metrics import jsd_between_sets, occupancy_grid  # noqa: F401
 
 __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer', 'MatchCostFunction', 'NNDistanceFunction',
-           'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'occupancy_grid', 'jsd_between_sets']
+           'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'group_points', 'sample_and_group',
+           'occupancy_grid', 'jsd_between_sets']

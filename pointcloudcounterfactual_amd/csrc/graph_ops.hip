@@ -5,6 +5,7 @@
 // index-driven copies; the kernels keep every global access coalesced along the (n,k) axis and reuse one index
 // load for all channels of a block; the backward scatter accumulates into per-workgroup LDS bins (no global
 // atomics).
+#include "chan_block.hpp"
 #include "pcc_common.hpp"
 #include "wave_ops.hpp"
 
@@ -59,18 +60,13 @@ struct NbrList {
 //              (what the fused EdgeConv needs: the edge that survives max-over-k for either sign of the BN scale)
 constexpr int kGather = 0, kFeatures = 1, kMaxPool = 2, kNbrSum = 3, kMinMax = 4;
 
-// The CB channels of one sample a workgroup owns: sample `smp`, channels c0 .. c0 + CB - 1 (those below c exist).
-// One-dimensional launch, sample-major on XCD-contiguous ids: the channel blocks of a sample share an L2 (they all
-// stream the sample's index list; side by side on eight XCDs each would fetch it over the fabric).
-struct ChanBlock {
-    int smp, c0;
-};
-template <int CB>
-__device__ __forceinline__ ChanBlock chan_block(int c) {
-    const int nblk = (c + CB - 1) / CB, lid = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
-    const int smp = lid / nblk;
-    return {smp, (lid - smp * nblk) * CB};
-}
+// (the channel blocks, their LDS budget and the choice of CB: chan_block.hpp, shared with grouping.hip)
+using pcc::chan_block;
+using pcc::dispatch_cb;
+using pcc::fit_cb;
+using pcc::kLdsHalfCu;
+using pcc::kLdsWg;
+using pcc::kLdsWgDyn;
 
 // The n counts in cur[] become their exclusive prefix sums (the write cursors of a counting sort), copied to start[] too
 // if START.  Every thread of a 1024-thread workgroup calls it, between two barriers of its own: after the counts are
@@ -714,26 +710,6 @@ __global__ __launch_bounds__(256) void global_pool_kernel(int rows, int n, const
         if (argmax) argmax[row] = bi == 0x7fffffff ? 0 : bi;
         if (out_mean) out_mean[row] = sum / (float)n;
     }
-}
-
-// LDS per workgroup, in bytes: all of a CU's; that less room for a kernel's static LDS; and the rows or bins of a
-// workgroup where two should share a CU
-constexpr size_t kLdsWg = 160 * 1024, kLdsWgDyn = kLdsWg - 256, kLdsHalfCu = 64 * 1024;
-
-// channels per workgroup: the largest CB in {cb_max, cb_max / 2, ..., 1} of which `row_bytes` each fit `bytes` (1 if none does)
-int fit_cb(int cb_max, size_t row_bytes, size_t bytes = kLdsHalfCu) {
-    int cb = cb_max;
-    while (cb > 1 && cb * row_bytes > bytes) cb >>= 1;
-    return cb;
-}
-
-// f(std::integral_constant<int, cb>) for cb a power of two <= CB_MAX
-template <int CB_MAX = 8, class F>
-void dispatch_cb(int cb, F &&f) {
-    if constexpr (CB_MAX > 1) {
-        if (cb < CB_MAX) return dispatch_cb<CB_MAX / 2>(cb, f);
-    }
-    f(std::integral_constant<int, CB_MAX>{});
 }
 
 template <int MODE>
