@@ -7,9 +7,10 @@ object has not been built (``python -c "import __graft_entry__ as g; g.build()"`
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
-from typing import Any
+from typing import Any, Iterator
 
 # torch FIRST: libpcc_structural.so needs libamdhip64.so.7, and the process must end up with ONE HIP runtime.  With
 # torch imported before the library is loaded, the loader resolves that name to the runtime torch already brought in
@@ -144,3 +145,14 @@ def set_tuning(name: str, value: int) -> None:
     """Set a measurement switch of the library (0 = the product's behaviour); raises if the hooks are not armed."""
     if lib.pcc_test_set_tuning(TUNING[name], int(value)) != 1:
         raise RuntimeError('test hooks are not armed: set PCC_TEST_HOOKS=1 before the library is loaded')
+
+
+@contextlib.contextmanager
+def tuning(name: str, value: int) -> Iterator[None]:
+    """``set_tuning(name, value)`` for the body of a ``with``; back to 0 behind it, whether or not the body raised: a
+    switch left set would reach every call the process makes afterwards."""
+    set_tuning(name, value)
+    try:
+        yield
+    finally:
+        set_tuning(name, 0)

@@ -49,11 +49,11 @@ inline int check_sizes(const char *who, int b, int n, int m) {
 
 // n == 0 or m == 0: the sums are empty, so cost[b] and the gradients that have elements are 0 (null: not requested)
 inline int zero_fill_empty(int b, int n, int m, float *cost, float *grad1, float *grad2, hipStream_t st, const char *what) {
-    hipError_t e = hipSuccess;
-    if (cost) e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st);
-    if (n && grad1 && e == hipSuccess) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(float), st);
-    if (m && grad2 && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(float), st);
-    return e == hipSuccess ? PCC_OK : (pcc::set_error((int)e, what), (int)e);
+    int rc = PCC_OK;
+    if (cost) rc = pcc::zero_async(cost, (size_t)b * sizeof(float), st, what);
+    if (n && grad1 && !rc) rc = pcc::zero_async(grad1, (size_t)b * n * 3 * sizeof(float), st, what);
+    if (m && grad2 && !rc) rc = pcc::zero_async(grad2, (size_t)b * m * 3 * sizeof(float), st, what);
+    return rc;
 }
 
 }  // namespace

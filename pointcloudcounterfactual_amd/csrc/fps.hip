@@ -35,11 +35,7 @@ struct Winner {
     float x, y, z;
 };
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    const unsigned e = 0x7f800000u;
-    return (__float_as_uint(x) & e) != e && (__float_as_uint(y) & e) != e && (__float_as_uint(z) & e) != e;
-}
-
+using pcc::finite3;
 using pcc::sqdist;  // pcc_knn's c <= 3 distance of x_j to the selected point (include/pcc_neighbour.h)
 
 __device__ __forceinline__ u64 fps_key(float mind, unsigned j) {

@@ -11,7 +11,6 @@
 
 #include <cstdlib>
 #include <initializer_list>
-#include <string>
 #include <type_traits>
 #include "pcc_neighbour.h"
 #include "pcc_test_hooks.h"
@@ -427,10 +426,6 @@ __host__ __device__ inline int es_run_len(int cnt) {  // entries one wave walks:
     return ((cnt + kEsWaves - 1) / kEsWaves + 63) & ~63;
 }
 
-__device__ __forceinline__ float es_keep(float u, unsigned f, int bit) {  // u if bit `bit` of f is set, +0 otherwise
-    return __int_as_float(__float_as_int(u) & -(int)((f >> bit) & 1u));
-}
-
 __global__ __launch_bounds__(1024) void edge_chunk_sort_kernel(int n, int k, int P, const int64_t *__restrict__ indices,
                                                                 unsigned *__restrict__ ent, unsigned char *__restrict__ flg) {
     extern __shared__ __attribute__((aligned(16))) int es_lds[];  // start[n] | cur[n] | key[kEsCE]
@@ -577,26 +572,15 @@ __global__ __launch_bounds__(kEsT, 8) void edge_stream_bwd_kernel(int c, int n, 
                     const unsigned kp = kp_r[gi], f = f_r[gi];
                     const int t = valid ? (int)(kp >> 13) : -2;
                     const int el = (int)(kp & 8191u) % kEsCE;  // (an invalid lane reads a harmless in-range address)
+                    // segmented inclusive prefix sum over the 64 lanes (pcc::seg_prefix_sum): a lane adds at step s iff bit s
+                    // of its flag says the partner belongs to the same target
+                    auto same = [f](int s) { return -(int)((f >> s) & 1u); };
+                    const pcc::SegMasks seg = {same(0), same(1), same(2), same(3), same(4), same(5)};
                     float v[CB];
 #pragma unroll
                     for (int cc = 0; cc < CB; cc++) v[cc] = valid ? buf[(size_t)cc * kEsCE + el] : 0.f;
 #pragma unroll
-                    for (int cc = 0; cc < CB; cc++) {
-                        // segmented inclusive prefix sum over the 64 lanes with cross-lane VALU operands (row_shr 1 2 4 8,
-                        // row_bcast 15 into rows 1 and 3, row_bcast 31 into rows 2 and 3); a lane adds at a step iff its flag
-                        // says the partner belongs to the same target
-                        // (the partner's value is taken by ALL lanes and then masked with bit arithmetic: written as a
-                        // select, the compiler moves the DPP move under the flag's exec mask, and a lane whose own flag is
-                        // clear then is an inactive -- invalid -- source for its neighbour)
-                        float x = v[cc];
-                        x += es_keep(pcc::dpp<pcc::kRowShr + 1>(x), f, 0);
-                        x += es_keep(pcc::dpp<pcc::kRowShr + 2>(x), f, 1);
-                        x += es_keep(pcc::dpp<pcc::kRowShr + 4>(x), f, 2);
-                        x += es_keep(pcc::dpp<pcc::kRowShr + 8>(x), f, 3);
-                        x += es_keep(pcc::dpp<pcc::kRowBcast15, 0xa>(x), f, 4);
-                        x += es_keep(pcc::dpp<pcc::kRowBcast31, 0xc>(x), f, 5);
-                        v[cc] = x;
-                    }
+                    for (int cc = 0; cc < CB; cc++) v[cc] = pcc::seg_prefix_sum(v[cc], seg);
                     // the segment left open by the previous group of this run continues at the head of this one
                     const bool head = t == carry_t;
                     const int t63 = __builtin_amdgcn_readlane(t, 63);              // (wave-uniform: scalar registers)
@@ -828,10 +812,10 @@ template <class Run>
 int graph_entry(const char *name, int b, int c, int n, int k, std::initializer_list<const void *> required, Run &&run) {
     pcc::clear_error();
     if (b < 0 || c < 1 || n < 0 || k < 1 || b > 65535 || (long long)n * k > 0x7fffffffLL)
-        return pcc::invalid((std::string(name) + ": bad size").c_str());
+        return pcc::invalidf("%s: bad size", name);
     if (b == 0 || n == 0) return PCC_OK;
     for (const void *p : required)
-        if (!p) return pcc::invalid((std::string(name) + ": null pointer").c_str());
+        if (!p) return pcc::invalidf("%s: null pointer", name);
     return run();
 }
 

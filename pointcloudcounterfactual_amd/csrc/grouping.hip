@@ -151,11 +151,6 @@ __global__ __launch_bounds__(kT) void group_fwd_kernel(int c, int n, int m, int 
     }
 }
 
-// u if keep is all ones, +0 if it is 0.  Bit arithmetic and not a select: written as a select the compiler moves the DPP
-// move under the flag's exec mask, and a lane whose own flag is clear is then an inactive -- invalid -- source for its
-// neighbour (the same care as in edge_stream_bwd_kernel).
-__device__ __forceinline__ float keep_if(float u, int keep) { return __int_as_float(__float_as_int(u) & keep); }
-
 // Backward of the gather: grad_x[smp, c0 + cc, t] += g[smp, out_c0 + c0 + cc, e] over the slots e with idx[e] == t.
 // LDS path: the bins of the unit live in LDS (zeroed, ds_add_f32, written out whole: every element of grad_x is
 // written); direct path: global atomics into grad_x, zero-filled by the host.  Either way the 64 consecutive slots of a
@@ -192,23 +187,12 @@ __global__ __launch_bounds__(kT) void group_bwd_kernel(int c, int n, int m, int 
             const int tp = __shfl_up(t, 1, 64);
             const unsigned long long heads = __ballot(lane == 0 || tp != t);
             const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
-            const int k1 = -(int)(lr >= 1 && lane - 1 >= head), k2 = -(int)(lr >= 2 && lane - 2 >= head);
-            const int k4 = -(int)(lr >= 4 && lane - 4 >= head), k8 = -(int)(lr >= 8 && lane - 8 >= head);
-            const int k15 = -(int)((lane & 16) != 0 && lane - lr - 1 >= head), k31 = -(int)(lane >= 32 && 31 >= head);
+            const pcc::SegMasks runs = {-(int)(lr >= 1 && lane - 1 >= head), -(int)(lr >= 2 && lane - 2 >= head),
+                                        -(int)(lr >= 4 && lane - 4 >= head), -(int)(lr >= 8 && lane - 8 >= head),
+                                        -(int)((lane & 16) != 0 && lane - lr - 1 >= head), -(int)(lane >= 32 && 31 >= head)};
             const bool tail = t >= 0 && (lane == 63 || ((heads >> ((lane + 1) & 63)) & 1ull) != 0);
 #pragma unroll
-            for (int cc = 0; cc < CB; cc++) {
-                // segmented inclusive prefix sum over the wave: row_shr 1 2 4 8 inside the rows of 16 lanes, then lane 15 /
-                // 47 into the next row, then lane 31 into the upper half
-                float s = v[cc];
-                s += keep_if(pcc::dpp<pcc::kRowShr + 1>(s), k1);
-                s += keep_if(pcc::dpp<pcc::kRowShr + 2>(s), k2);
-                s += keep_if(pcc::dpp<pcc::kRowShr + 4>(s), k4);
-                s += keep_if(pcc::dpp<pcc::kRowShr + 8>(s), k8);
-                s += keep_if(pcc::dpp<pcc::kRowBcast15, 0xa>(s), k15);
-                s += keep_if(pcc::dpp<pcc::kRowBcast31, 0xc>(s), k31);
-                v[cc] = s;
-            }
+            for (int cc = 0; cc < CB; cc++) v[cc] = pcc::seg_prefix_sum(v[cc], runs);
             if (tail) {
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++) {
@@ -283,8 +267,7 @@ Plan make_plan(int b, int c, int n, unsigned mk, bool split_lds) {
     const long long blocks = (long long)b * pcc::ceil_div(c, p.cb);
     long long want = 1;
     if (!p.lds || split_lds) {
-        const int cus = pcc::device_cus() > 0 ? pcc::device_cus() : 256;
-        want = (2LL * cus + blocks - 1) / blocks;  // two workgroups per compute unit
+        want = (2LL * pcc::device_cus_or(256) + blocks - 1) / blocks;  // two workgroups per compute unit
         const long long most = (mk + kMinChunk - 1) / kMinChunk;
         want = want < most ? want : most;
         want = want < 1 ? 1 : want;
@@ -297,16 +280,12 @@ Plan make_plan(int b, int c, int n, unsigned mk, bool split_lds) {
 
 int check_sizes(const char *name, int b, int c, int n, int m, int k, int point_major, int out_c, int out_c0) {
     pcc::clear_error();
-    char buf[96];
-    auto fail = [&](const char *what) {
-        std::snprintf(buf, sizeof buf, "%s: %s", name, what);
-        return pcc::invalid(buf);
-    };
-    if (b < 0 || c < 1 || n < 1 || m < 0 || k < 1) return fail("bad size");
-    if (b > 65535) return fail("batch too large");
-    if ((long long)m * k > 0x7fffffffLL) return fail("list too long (m * k >= 2^31)");
-    if (out_c0 < 0 || (long long)out_c0 + c > out_c) return fail("channels out_c0 .. out_c0 + c - 1 are not inside out_c");
-    if (point_major != 0 && point_major != 1) return fail("point_major must be 0 or 1");
+    if (b < 0 || c < 1 || n < 1 || m < 0 || k < 1) return pcc::invalidf("%s: bad size", name);
+    if (b > 65535) return pcc::invalidf("%s: batch too large", name);
+    if ((long long)m * k > 0x7fffffffLL) return pcc::invalidf("%s: list too long (m * k >= 2^31)", name);
+    if (out_c0 < 0 || (long long)out_c0 + c > out_c)
+        return pcc::invalidf("%s: channels out_c0 .. out_c0 + c - 1 are not inside out_c", name);
+    if (point_major != 0 && point_major != 1) return pcc::invalidf("%s: point_major must be 0 or 1", name);
     return PCC_OK;
 }
 
@@ -342,10 +321,9 @@ int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, con
     if (b == 0 || (!grad_x && !grad_centre)) return PCC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t gx_bytes = (size_t)b * c * n * sizeof(float);
-    if (m == 0) {  // an empty list: nothing points anywhere
-        if (grad_x && hipMemsetAsync(grad_x, 0, gx_bytes, st) != hipSuccess) return pcc::check_launch("group_points_bwd");
-        return PCC_OK;
-    }
+    const char *cannot_zero = "group_points_bwd: cannot zero grad_x";
+    if (m == 0)  // an empty list: nothing points anywhere
+        return grad_x ? pcc::zero_async(grad_x, gx_bytes, st, cannot_zero) : PCC_OK;
     if (!idx || !grad_out) return pcc::invalid("group_points_bwd: null pointer");
     if (grad_x) {
         const Plan p = make_plan(b, c, n, (unsigned)m * (unsigned)k, false);
@@ -357,7 +335,7 @@ int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, con
                                    point_major, p.units, p.nsplit, p.chunk, idx, grad_out, out_c, out_c0, grad_x);
             });
         } else {
-            if (hipMemsetAsync(grad_x, 0, gx_bytes, st) != hipSuccess) return pcc::check_launch("group_points_bwd");
+            if (int rc = pcc::zero_async(grad_x, gx_bytes, st, cannot_zero)) return rc;
             pcc::ProfScope prof("group_bwd_kernel<direct>", st);
             hipLaunchKernelGGL((group_bwd_kernel<kCbDirect, true>), dim3(p.grid()), dim3(kT), 0, st, c, n, m, k, point_major,
                                p.units, p.nsplit, p.chunk, idx, grad_out, out_c, out_c0, grad_x);

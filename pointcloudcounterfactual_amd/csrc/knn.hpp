@@ -37,17 +37,12 @@ constexpr int prev_slots(int K) {
 // The entry checks pcc_knn ("knn", "points", nq = n) and pcc_knn_cross ("knn_cross", "candidates") share.  *empty: the
 // call has nothing to do (PCC_OK).
 inline int knn_check_sizes(const char *who, const char *what, int b, int c, int nq, int n, int k, bool *empty) {
-    char msg[128];
-    auto refuse = [&](const char *fmt) {
-        std::snprintf(msg, sizeof msg, fmt, who, what);
-        return pcc::invalid(msg);
-    };
     *empty = false;
-    if (b < 0 || c < 1 || nq < 0 || n < 0 || k < 1) return refuse("%s: bad size");
+    if (b < 0 || c < 1 || nq < 0 || n < 0 || k < 1) return pcc::invalidf("%s: bad size", who);
     if (b == 0 || nq == 0) return *empty = true, PCC_OK;
-    if (k > n) return refuse("%s: k exceeds the number of %s (torch.topk raises too)");
-    if (k > 128) return refuse("%s: k > 128 is not supported");
-    if (b > 65535) return refuse("%s: batch too large");
+    if (k > n) return pcc::invalidf("%s: k exceeds the number of %s (torch.topk raises too)", who, what);
+    if (k > 128) return pcc::invalidf("%s: k > 128 is not supported", who);
+    if (b > 65535) return pcc::invalidf("%s: batch too large", who);
     return PCC_OK;
 }
 

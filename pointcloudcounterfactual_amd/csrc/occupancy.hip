@@ -37,11 +37,6 @@ struct Grid {
     float lo, inv, step, top;  // inv = (res - 1) / extent, step = extent / (res - 1), top = res - 1
 };
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    const unsigned e = 0x7f800000u;
-    return (__float_as_uint(x) & e) != e && (__float_as_uint(y) & e) != e && (__float_as_uint(z) & e) != e;
-}
-
 // nearest grid index on one axis: two roundings (the file is built with -ffp-contract=off), clamped as a float
 __device__ __forceinline__ int axis_cell(float x, const Grid &g) {
     const float t = (x - g.lo) * g.inv;
@@ -59,7 +54,7 @@ __device__ __forceinline__ int cell_of(const float *__restrict__ xyz, unsigned p
     deferred = false;
     if (!active) return -1;
     const float x = xyz[(size_t)p * 3], y = xyz[(size_t)p * 3 + 1], z = xyz[(size_t)p * 3 + 2];
-    if (!finite3(x, y, z)) return -1;
+    if (!pcc::finite3(x, y, z)) return -1;
     const int i = axis_cell(x, g), j = axis_cell(y, g), k = axis_cell(z, g);
     if (g.in_sphere && !in_sphere(i, j, k, g.res - 1)) {
         deferred = true;
@@ -76,7 +71,7 @@ __device__ __forceinline__ void defer(bool want, unsigned p, int *__restrict__ l
     unsigned base = 0;
     if (lane == leader) base = atomicAdd(list_n, (unsigned)__popcll(mask));
     base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
-    if (want) list[base + (unsigned)__popcll(mask & ((1ull << lane) - 1))] = (int)p;
+    if (want) list[base + (unsigned)pcc::lanes_below(mask)] = (int)p;
 }
 
 template <bool PER_CLOUD>
@@ -164,14 +159,6 @@ __global__ __launch_bounds__(kFallbackBlock) void occ_fallback_kernel(int n, int
     }
 }
 
-int memset_async(void *p, size_t bytes, hipStream_t st, const char *what) {
-    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
-    if (e == hipSuccess) return PCC_OK;
-    (void)hipGetLastError();
-    pcc::set_error((int)e, what);
-    return (int)e;
-}
-
 template <bool PER_CLOUD>
 int launch_lds(int blocks, int n, int total, int slab, const float *xyz, const Grid &g, int32_t *counts, int *list, unsigned *list_n,
                hipStream_t st) {
@@ -214,7 +201,7 @@ extern "C" int pcc_occupancy_grid(int s, int n, const float *xyz, int res, float
     const int total = s * n;
     const int forced = pcc::tuning(PCC_TUNE_OCCUPANCY_PATH);  // measurement switch: 1 = global path, 2 = LDS path where it fits
     const bool lds_path = (size_t)bins * sizeof(int) <= (size_t)kLdsBudget && forced != 1;
-    const int cus = pcc::device_cus() > 0 ? pcc::device_cus() : 256;
+    const int cus = pcc::device_cus_or(256);
 
     // in_sphere: [0] the length of the list of deferred points, [4 ..] the list (every point may be on it)
     pcc::WsBlock ws(st);
@@ -224,11 +211,11 @@ extern "C" int pcc_occupancy_grid(int s, int n, const float *xyz, int res, float
         if (int rc = ws.alloc(((size_t)total + 4) * sizeof(int), "occupancy_grid: workspace allocation failed")) return rc;
         list_n = static_cast<unsigned *>(ws.p);
         list = static_cast<int *>(ws.p) + 4;
-        if (int rc = memset_async(list_n, sizeof(unsigned), st, "occupancy_grid: cannot zero the list counter")) return rc;
+        if (int rc = pcc::zero_async(list_n, sizeof(unsigned), st, "occupancy_grid: cannot zero the list counter")) return rc;
     }
     // the per-cloud LDS kernel stores every bin of every row; everything else adds into zeroed counts
     if (!(lds_path && per_cloud))
-        if (int rc = memset_async(counts, (size_t)(per_cloud ? s : 1) * bins * sizeof(int32_t), st, "occupancy_grid: cannot zero counts"))
+        if (int rc = pcc::zero_async(counts, (size_t)(per_cloud ? s : 1) * bins * sizeof(int32_t), st, "occupancy_grid: cannot zero counts"))
             return rc;
 
     if (lds_path && per_cloud) {

@@ -2,6 +2,7 @@
 #include "pcc_common.hpp"
 
 #include <atomic>
+#include <cstdarg>
 #include <cstdlib>
 #include <mutex>
 #include <string>
@@ -35,6 +36,10 @@ int device_cus() {
     }
     return v;
 }
+int device_cus_or(int fallback) {
+    const int cus = device_cus();
+    return cus > 0 ? cus : fallback;
+}
 
 int tuning(int key) { return key >= 0 && key < PCC_TUNE_KEYS ? __atomic_load_n(&g_tuning[key], __ATOMIC_RELAXED) : 0; }
 void set_error(int status, const char *what) {
@@ -45,6 +50,21 @@ void set_error(int status, const char *what) {
 void clear_error() {
     t_status = 0;
     t_msg[0] = '\0';
+}
+int invalidf(const char *fmt, ...) {
+    char buf[256];
+    va_list args;
+    va_start(args, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, args);
+    va_end(args);
+    return invalid(buf);
+}
+int zero_async(void *p, size_t bytes, hipStream_t st, const char *what) {
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
+    if (e == hipSuccess) return PCC_OK;
+    (void)hipGetLastError();
+    set_error((int)e, what);
+    return (int)e;
 }
 
 namespace {

@@ -35,6 +35,17 @@ inline int invalid(const char *what) {
     set_error(PCC_EINVAL, what);
     return PCC_EINVAL;
 }
+// ... with a printf-style message (256 bytes at the most), for checks shared under several entry points' names
+__attribute__((format(printf, 1, 2))) int invalidf(const char *fmt, ...);
+
+// Stream-ordered zero fill.  PCC_OK, or the HIP error with `what` as the error message (the sticky error is cleared).
+int zero_async(void *p, size_t bytes, hipStream_t st, const char *what);
+
+// No coordinate is an infinity or a NaN.
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    const unsigned e = 0x7f800000u;
+    return (__float_as_uint(x) & e) != e && (__float_as_uint(y) & e) != e && (__float_as_uint(z) & e) != e;
+}
 
 // Squared norm of a difference vector, in the one rounding order shared with the CPU oracle
 // (oracle/structural_oracle.c sqsum3 mode 0).  The translation unit is built with
@@ -56,6 +67,7 @@ int tuning(int key);
 
 // Compute units of the CURRENT device (cached per device: a process may drive several); 0 if the query fails.
 int device_cus();
+int device_cus_or(int fallback);  // ... `fallback` instead of 0
 
 // Optional hipEvent bracket around one kernel launch (pcc_profile_* in the C ABI).
 bool profiling();

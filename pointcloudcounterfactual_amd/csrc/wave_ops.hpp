@@ -74,6 +74,29 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
+// u where keep is all ones, +0 where it is 0.  Bit arithmetic and not a select: see seg_prefix_sum.
+__device__ __forceinline__ float keep_bits(float u, int keep) { return __int_as_float(__float_as_int(u) & keep); }
+
+// Segmented inclusive prefix sum over the 64 lanes: every lane ends with the sum of its segment's lanes up to itself.
+// Six steps, fixed order (so fixed bits): row_shr 1 2 4 8 inside the rows of 16 lanes, then lane 15 / 47 into the next
+// row (rows 1 and 3), then lane 31 into the upper half (rows 2 and 3).  The caller says, per lane and step, whether the
+// step's partner belongs to the lane's segment (all ones) or not (0; also where the step gives the lane no partner);
+// the masks depend on the segments alone, so one set serves every value summed over them.
+// The partner's value is taken by ALL lanes and then masked with bit arithmetic: written as a select, the compiler moves
+// the DPP move under the mask's exec mask, and a lane whose own mask is clear is then an inactive -- invalid -- source
+// for its neighbour.
+struct SegMasks {
+    int shr1, shr2, shr4, shr8, bcast15, bcast31;
+};
+__device__ __forceinline__ float seg_prefix_sum(float v, const SegMasks &m) {
+    v += keep_bits(dpp<kRowShr + 1>(v), m.shr1);
+    v += keep_bits(dpp<kRowShr + 2>(v), m.shr2);
+    v += keep_bits(dpp<kRowShr + 4>(v), m.shr4);
+    v += keep_bits(dpp<kRowShr + 8>(v), m.shr8);
+    v += keep_bits(dpp<kRowBcast15, 0xa>(v), m.bcast15);
+    return v + keep_bits(dpp<kRowBcast31, 0xc>(v), m.bcast31);
+}
+
 // Maximum of a 64-bit key: over the 16 lanes of a row in every lane of the row (the tree of row_reduce16, both halves of
 // the key through DPP), and over the wave as a wave-uniform value (the four row results read back with v_readlane).
 template <int CTRL>

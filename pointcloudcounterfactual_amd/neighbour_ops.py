@@ -26,6 +26,20 @@ _L = _lib.lib
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
 
 
+def _same_device(name: str, t: torch.Tensor, dev: torch.device) -> None:
+    """``t`` is on ``dev``, or the ``RuntimeError`` of ``_lib.ptr``."""
+    if t.device != dev:
+        if dev.type == 'cuda' and t.device.type != 'cuda':
+            raise RuntimeError(f'{name} must be a CUDA tensor')
+        raise RuntimeError(f'{name} is on {t.device}, expected {dev}')
+
+
+def _float32(name: str, t: torch.Tensor) -> None:
+    """``t`` is float32, or the ``RuntimeError`` of ``_lib.ptr``."""
+    if t.dtype != F32:
+        raise RuntimeError(f'{name} must be {F32}, found {t.dtype}')
+
+
 # ---- squared distances (reference neighbour_ops.py:16-50) -----------------------------------------------------------------
 
 
@@ -161,8 +175,7 @@ def _fps_args(xyz: torch.Tensor, m: int, start: Any) -> tuple[torch.Tensor, int,
     """The checks ``farthest_point_sample`` makes before anything runs: ``(xyz detached, m, start as a tensor or None)``."""
     if xyz.dim() != 3 or xyz.shape[2] != 3:
         raise ValueError(f'farthest_point_sample: expected xyz[B,N,3], got {tuple(xyz.shape)}')
-    if xyz.dtype != F32:
-        raise RuntimeError(f'xyz must be {F32}, found {xyz.dtype}')
+    _float32('xyz', xyz)
     b, n = xyz.shape[:2]
     if isinstance(m, bool) or not isinstance(m, int) or m < 1 or m > n:
         raise ValueError(f'farthest_point_sample: m must be an int in [1, N = {n}], got {m!r}')
@@ -170,10 +183,7 @@ def _fps_args(xyz: torch.Tensor, m: int, start: Any) -> tuple[torch.Tensor, int,
         if start is not None:
             if start.dim() != 1 or start.shape[0] != b or start.dtype not in (I32, I64, torch.int16, torch.int8, torch.uint8):
                 raise ValueError(f'farthest_point_sample: start must be an int tensor [B = {b}], got {tuple(start.shape)} {start.dtype}')
-            if start.device != xyz.device:
-                if xyz.device.type == 'cuda' and start.device.type != 'cuda':
-                    raise RuntimeError('start must be a CUDA tensor')
-                raise RuntimeError(f'start is on {start.device}, expected {xyz.device}')
+            _same_device('start', start, xyz.device)
     elif isinstance(start, int) and not isinstance(start, bool):
         start = torch.full((b,), min(max(start, 0), n - 1), dtype=I32, device=xyz.device) if b else None
     else:
@@ -245,13 +255,9 @@ def _ball_args(xyz: torch.Tensor, centres: torch.Tensor, radius: Any, nsample: i
         raise ValueError(f'ball_query: expected xyz[B,N,3] with N >= 1, got {tuple(xyz.shape)}')
     if centres.dim() != 3 or centres.shape[2] != 3 or centres.shape[0] != xyz.shape[0]:
         raise ValueError(f'ball_query: expected centres[B = {xyz.shape[0]},M,3], got {tuple(centres.shape)}')
-    for name, t in (('xyz', xyz), ('centres', centres)):
-        if t.dtype != F32:
-            raise RuntimeError(f'{name} must be {F32}, found {t.dtype}')
-    if centres.device != xyz.device:
-        if xyz.device.type == 'cuda' and centres.device.type != 'cuda':
-            raise RuntimeError('centres must be a CUDA tensor')
-        raise RuntimeError(f'centres is on {centres.device}, expected {xyz.device}')
+    _float32('xyz', xyz)
+    _float32('centres', centres)
+    _same_device('centres', centres, xyz.device)
     if isinstance(nsample, bool) or not isinstance(nsample, int) or nsample < 1:
         raise ValueError(f'ball_query: nsample must be an int >= 1, got {nsample!r}')
     if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
@@ -324,14 +330,6 @@ def ball_query(xyz: torch.Tensor, centres: torch.Tensor, radius: float, nsample:
 # ---- grouping along a list of another point set ------------------------------------------------------------------------
 
 
-def _same_device(name: str, t: torch.Tensor, dev: torch.device) -> None:
-    """``t`` is on ``dev``, or the ``RuntimeError`` of ``_lib.ptr``."""
-    if t.device != dev:
-        if dev.type == 'cuda' and t.device.type != 'cuda':
-            raise RuntimeError(f'{name} must be a CUDA tensor')
-        raise RuntimeError(f'{name} is on {t.device}, expected {dev}')
-
-
 def _group_args(x: torch.Tensor, idx: torch.Tensor, centres: torch.Tensor | None, point_major: Any,
                 what: str = 'group_points') -> tuple[int, int, int, int, int]:
     """The checks ``group_points`` makes before anything runs: ``(b, c, n, m, k)``."""
@@ -349,11 +347,13 @@ def _group_args(x: torch.Tensor, idx: torch.Tensor, centres: torch.Tensor | None
         raise ValueError(f'{what}: idx[B,M,k] with M * k >= 2^31, got {tuple(idx.shape)}')
     if centres is not None and tuple(centres.shape) != ((b, m, c) if point_major else (b, c, m)):
         raise ValueError(f'{what}: expected {clay} = {(b, m, c) if point_major else (b, c, m)}, got {tuple(centres.shape)}')
-    for name, t, dtype in (('x', x, F32), ('idx', idx, I64), ('centres', centres, F32)):
-        if t is not None:
-            if t.dtype != dtype:
-                raise RuntimeError(f'{name} must be {dtype}, found {t.dtype}')
-            _same_device(name, t, x.device)
+    _float32('x', x)
+    if idx.dtype != I64:
+        raise RuntimeError(f'idx must be {I64}, found {idx.dtype}')
+    _same_device('idx', idx, x.device)
+    if centres is not None:
+        _float32('centres', centres)
+        _same_device('centres', centres, x.device)
     return b, c, n, m, k
 
 
@@ -463,8 +463,7 @@ def sample_and_group(xyz: torch.Tensor, features: torch.Tensor | None, m: int, r
         if features.dim() != 3 or features.shape[0] != xyz.shape[0] or features.shape[2] != xyz.shape[1] or features.shape[1] < 1:
             raise ValueError(f'sample_and_group: expected features[B = {xyz.shape[0]},C,N = {xyz.shape[1]}] with C >= 1, '
                              f'got {tuple(features.shape)}')
-        if features.dtype != F32:
-            raise RuntimeError(f'features must be {F32}, found {features.dtype}')
+        _float32('features', features)
         _same_device('features', features, xyz.device)
     b = xyz.shape[0]
     _ball_args(xyz, xyz.new_zeros((b, 0, 3)), radius, nsample, pad)  # (radius, nsample and pad, before the sampling runs)

@@ -310,3 +310,48 @@ def test_graph_entry_points_check_sizes_and_pointers_before_any_launch():
     assert status_and_error(pool, 1, 1, 4, None, None, None, None) == (PCC_EINVAL, 'global_pool: null pointer')
     assert status_and_error(pool, 0, 1, 4, dummy, None, None, None)[0] == PCC_OK
     assert status_and_error(pool, 1, 0, 4, dummy, None, None, None)[0] == PCC_OK
+
+
+def test_tuning_scope_sets_the_switch_and_always_sets_it_back(monkeypatch):
+    """``_lib.tuning`` is ``set_tuning(name, value)`` on entry and ``set_tuning(name, 0)`` on exit, also when the body
+    raises; the body's exception is the caller's."""
+    from pointcloudcounterfactual_amd import _lib
+
+    calls = []
+    monkeypatch.setattr(_lib, 'set_tuning', lambda name, value: calls.append((name, value)))
+    with _lib.tuning('group_path', 2):
+        assert calls == [('group_path', 2)]
+    assert calls == [('group_path', 2), ('group_path', 0)]
+    del calls[:]
+    with pytest.raises(ZeroDivisionError):
+        with _lib.tuning('group_path', 2):
+            1 / 0
+    assert calls == [('group_path', 2), ('group_path', 0)]
+
+
+def test_sampling_and_grouping_dtype_and_device_errors_word_for_word():
+    """The two raises ``farthest_point_sample``, ``ball_query``, ``group_points`` and ``sample_and_group`` share
+    (``_float32``, ``_same_device``) carry the tensor's name in the words of ``_lib.ptr``; where two apply, the first in the
+    function's order of checks wins."""
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+
+    f64, meta, i32 = '{} must be torch.float32, found torch.float64', '{} is on meta, expected cpu', 'idx must be torch.int64, found torch.int32'
+    xyz, centres, start = torch.rand(2, 10, 3), torch.rand(2, 4, 3), torch.zeros(2, dtype=torch.int64)
+    x, idx, c, feat = torch.zeros(2, 4, 10), torch.zeros(2, 5, 3, dtype=torch.int64), torch.zeros(2, 4, 5), torch.zeros(2, 4, 10)
+    fps, ball, group, sag = ops.farthest_point_sample, ops.ball_query, ops.group_points, ops.sample_and_group
+    cases = [(fps, (xyz.double(), 2), f64.format('xyz')), (fps, (xyz, 2, start.to('meta')), meta.format('start')),
+             (fps, (xyz.double(), 2, start.to('meta')), f64.format('xyz')),
+             (ball, (xyz.double(), centres, 1.0, 4), f64.format('xyz')), (ball, (xyz, centres.double(), 1.0, 4), f64.format('centres')),
+             (ball, (xyz, centres.to('meta'), 1.0, 4), meta.format('centres')),
+             (ball, (xyz, centres.double().to('meta'), 1.0, 4), f64.format('centres')),
+             (group, (x.double(), idx), f64.format('x')), (group, (x, idx.int()), i32), (group, (x, idx, c.double()), f64.format('centres')),
+             (group, (x, idx.to('meta')), meta.format('idx')), (group, (x, idx, c.to('meta')), meta.format('centres')),
+             (group, (x.double(), idx.to('meta')), f64.format('x')), (group, (x, idx.int().to('meta'), c.double()), i32),
+             (group, (x, idx.to('meta'), c.double()), meta.format('idx')),
+             (sag, (xyz, feat.double(), 4, 0.5, 3), f64.format('features')), (sag, (xyz, feat.to('meta'), 4, 0.5, 3), meta.format('features')),
+             (sag, (xyz.double(), feat.to('meta'), 4, 0.5, 3), f64.format('xyz')),
+             (sag, (xyz, feat.double().to('meta'), 4, 0.5, 3), f64.format('features'))]
+    for fn, args, expected in cases:
+        with pytest.raises(RuntimeError) as e:
+            fn(*args)
+        assert str(e.value) == expected, (fn.__name__, expected)

@@ -123,12 +123,9 @@ def test_auction_cluster_sizes_agree(cuda, oracle_mod, cluster):
 
     a, c = _clouds(5, 3, 2048)
     od, oa, _ = oracle_mod.auction_forward(a, c, 0.005, 30)
-    _lib.set_tuning('auction_cluster', cluster)
-    try:
+    with _lib.tuning('auction_cluster', cluster):
         d, asg = emdModule()(torch.from_numpy(a).to(cuda), torch.from_numpy(c).to(cuda), 0.005, 30)
         torch.cuda.synchronize()
-    finally:
-        _lib.set_tuning('auction_cluster', 0)
     assert np.array_equal(asg.cpu().numpy(), oa) and np.array_equal(d.cpu().numpy(), od)
 
 

@@ -37,11 +37,8 @@ def _ball(x, c, radius, nsample, pad, count=True):
 def _forced(path, fn):
     from pointcloudcounterfactual_amd import _lib
 
-    try:
-        _lib.set_tuning('ball_path', path)
+    with _lib.tuning('ball_path', path):
         return fn()
-    finally:
-        _lib.set_tuning('ball_path', 0)
 
 
 def _lattice_centres(seed, x, m, between):

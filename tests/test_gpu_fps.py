@@ -73,11 +73,8 @@ def test_every_path_gives_the_same_bits(cuda, n):
             for path, cap in CAPACITY.items():
                 if cap is not None and cap < n:
                     continue
-                try:
-                    _lib.set_tuning('fps_path', path)
+                with _lib.tuning('fps_path', path):
                     got = _fps(x, m, cuda, start)
-                finally:
-                    _lib.set_tuning('fps_path', 0)
                 assert np.array_equal(got[0], base[0]) and _same_bits(got[1], base[1]), (levels, m, path)
 
 
@@ -136,11 +133,8 @@ def test_non_finite_points_are_excluded(cuda):
     from pointcloudcounterfactual_amd import _lib
 
     for path in CAPACITY:
-        try:
-            _lib.set_tuning('fps_path', path)
+        with _lib.tuning('fps_path', path):
             got = _fps(x, m, cuda, start)
-        finally:
-            _lib.set_tuning('fps_path', 0)
         assert np.array_equal(got[0], ref_idx) and _same_bits(got[1], ref_dist), path
 
 

@@ -94,15 +94,6 @@ def _profiled():
         lib.pcc_profile_enable(0)
 
 
-@contextlib.contextmanager
-def _tuning(name, value):
-    _lib().set_tuning(name, value)
-    try:
-        yield
-    finally:
-        _lib().set_tuning(name, 0)
-
-
 # ---- inputs ---------------------------------------------------------------------------------------------------------
 
 
@@ -269,7 +260,7 @@ def test_scatter_switches_give_the_exact_bits(cuda, b, c, n, k):
     sum to the per-edge scatter; on integer values that must give the float64 reference's bits, as the product's
     schedules do (test_graph_ops_at_every_schedule)."""
     x, idx, ws = _inputs(b, c, n, k, 'exact', seed=n * 7 + k)
-    with _tuning('edge_scatter', 1), _tuning('nbrsum_scatter', 1), _profiled() as launches:
+    with _lib().tuning('edge_scatter', 1), _lib().tuning('nbrsum_scatter', 1), _profiled() as launches:
         res = _run_ops(x, idx, ws, cuda)
         assert launches('edge_stream_bwd_kernel') == 0 and launches('nbrsum_bwd_sorted_kernel') == 0
         for p in (*BWD_KERNELS['scatter'], NBRSUM_KERNELS['scatter']):

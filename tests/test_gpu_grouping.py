@@ -18,11 +18,8 @@ SENTINEL = -1234.5  # what the channels outside a call's slice must keep
 def _forced(path, fn):
     from pointcloudcounterfactual_amd import _lib
 
-    try:
-        _lib.set_tuning('group_path', path)
+    with _lib.tuning('group_path', path):
         return fn()
-    finally:
-        _lib.set_tuning('group_path', 0)
 
 
 def _p(t):

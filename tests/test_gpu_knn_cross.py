@@ -171,14 +171,11 @@ def test_knn_cross_split_is_invisible(cuda, b, nq, n, c):
     q, x = _cloud(nq + c, b, c, nq).to(cuda), _cloud(n + c, b, c, n).to(cuda)
     for k in (16, 128):
         auto = ops.hip_knn_cross(q, x, k, return_distance=True)
-        try:
-            for s in (1, 2, 7, 16):
-                _lib.set_tuning('knn_cross_split', s)
+        for s in (1, 2, 7, 16):
+            with _lib.tuning('knn_cross_split', s):
                 idx, dist = ops.hip_knn_cross(q, x, k, return_distance=True)
-                assert torch.equal(idx, auto[0]), (k, s)
-                assert torch.equal(dist, auto[1]), (k, s)
-        finally:
-            _lib.set_tuning('knn_cross_split', 0)
+            assert torch.equal(idx, auto[0]), (k, s)
+            assert torch.equal(dist, auto[1]), (k, s)
         assert idx.min() >= 0 and idx.max() < n
 
 

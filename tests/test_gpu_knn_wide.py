@@ -84,12 +84,9 @@ def test_knn_wide_degenerate_clouds(cuda, oracle_mod):
         same = torch.full((2, c, 100), 0.25)
         assert (_knn(same, 40, cuda) == np.arange(40)[None, None, :]).all(), c
     one = torch.rand(3, 3, 1)
-    _lib.set_tuning('knn_wide', 1)
-    try:
+    with _lib.tuning('knn_wide', 1):
         assert (_knn(one, 1, cuda) == 0).all()
         assert (_knn(torch.rand(2, 9, 1), 1, cuda) == 0).all()
-    finally:
-        _lib.set_tuning('knn_wide', 0)
     for c, oracle in ((3, oracle_mod.knn_diff), (200, oracle_mod.knn_expanded)):
         x = _cloud(5 + c, 2, c, 200)
         x[0, 1, 17] = float('nan')
@@ -113,11 +110,8 @@ def test_knn_wide_switch_matches_the_existing_kernels(cuda, b, c, n, k):
 
     x = _cloud(b * 13 + c + n + k, b, c, n)
     ref = _knn(x, k, cuda)
-    _lib.set_tuning('knn_wide', 1)
-    try:
+    with _lib.tuning('knn_wide', 1):
         got = _knn(x, k, cuda)
-    finally:
-        _lib.set_tuning('knn_wide', 0)
     assert np.array_equal(got, ref)
 
 

@@ -157,11 +157,8 @@ def test_knn_mfma_vs_oracle(cuda, oracle_mod, b, c, n, k, kernel):
     from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
 
     x = _x(c * 7 + n, b, c, n)
-    _lib.set_tuning('knn_nosplit', kernel)
-    try:
+    with _lib.tuning('knn_nosplit', kernel):
         idx = ops.knn(x.to(cuda), k).cpu().numpy()
-    finally:
-        _lib.set_tuning('knn_nosplit', 0)
     exp = oracle_mod.knn_expanded(x.numpy(), k)
     assert np.array_equal(idx, exp)
 
@@ -177,11 +174,8 @@ def test_knn_mfma_instantiation_choice(cuda, oracle_mod, c, k, kernel):
     from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
 
     x = _x(c * 131 + k, 2, c, 130)
-    _lib.set_tuning('knn_nosplit', kernel)
-    try:
+    with _lib.tuning('knn_nosplit', kernel):
         idx = ops.knn(x.to(cuda), k).cpu().numpy()
-    finally:
-        _lib.set_tuning('knn_nosplit', 0)
     assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), k))
 
 
@@ -209,11 +203,8 @@ def test_knn_mfma_adversarial_orders(cuda, oracle_mod, kernel):
     ties = torch.cat([_x(11, 1, c, 70)] * 10, dim=2)                                 # every point ten times
     for x, k in ((line, 25), (rev, 25), (ties, 16), (torch.cat([line, rev, ties], 0), 20)):
         x = x.contiguous()
-        _lib.set_tuning('knn_nosplit', kernel)
-        try:
+        with _lib.tuning('knn_nosplit', kernel):
             idx = ops.knn(x.to(cuda), k).cpu().numpy()
-        finally:
-            _lib.set_tuning('knn_nosplit', 0)
         assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), k))
 
 

@@ -32,11 +32,8 @@ def _gpu(x, cuda, *args, path=0, **kwargs):
     from pointcloudcounterfactual_amd import _lib
 
     x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x, dtype=np.float32))
-    try:
-        _lib.set_tuning('occupancy_path', path)
+    with _lib.tuning('occupancy_path', path):
         out = _sm().occupancy_grid(x.to(cuda), *args, **kwargs)
-    finally:
-        _lib.set_tuning('occupancy_path', 0)
     assert out.dtype == torch.int64 and out.device.type == 'cuda'
     return out.cpu()
 
@@ -143,13 +140,10 @@ def test_a_dirty_counts_buffer_is_overwritten(cuda):
             for per_cloud in (0, 1):
                 for path in PATHS:
                     counts = torch.full((s if per_cloud else 1, res ** 3), 12345, dtype=torch.int32, device=cuda)
-                    try:
-                        _lib.set_tuning('occupancy_path', path)
+                    with _lib.tuning('occupancy_path', path):
                         for _ in range(2):  # (the second call finds the first one's counts)
                             call(_lib.lib.pcc_occupancy_grid, 'occupancy_grid', cuda, s, n, ptr(xd, 'xyz', torch.float32, cuda), res, -0.5,
                                  1.0, in_sphere, per_cloud, ptr(counts, 'counts', torch.int32, cuda))
-                    finally:
-                        _lib.set_tuning('occupancy_path', 0)
                     want = cpu if per_cloud else cpu.sum(0, keepdim=True)
                     assert torch.equal(counts.cpu().to(torch.int64), want.reshape(-1, res ** 3)), (s, n, res, in_sphere, per_cloud, path)
 

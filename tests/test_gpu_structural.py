@@ -449,13 +449,10 @@ def test_two_lane_schedule_equals_single_stream(cuda):
     rowmass1 = m1[0].sum(2)
     temp1, mc1 = m1[1].clone(), m1[2].clone()
     del m1
-    _lib.set_tuning('am_nosplit', 1)
-    try:
+    with _lib.tuning('am_nosplit', 1):
         s1 = backend.MatchCostImplicit(t1, t2, True)
         sm = backend.ApproxMatchCost(t1, t2)
         torch.cuda.synchronize()
-    finally:
-        _lib.set_tuning('am_nosplit', 0)
     assert all(torch.equal(x, y) for x, y in zip(r1, s1))
     assert torch.equal(mc1, sm[2]) and torch.equal(temp1, sm[1]) and torch.equal(rowmass1, sm[0].sum(2))
 
@@ -482,12 +479,9 @@ def test_resident_fine_levels_equal_one_launch_per_pass(cuda):
 
     for k, shape in enumerate(shapes):
         resident = run(k, *shape)
-        _lib.set_tuning('am_noresident', 1)
-        try:
+        with _lib.tuning('am_noresident', 1):
             per_pass = run(k, *shape)
             torch.cuda.synchronize()
-        finally:
-            _lib.set_tuning('am_noresident', 0)
         for name in resident:
             assert np.array_equal(resident[name].cpu().numpy(), per_pass[name].cpu().numpy(), equal_nan=True), (name, shape)
         assert torch.isfinite(resident['cost']).all()

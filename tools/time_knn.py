@@ -28,9 +28,8 @@ if len(sys.argv) > 1:
             x = torch.randn(bb, c, N, device=dev)
             t = []
             for nosplit in (0, 1):  # 0: the product's choice; 1: the 128-query kernel everywhere
-                _lib.set_tuning('knn_nosplit', nosplit)
-                t.append(ev(lambda: ops.hip_knn(x, 25)))
-            _lib.set_tuning('knn_nosplit', 0)
+                with _lib.tuning('knn_nosplit', nosplit):
+                    t.append(ev(lambda: ops.hip_knn(x, 25)))
             print(f'knn B={bb} c={c} k=25: {t[0]:.1f} us   (128-query kernel: {t[1]:.1f} us)')
     # the reference's CPU formula (torch_knn, neighbour_ops.py:53-74) run by stock PyTorch on the GPU: expanded-form
     # distances through bmm, then topk -- what a user gets without this library

@@ -54,11 +54,8 @@ def torch_knn_cross(q, x, k):
 
 def with_switch(name, value, fn):
     def run():
-        _lib.set_tuning(name, value)
-        try:
+        with _lib.tuning(name, value):
             return fn()
-        finally:
-            _lib.set_tuning(name, 0)
     return run
 
 
