@@ -125,6 +125,38 @@ int pcc_group_points(int b, int c, int n, int m, int k, int point_major, const f
 int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, const int64_t *idx, const float *grad_out,
                          int out_c, int out_c0, float *grad_x, float *grad_centre, pcc_stream_t stream);
 
+/* Feature propagation: every one of m dense points becomes the weighted sum of the features of the k sparse points its list
+ * names: idx[b, m, k] int64 into a cloud of n points (the list of pcc_knn_cross with the dense points as queries), w[b, m, k]
+ * float32 (inverse-distance weights, or any others).  No counterpart in the reference; what a user writes in torch instead
+ * is an expanded gather of [b, c, m, k], a multiplication and a sum over k.
+ *   layouts     x[b, c, n] and grad_x[b, c, n] channels-major (the feature layout of the graph ops).  out and grad_out are
+ *               [b, out_c, m], and a call touches their channels out_c0 .. out_c0 + c - 1 only (the slice convention of
+ *               pcc_group_points): the skip features are concatenated without a cat of the interpolated half.
+ *   forward     out[b, out_c0 + ch, i]: acc = +0.0f, then for j = 0 .. k - 1 in order acc = acc + (w[b, i, j] *
+ *               x[b, ch, idx[b, i, j]]): one float32 multiplication and one float32 addition per slot, two roundings, not an
+ *               fmaf.  A slot whose index is outside [0, n) is skipped: it adds nothing, whatever its weight (a NaN
+ *               included), and carries no gradient.  Everything else is IEEE: 0 * inf is NaN, NaN weights propagate.  IEEE
+ *               leaves the sign and payload of a NaN result open, so a NaN acc is written as the word 0x7fc00000.  Every
+ *               output word is determined by x, the point's index row and its weight row: it does not depend on b, m, the
+ *               position in the batch or the variant that ran.
+ *   backward    grad_x[b, ch, t] = sum of w[b, i, j] * grad_out[b, out_c0 + ch, i] (one rounded product per slot) over the
+ *               in-range slots with idx[b, i, j] == t; every element of grad_x is written, +0.0 where nothing points.  The
+ *               products are accumulated with float atomics (LDS bins, or global memory where a cloud's bins do not fit
+ *               LDS), as in pcc_group_points_bwd: the float summation order of grad_x is not fixed.
+ *               grad_w[b, i, j]: acc = +0.0f, then for ch = 0 .. c - 1 in order acc = acc + (grad_out[b, out_c0 + ch, i] *
+ *               x[b, ch, idx[b, i, j]]): a fixed order, so the words are determined (up to the payload of a NaN); +0.0 for a
+ *               slot outside [0, n).  Either gradient pointer may be null; with both null nothing is enqueued; x may be
+ *               null when grad_w is.
+ * Requires c >= 1, n >= 1, k >= 1, m >= 0, 0 <= out_c0, out_c0 + c <= out_c, b <= 65535, m * k < 2^31 and non-null x, idx,
+ * w, out / idx, w, grad_out (PCC_EINVAL otherwise, under "interpolate:" / "interpolate_bwd:", before anything is enqueued).
+ * b = 0 enqueues nothing and returns PCC_OK; m = 0: the forward enqueues nothing, the backward zero-fills grad_x.  64-bit
+ * offsets throughout, no workspace, and no n is refused: where not even one channel row of a cloud fits a workgroup's LDS
+ * (n > 40960) the gathers and the atomics go to global memory. */
+int pcc_interpolate(int b, int c, int n, int m, int k, const float *x, const int64_t *idx, const float *w, float *out,
+                    int out_c, int out_c0, pcc_stream_t stream);
+int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const int64_t *idx, const float *w,
+                        const float *grad_out, int out_c, int out_c0, float *grad_x, float *grad_w, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

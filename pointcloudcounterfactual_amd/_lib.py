@@ -60,6 +60,8 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_ball_query': (_int, [_int, _int, _int, _int, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_group_points': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     'pcc_group_points_bwd': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    'pcc_interpolate': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    'pcc_interpolate_bwd': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     'pcc_gather_neighbours': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_graph_features': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
@@ -138,7 +140,7 @@ def call(fn: Any, what: str, device: torch.device, *args: Any) -> None:
 # include/pcc_test_hooks.h: measurement / bit-identity switches (inert unless PCC_TEST_HOOKS=1 is in the environment)
 TUNING = {'am_nocull': 2, 'am_nosplit': 3, 'am_noresident': 4, 'edge_scatter': 5, 'nbrsum_scatter': 6,
           'auction_cluster': 7, 'knn_nosplit': 8, 'knn_wide': 9, 'knn_cross_split': 10, 'fps_path': 11, 'occupancy_path': 12,
-          'ball_path': 13, 'group_path': 14}
+          'ball_path': 13, 'group_path': 14, 'interp_path': 15}
 
 
 def set_tuning(name: str, value: int) -> None:
