@@ -184,7 +184,10 @@ int pcc_approxmatch_cost(int b, int n, int m, const float *xyz1, const float *xy
 
 /* Replaces `matchcost` (reference approxmatch.cu:309-316; declared structural_loss.cpp:11).
  *   out[b] = sum_{k<m} sum_{j<n} match[b,k,j] * sqrt(|xyz1_j - xyz2_k|^2).  `match` is read-only
- *   (the reference declares it non-const but never writes it). */
+ *   (the reference declares it non-const but never writes it).
+ * b <= 65535 (the batch is a grid dimension): more returns PCC_EINVAL "matchcost: batch too large" before anything is
+ * allocated or enqueued.  The same limit and message, under their own names, hold for matchcostgrad, approxmatch and
+ * pcc_match_cost / pcc_chamfer_emd. */
 void matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *out,
                pcc_stream_t stream);
 int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *out,
@@ -198,7 +201,8 @@ void matchcostgrad(int b, int n, int m, const float *xyz1, const float *xyz2, co
 int pcc_matchcostgrad(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                       float *grad1, float *grad2, pcc_stream_t stream);
 /* The same with the upstream gradient folded in: grad1[b] *= grad_cost[b], grad2[b] *= grad_cost[b] -- what the
- * Python wrapper does with two extra elementwise passes (match_cost.py:41-42).  grad_cost == NULL means 1. */
+ * Python wrapper does with two extra elementwise passes (match_cost.py:41-42).  grad_cost == NULL means 1.
+ * Both refuse b > 65535 ("matchcostgrad: batch too large"). */
 int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                              const float *grad_cost, float *grad1, float *grad2, pcc_stream_t stream);
 

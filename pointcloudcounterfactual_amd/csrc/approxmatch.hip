@@ -1538,7 +1538,7 @@ int match_cost_implicit_impl(int b, int n, int m, const float *xyz1, const float
 int approxmatch_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, bool with_cost,
                       float *cost, hipStream_t st) {
     pcc::clear_error();
-    if (int rc = check_sizes(with_cost ? "approxmatch_cost: bad size" : "approxmatch: bad size", b, n, m)) return rc;
+    if (int rc = check_sizes(with_cost ? "approxmatch_cost" : "approxmatch", b, n, m)) return rc;
     const char *null_ptr = with_cost ? "approxmatch_cost: null pointer" : "approxmatch: null pointer";
     if (b == 0) return PCC_OK;
     if (with_cost && !cost) return pcc::invalid(null_ptr);
@@ -1571,7 +1571,7 @@ size_t pcc_approxmatch_workspace_bytes(int b, int n, int m) {
 int pcc_approxmatch_ws(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                        void *workspace, size_t workspace_bytes, pcc_stream_t stream) {
     pcc::clear_error();
-    if (int rc = check_sizes("approxmatch: bad size", b, n, m)) return rc;
+    if (int rc = check_sizes("approxmatch", b, n, m)) return rc;
     if (b == 0 || n == 0 || m == 0) return PCC_OK;  // nothing to match (reference: empty loops)
     if (!xyz1 || !xyz2 || !match || !temp || !workspace) return pcc::invalid("approxmatch: null pointer");
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, workspace, workspace_bytes, nullptr,
@@ -1591,7 +1591,7 @@ int pcc_approxmatch_cost(int b, int n, int m, const float *xyz1, const float *xy
 int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost, float *cost,
                    float *grad1, float *grad2, pcc_stream_t stream) {
     pcc::clear_error();
-    if (int rc = check_sizes("match_cost: bad size", b, n, m)) return rc;
+    if (int rc = check_sizes("match_cost", b, n, m)) return rc;
     if (b == 0) return PCC_OK;
     if (!cost) return pcc::invalid("match_cost: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);

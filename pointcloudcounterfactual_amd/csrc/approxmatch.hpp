@@ -41,9 +41,12 @@ inline float zero_cut2(const LevelConsts &lc, int i) { return kZeroExp / -lc.c[i
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Every entry that goes through here launches at least one grid with the batch in y or z (am_row_kernel, am_grad_fused_kernel,
+// reduce_splits_kernel, am_unpermute_kernel, am_materialise_kernel, pair_finish_kernel): 65535 is the most those take.
 inline int check_sizes(const char *who, int b, int n, int m) {
-    if (b < 0 || n < 0 || m < 0) return pcc::invalid(who);
-    if ((long long)n * 3 > 0x7fffffffLL || (long long)m * 3 > 0x7fffffffLL) return pcc::invalid(who);
+    if (b < 0 || n < 0 || m < 0) return pcc::invalidf("%s: bad size", who);
+    if ((long long)n * 3 > 0x7fffffffLL || (long long)m * 3 > 0x7fffffffLL) return pcc::invalidf("%s: bad size", who);
+    if (b > 65535) return pcc::invalidf("%s: batch too large", who);
     return PCC_OK;
 }
 

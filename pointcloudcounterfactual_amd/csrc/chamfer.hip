@@ -442,6 +442,7 @@ int pcc_chamfer_emd(int b, int n, const float *xyz1, int m, const float *xyz2, i
     if (b == 0) return PCC_OK;
     if (n == 0 || m == 0) return pcc::invalid("chamfer_emd: one cloud is empty");
     if ((long long)n * 3 > 0x7fffffffLL || (long long)m * 3 > 0x7fffffffLL) return pcc::invalid("chamfer_emd: bad size");
+    if (b > 65535) return pcc::invalid("chamfer_emd: batch too large");  // the match_cost grids carry the batch in y
     if (!xyz1 || !xyz2 || !chamfer_loss || !dist1 || !idx1 || !dist2 || !idx2 || !emd_cost)
         return pcc::invalid("chamfer_emd: null pointer");
     if ((emd_grad1 == nullptr) != (emd_grad2 == nullptr)) return pcc::invalid("chamfer_emd: emd_grad1 and emd_grad2 go together");

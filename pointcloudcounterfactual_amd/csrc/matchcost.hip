@@ -261,7 +261,7 @@ extern "C" {
 int pcc_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *out,
                   pcc_stream_t stream) {
     pcc::clear_error();
-    if (int rc = check_sizes("matchcost: bad size", b, n, m)) return rc;
+    if (int rc = check_sizes("matchcost", b, n, m)) return rc;
     if (b == 0) return PCC_OK;
     if (!out) return pcc::invalid("matchcost: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -290,7 +290,7 @@ void matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, float 
 int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                              const float *grad_cost, float *grad1, float *grad2, pcc_stream_t stream) {
     pcc::clear_error();
-    if (int rc = check_sizes("matchcostgrad: bad size", b, n, m)) return rc;
+    if (int rc = check_sizes("matchcostgrad", b, n, m)) return rc;
     if (b == 0) return PCC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n == 0 || m == 0) return zero_fill_empty(b, n, m, nullptr, grad1, grad2, st, "matchcostgrad: memset failed");

@@ -67,6 +67,11 @@ U = 2.0 ** -24
 D40 = 2.0 ** -40
 RSQ_MEASURED_ULP = 0.8636  # at x = 1.34368575 (worst relative error 1.5767 u); sampled binades: 0.8345
 RSQ_ULPS = 1
+# v_sqrt_f32, measured the same way (used by tests/structural_grad_reference.py).  Both instructions, exhaustively over
+# [1, 4) against float64: build tools/sqrt_probe.hip with the line in its header, then `timeout -k 10 120 tools/sqrt_probe`
+# on an MI355X; the run prints 0.9236 ulp for v_sqrt_f32 and reproduces the 0.8636 ulp of v_rsq_f32 above.
+SQRT_MEASURED_ULP = 0.9236  # at x = 3.49945736
+SQRT_ULPS = 1
 MASK_MARGIN = 16.0
 EPS = 1e-5
 
@@ -76,6 +81,7 @@ def g(k: float) -> float:
 
 
 R_RSQ = RSQ_ULPS * 2.0 * U
+R_SQRT = SQRT_ULPS * 2.0 * U
 DINV = g(1) + R_RSQ
 DELTA = DINV + U
 
