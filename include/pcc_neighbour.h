@@ -157,6 +157,53 @@ int pcc_interpolate(int b, int c, int n, int m, int k, const float *x, const int
 int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const int64_t *idx, const float *w,
                         const float *grad_out, int out_c, int out_c0, float *grad_x, float *grad_w, pcc_stream_t stream);
 
+/* Local surface geometry: for every row of an index list idx[b, m, k] int64 into the cloud xyz[b, n, 3] (point-major float32,
+ * the layout of pcc_fps and pcc_ball_query; m != n allowed: the list of pcc_knn, pcc_knn_cross or pcc_ball_query) the mean of
+ * the points it names, their scatter matrix, its eigen-decomposition and the surface variation: mean[b, m, 3],
+ * cov[b, m, 3, 3], eval[b, m, 3], evec[b, m, 3, 3], curv[b, m].  The fused form of the reference's get_local_covariance
+ * (neighbour_ops.py:97-103: gather, subtract the mean, matmul) and of the torch.linalg.eigh a user runs on its result for
+ * normals.  Every output pointer may be null: only what is asked for is computed and written (eval, evec and curv need the
+ * scatter matrix but not its store); with all five null nothing is enqueued.
+ *   valid slots a slot is valid iff its index is in [0, n); cnt is the number of valid slots of the row.  The -1 of
+ *               PCC_BALL_PAD_NONE is skipped, as in pcc_group_points and pcc_interpolate.  A repeated index counts as often
+ *               as it occurs, so a PCC_BALL_PAD_FIRST list weighs its first point by the padding: PCC_BALL_PAD_NONE is the
+ *               unbiased choice.
+ *   mean        per coordinate acc = +0.0f, then acc = acc + x over the valid slots in slot order, then one float32 division
+ *               by (float)cnt; +0.0 if cnt = 0.
+ *   cov         the scatter matrix, NOT divided by cnt (the reference's convention).  d_j = x_j - mean, one float32
+ *               subtraction per coordinate; for a <= b acc = +0.0f, then acc = acc + (d_a * d_b) over the valid slots in slot
+ *               order: a rounded product and a rounded sum, not an fmaf.  The lower triangle is a copy of the upper one.
+ *               A NaN in mean or cov is written as the word 0x7fc00000 (the convention of pcc_interpolate).  Every word of
+ *               mean and cov is determined by the cloud and the index row: it does not depend on b, m, the position in the
+ *               batch or the variant that ran.
+ *   eval, evec  the eigenvalues of the scatter matrix in ascending order; evec[b, i, r, :] is the unit eigenvector of
+ *               eval[b, i, r], so row 0 is the surface normal.  Sign: the component of largest magnitude of each row is
+ *               non-negative, the lowest axis deciding a tie.  An axis whose two off-diagonal entries are exactly 0 is
+ *               decoupled: its unit vector is returned exactly and its eigenvalue is the diagonal entry.  A zero matrix
+ *               (cnt <= 1) gives eigenvalues +0.0 and the rows e_x, e_y, e_z.  A non-finite entry of the scatter matrix
+ *               makes eval, evec and curv of the row the word 0x7fc00000.  The words of these three outputs depend on the
+ *               row's scatter matrix only.  They are not pinned to a CPU formula (a cyclic Jacobi iteration in float32 on
+ *               the matrix scaled by a power of two); the tests bound them against float64: residual and eigenvalue error
+ *               <= 64 * 2^-24 * |S|_F, |V V^T - I| <= 64 * 2^-24.
+ *   curv        the surface variation max(eval0, 0) / (eval0 + eval1 + eval2), taken on the scaled matrix (the scale
+ *               cancels); +0.0 where the sum is not positive.
+ *   backward    pcc_local_covariance_bwd: the gradient of cov and mean in xyz.  Gs = grad_cov + grad_cov^T, one rounded sum
+ *               per entry; gm = grad_mean / (float)cnt, one division per coordinate, absent when grad_mean is null.  For
+ *               every valid slot grad_xyz[b, idx[b,i,j], a] += ((Gs_a0 * d_0 + Gs_a1 * d_1) + Gs_a2 * d_2) + gm_a with d
+ *               recomputed from xyz and the saved mean (the mean's own contribution through d cancels: sum_j d_j = 0).
+ *               Every element of grad_xyz is written, +0.0 where nothing points.  The terms are accumulated with float
+ *               atomics (LDS bins where a cloud's 3 * n floats fit beside the index tile, global memory otherwise) after the
+ *               runs of equal consecutive indices of a row have been summed: as in pcc_group_points_bwd the float summation
+ *               order of grad_xyz is not fixed.  A null grad_xyz enqueues nothing.
+ * Requires n >= 1, k >= 1, m >= 0, b <= 65535, m * k < 2^31 and non-null xyz and idx, for the backward also mean and
+ * grad_cov (PCC_EINVAL otherwise, under "local_geometry:" / "local_covariance_bwd:", before anything is enqueued).  b = 0 or
+ * m = 0 returns PCC_OK; the backward zero-fills grad_xyz for m = 0.  64-bit offsets throughout, no workspace, and no n is
+ * refused. */
+int pcc_local_geometry(int b, int n, int m, int k, const float *xyz, const int64_t *idx, float *mean, float *cov,
+                       float *eval, float *evec, float *curv, pcc_stream_t stream);
+int pcc_local_covariance_bwd(int b, int n, int m, int k, const float *xyz, const int64_t *idx, const float *mean,
+                             const float *grad_cov, const float *grad_mean, float *grad_xyz, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

@@ -16,15 +16,19 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     ball_query,
+    estimate_normals,
     farthest_point_sample,
     feature_propagation,
     group_points,
     interpolate_points,
     interpolation_weights,
+    local_covariance,
+    local_geometry,
     sample_and_group,
 )
 from pointcloudcounterfactual_amd.set_metrics import jsd_between_sets, occupancy_grid  # noqa: F401
 
 __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer', 'MatchCostFunction', 'NNDistanceFunction',
            'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'group_points', 'sample_and_group',
-           'occupancy_grid', 'jsd_between_sets', 'interpolation_weights', 'interpolate_points', 'feature_propagation']
+           'occupancy_grid', 'jsd_between_sets', 'interpolation_weights', 'interpolate_points', 'feature_propagation',
+           'local_covariance', 'local_geometry', 'estimate_normals']

@@ -62,6 +62,8 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_group_points_bwd': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     'pcc_interpolate': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     'pcc_interpolate_bwd': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    'pcc_local_geometry': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_local_covariance_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_graph_features': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
