@@ -22,9 +22,21 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default)
 
-/* emd_cuda_forward (emd_cuda.cu:227-281).  Returns 0, or PCC_EINVAL for iters < 1, n < 1 or n > 8192
- * (the reference's own n % 1024 == 0 and b <= 512 limits, emd_module.py:23-30, are enforced by the Python
- * wrapper, not needed by the kernel). */
+/* emd_cuda_forward (emd_cuda.cu:227-281).  Returns 0, or PCC_EINVAL for iters < 1, n < 1, n > 8192, or eps < 0 or NaN
+ * (the highest increment per target is kept with an integer atomic on the float's bits, which orders values >= 0 only;
+ * eps == 0 is accepted).  The reference's own n % 1024 == 0 and b <= 512 limits, emd_module.py:23-30, are enforced by
+ * the Python wrapper, not needed by the kernel; b == 0 returns 0 and writes nothing.
+ *
+ * Every n in [1, 8192] runs on either schedule.  The one-workgroup schedule keeps all of a sample's state in LDS up to
+ * n = 4095 (40 n + 16 bytes <= 160 KiB); from n = 4096 on the bidder-side arrays and the highest increments live in
+ * 24 n bytes of stream-ordered scratch per sample and LDS holds targets and prices only (16 n + 16 bytes).
+ *
+ * Non-finite input.  A bidder (point of xyz1) to which no target offers a value above the scan's floor of -1e9 -- one of
+ * its own coordinates is NaN or +-inf, or every target is non-finite or ~1e9 away -- makes no bid: it is never assigned,
+ * changes no price, and ends with assignment -1 and dist NaN (pcc_auction_backward gives it a zero gradient).  The other
+ * points of its sample run the auction among themselves; other samples are unaffected.  A non-finite target (point of
+ * xyz2) needs no rule of its own: its value is NaN or -inf, which is never a best or second-best value, so nobody bids on
+ * it and it is never assigned. */
 int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, float eps, int iters, float *dist,
                         int *assignment, pcc_stream_t stream);
 

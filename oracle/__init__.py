@@ -215,6 +215,25 @@ def auction_forward(xyz1, xyz2, eps: float, iters: int):
     return dist, ass, price
 
 
+def auction_forward_ext(xyz1, xyz2, eps: float, iters: int):
+    """``auction_forward`` without the reference's ``n % 1024`` / ``b <= 512`` limits (the sizes the library's C ABI
+    takes) -> dist, assignment, price, iters_used[B] i32: the iterations of each sample that started with at least one
+    unassigned bidder (``iters_used < iters``: the sample converged and the remaining iterations were no-ops)."""
+    xyz1, xyz2 = _f(xyz1), _f(xyz2)
+    b, n, m = _dims(xyz1, xyz2)
+    assert n == m
+    dist = np.zeros((b, n), np.float32)
+    ass = np.zeros((b, n), np.int32)
+    price = np.zeros((b, n), np.float32)
+    used = np.zeros((b,), np.int32)
+    lib().oracle_auction_forward_ext.restype = ctypes.c_int
+    rc = lib().oracle_auction_forward_ext(b, n, _p(xyz1), _p(xyz2), ctypes.c_float(eps), int(iters), _p(dist),
+                                          _p(ass, _i32p), _p(price), _p(used, _i32p))
+    if rc != 1:
+        raise ValueError('auction: invalid input (n >= 1, iters >= 1)')
+    return dist, ass, price, used
+
+
 def auction_backward(xyz1, xyz2, grad_dist, assignment):
     xyz1, xyz2, g, a = _f(xyz1), _f(xyz2), _f(grad_dist), _i(assignment)
     b, n, _ = _dims(xyz1, xyz2)

@@ -2,9 +2,16 @@
 //
 // Replaces external/emd/src/emd_cuda.cu (7 kernels x iters launches, all state in global memory, racy GetMax /
 // Assign).  One persistent 1024-thread workgroup per sample runs every iteration with the auction state in
-// LDS (targets SoA, prices, max increments; for n <= 4096 also the bidder-side arrays): phases are separated
-// by workgroup barriers instead of kernel boundaries, compaction/winner selection use LDS integer atomics,
-// and every tie is resolved deterministically (lowest bidder index), so two runs agree bit for bit.
+// LDS (targets SoA and prices; for n <= 4095, where 40 n + 16 bytes fit the 160 KiB, also the max increments and
+// the bidder-side arrays -- from n = 4096 on those six arrays live in global scratch, which leaves 16 n + 16
+// bytes of LDS and lets n = 8192 launch): phases are separated by workgroup barriers instead of kernel
+// boundaries, compaction/winner selection use integer atomics, and every tie is resolved deterministically
+// (lowest bidder index), so two runs agree bit for bit.
+// A bidder that no target gives a value above the scan's floor of -1e9 (its own coordinates are NaN or
+// infinite, or every target is non-finite or ~1e9 away) makes NO BID in that iteration: best_i stays -1, it
+// writes bid -1 and nothing else, GetMax and Assign skip it (the forced last iteration too) and it ends with
+// assignment -1 and dist NaN.  A non-finite target needs no rule: its value is NaN or -inf, which wins neither
+// `d > best` nor `d > better`, so nobody ever bids on it.
 // Bid values follow emd_cuda.cu:145 literally: `3.0 - sqrtf(d2) - price` is DOUBLE arithmetic rounded once
 // to float; sqrtf is correctly rounded (-fno-fast-math).
 #include "pcc_common.hpp"
@@ -40,11 +47,12 @@ __global__ __launch_bounds__(1024) void auction_kernel(int n, const float *__res
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sx = reinterpret_cast<float *>(smem);
     float *sy = sx + n, *sz = sy + n, *price = sz + n;
-    int *max_inc = reinterpret_cast<int *>(price + n);  // float bits; values written are > 0 or -1e9
-    int *cnt = max_inc + n;                              // [4]
-    int *st = state_in_lds ? cnt + 4 : scratch + (size_t)blockIdx.x * 5 * n;
+    int *hot_end = reinterpret_cast<int *>(price + n);
+    int *cnt = state_in_lds ? hot_end + n : hot_end;  // [4]
+    int *st = state_in_lds ? cnt + 4 : scratch + (size_t)blockIdx.x * 6 * n;
     int *unass = st, *inv = st + n, *bid = st + 2 * n, *win = st + 3 * n;
     float *inc = reinterpret_cast<float *>(st + 4 * n);
+    int *max_inc = state_in_lds ? hot_end : st + 5 * n;  // float bits; values written are >= 0 or -1e9
 
     const int tid = threadIdx.x, T = 1024;
     const int smp = blockIdx.x;
@@ -103,17 +111,20 @@ __global__ __launch_bounds__(1024) void auction_kernel(int n, const float *__res
                 c = merge(c, o);
             }
             if (live && sub == 0) {
-                const float bi = c.best - c.better + eps;  // :174
-                bid[j] = c.best_i;
-                inc[j] = bi;
-                atomicMax(&max_inc[c.best_i], __float_as_int(bi));  // :175 (bi > 0: int order == float order)
-                win[c.best_i] = 0x7fffffff;
+                bid[j] = c.best_i;  // -1: no bid in this iteration
+                if (c.best_i >= 0) {
+                    const float bi = c.best - c.better + eps;  // :174
+                    inc[j] = bi;
+                    atomicMax(&max_inc[c.best_i], __float_as_int(bi));  // :175 (bi >= 0: int order == float order)
+                    win[c.best_i] = 0x7fffffff;
+                }
             }
         }
         __syncthreads();
         // ---- GetMax (:180-193): lowest qualifying bidder wins ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bid[j];
+            if (t < 0) continue;
             const double bi = inc[j], mi = __int_as_float(max_inc[t]);
             if (bi - 1e-6 <= mi && mi <= bi + 1e-6) atomicMin(&win[t], j);
         }
@@ -121,6 +132,7 @@ __global__ __launch_bounds__(1024) void auction_kernel(int n, const float *__res
         // ---- Assign (:195-214) ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bid[j];
+            if (t < 0) continue;
             if (last || win[t] == j) {
                 const int owner = inv[t];
                 if (!last && owner != -1) ass[owner] = -1;
@@ -136,7 +148,10 @@ __global__ __launch_bounds__(1024) void auction_kernel(int n, const float *__res
     __syncthreads();
     for (int j = tid; j < n; j += T) {  // CalcDist :216-225
         const int k = ass[j];
-        dist[(size_t)smp * n + j] = sq3(p1[j * 3 + 0] - sx[k], p1[j * 3 + 1] - sy[k], p1[j * 3 + 2] - sz[k]);
+        const bool valid = k >= 0 && k < n;  // -1: a bidder that never had a bid
+        const int kk = valid ? k : 0;
+        const float d = sq3(p1[j * 3 + 0] - sx[kk], p1[j * 3 + 1] - sy[kk], p1[j * 3 + 2] - sz[kk]);
+        dist[(size_t)smp * n + j] = valid ? d : __builtin_nanf("");
     }
 }
 
@@ -239,12 +254,14 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
                 cd = merge(cd, o);
             }
             if (live && sub == 0) {
-                const float bi = cd.best - cd.better + eps;  // :174
-                bidl[u] = cd.best_i;
-                incl[u] = bi;
-                // :175 (bi > 0: int order == float order)
-                __hip_atomic_fetch_max(&max_inc[cd.best_i], __float_as_int(bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                agent_st(&win[cd.best_i], 0x7fffffff);
+                bidl[u] = cd.best_i;  // -1: no bid in this iteration
+                if (cd.best_i >= 0) {
+                    const float bi = cd.best - cd.better + eps;  // :174
+                    incl[u] = bi;
+                    // :175 (bi >= 0: int order == float order)
+                    __hip_atomic_fetch_max(&max_inc[cd.best_i], __float_as_int(bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    agent_st(&win[cd.best_i], 0x7fffffff);
+                }
             }
         }
         ok = barrier();
@@ -255,6 +272,7 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
         // ---- GetMax (:180-193): lowest qualifying bidder wins ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bidl[u];
+            if (t < 0) continue;
             const double bi = incl[u], mi = __int_as_float(agent_ld(&max_inc[t]));
             if (bi - 1e-6 <= mi && mi <= bi + 1e-6) __hip_atomic_fetch_min(&win[t], j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -263,6 +281,7 @@ __global__ __launch_bounds__(1024) void auction_cluster_kernel(int n, int C, con
         // ---- Assign (:195-214) ----
         for (int u = tid; u < nu; u += T) {
             const int j = unass[u], t = bidl[u];
+            if (t < 0) continue;
             if (last || agent_ld(&win[t]) == j) {
                 const int owner = agent_ld(&inv[t]);
                 if (!last && owner != -1) agent_st(&ass[owner], -1);
@@ -314,6 +333,8 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
     pcc::clear_error();
     if (b < 0 || n < 1 || iters < 1) return pcc::invalid("auction: bad size (n >= 1, iters >= 1)");
     if (n > 8192) return pcc::invalid("auction: n > 8192 does not fit the LDS-resident state");
+    // the highest increment per target is an integer atomicMax on the float's bits: right for increments >= 0 only
+    if (!(eps >= 0.f)) return pcc::invalid("auction: eps must be >= 0 (and not NaN)");
     if (b == 0) return PCC_OK;
     if (!xyz1 || !xyz2 || !dist || !assignment) return pcc::invalid("auction: null pointer");
     if (pcc::take_coresident_failure(pcc::kAuctionCluster))
@@ -357,7 +378,9 @@ int pcc_auction_forward(int b, int n, const float *xyz1, const float *xyz2, floa
             }
         }
     }
-    const size_t hot = (size_t)5 * n * 4 + 16, state = (size_t)5 * n * 4;
+    // targets, prices and the counters always; max increments + the five bidder-side arrays while all of it fits
+    // (40 n + 16 <= 160 KiB: n <= 4095), in global scratch otherwise (16 n + 16 bytes of LDS: 128 KiB + 16 at n = 8192)
+    const size_t hot = (size_t)4 * n * 4 + 16, state = (size_t)6 * n * 4;
     const int in_lds = hot + state <= 160 * 1024;
     const size_t lds = in_lds ? hot + state : hot;
     (void)pcc::allow_lds<auction_kernel>(160 * 1024);
