@@ -221,6 +221,38 @@ int pcc_matchcostgrad_scaled(int b, int n, int m, const float *xyz1, const float
 int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *grad_cost, float *cost,
                    float *grad1, float *grad2, pcc_stream_t stream);
 
+/* ---- sliced Wasserstein distance (extension) -------------------------------------------------------
+ * The third set-to-set loss beside Chamfer and the approximate EMD: the squared 2-Wasserstein distance between the two
+ * clouds projected onto p directions, averaged.  On a line the optimal transport plan is the sorted order, so the cost of
+ * a direction is a sort.  x[b,n,3], y[b,n,3] point-major like the other losses (both clouds have n points); theta[p,3] is
+ * shared by the batch and used as given (not normalised).  No counterpart in the reference.  Every word of cost_p and
+ * cost is determined by the inputs:
+ *   projection  t = (v0 * theta0 + v1 * theta1) + v2 * theta2: three rounded float32 products and two rounded sums, left
+ *               to right, no fmaf.  A projection of -0 is taken as +0.
+ *   order       the n projections of a cloud ascending; every NaN is one value above +inf; equal values go by ascending
+ *               point index.  a_r / b_r: the sorted projections of x / y, pi_x(r) / pi_y(r): the point at rank r.
+ *   slice cost  d_r = a_r - b_r, e_r = d_r * d_r; L = the smallest power of two >= n and e_r = +0 for n <= r < L; the
+ *               halving tree: for h = L/2, L/4 .. 1: e_i = e_i + e_{i+h} for every i < h; cost_p[b,p] = e_0.
+ *   cost        S = ((c_0 + c_1) + c_2) + .. over cost_p[b,:] in ascending p; cost[b] = S * inv, inv = the float32 nearest
+ *               to 1 / (n p), formed in double on the host.
+ *   gradient    of cost[b] with the permutations held constant: grad_x[b, pi_x(r), c] = (2 inv) * sum_p d_r * theta[p,c]
+ *               and grad_y[b, pi_y(r), c] = (2 inv) * sum_p (-d_r) * theta[p,c]; every term is one rounded product, the sum
+ *               over p runs in a fixed order that depends on p alone (the projections in ascending order inside chunks of
+ *               PCC_SW_CHUNK, then the chunks in ascending order), no float atomics: the words of a cloud's gradient are
+ *               the same from run to run and do not depend on b or on the cloud's position in the batch.  Every element of
+ *               a requested gradient is written.
+ * Any of cost, cost_p, grad_x, grad_y may be NULL; with all four NULL nothing is enqueued.  x and y may alias.
+ * Non-finite coordinates: IEEE arithmetic on the order above: a cloud with a NaN coordinate gets a NaN cost, an infinite
+ * one an infinite or NaN cost; the other clouds of the batch are unaffected.
+ * Requires 1 <= n <= PCC_SW_MAX_N, p >= 1, b <= 65535, b * p < 2^31 and non-null x, y, theta (PCC_EINVAL otherwise, before
+ * anything is enqueued); b = 0 enqueues nothing and returns PCC_OK.  64-bit offsets throughout.  Workspace (with
+ * p > PCC_SW_CHUNK only: the partial gradients, b * ceil(p / PCC_SW_CHUNK) * n * 3 floats per requested gradient, and cost_p
+ * when it is NULL and cost is not) comes from the library's private pool (PCC_ENOMEM if that fails). */
+#define PCC_SW_MAX_N 8192
+#define PCC_SW_CHUNK 8 /* projections per workgroup */
+int pcc_sliced_wasserstein(int b, int n, int p, const float *x, const float *y, const float *theta, float *cost,
+                           float *cost_p, float *grad_x, float *grad_y, pcc_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -24,6 +24,9 @@ int pcc_test_inject_approxmatch_failure(void);
  * behaviour).  They replace the PCC_* environment variables earlier rounds read inside the product library: nothing
  * in the product path selects behaviour from the environment any more.  Returns 1 when armed. */
 enum {
+    PCC_TUNE_SW_PATH = 1,          /* pcc_sliced_wasserstein: 1..10 = the variant (threads, elements per thread) = (64,1) (64,2) (64,4) (128,4)
+                                      (256,4) (512,4) (1024,4) (1024,8) (256,8) (512,8); a variant that cannot hold n is ignored.  (Key 1: a
+                                      slot a retired switch left free.) */
     PCC_TUNE_AM_NOCULL = 2,        /* approxmatch: every exact-zero skip off (the no-skip roofline of bench.py) */
     PCC_TUNE_AM_NOSPLIT = 3,       /* approxmatch: everything on the caller's stream (no half-batch lanes) */
     PCC_TUNE_AM_NORESIDENT = 4,    /* approxmatch: levels 0-2 as one launch per pass even where the resident launch qualifies */

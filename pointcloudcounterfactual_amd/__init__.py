@@ -12,7 +12,10 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     chamfer_emd,
     match_cost,
     nn_distance,
+    random_directions,
+    sliced_wasserstein,
     torch_chamfer,
+    torch_sliced_wasserstein,
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     ball_query,
@@ -31,4 +34,5 @@ from pointcloudcounterfactual_amd.set_metrics import jsd_between_sets, occupancy
 __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer', 'MatchCostFunction', 'NNDistanceFunction',
            'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'group_points', 'sample_and_group',
            'occupancy_grid', 'jsd_between_sets', 'interpolation_weights', 'interpolate_points', 'feature_propagation',
-           'local_covariance', 'local_geometry', 'estimate_normals']
+           'local_covariance', 'local_geometry', 'estimate_normals', 'sliced_wasserstein', 'torch_sliced_wasserstein',
+           'random_directions']

@@ -231,3 +231,24 @@ def NNDistanceGrad(set_d: torch.Tensor, set_q: torch.Tensor, idx1: torch.Tensor,
          ptr(grad_dist2, 'grad_dist2', F32, dev), ptr(idx2, 'idx2', I32, dev), ptr(grad1, 'grad1', F32, dev),
          ptr(grad2, 'grad2', F32, dev))
     return [grad1, grad2]
+
+
+def SlicedWasserstein(set_d: torch.Tensor, set_q: torch.Tensor, theta: torch.Tensor, grad1: bool = False, grad2: bool = False,
+                      per_direction: bool = False) -> list[torch.Tensor | None]:
+    """Sliced Wasserstein distance between paired clouds of equal size along ``theta[P,3]`` (extension,
+    ``pcc_sliced_wasserstein``) -> [cost[B], cost_p[B,P] or None, grad1[B,N,3] or None, grad2[B,N,3] or None]: the
+    gradients of ``cost`` (upstream gradient 1), each computed only when asked for."""
+    if set_d.dim() != 3 or set_d.size(2) != 3 or set_q.shape != set_d.shape:
+        raise ValueError(f'SlicedWasserstein: clouds must be [B,N,3] of one shape, got {tuple(set_d.shape)} and {tuple(set_q.shape)}')
+    if theta.dim() != 2 or theta.size(1) != 3:
+        raise ValueError(f'SlicedWasserstein: directions must be [P,3], got {tuple(theta.shape)}')
+    b, n, p = set_d.size(0), set_d.size(1), theta.size(0)
+    dev = set_d.device
+    cost = torch.empty((b,), dtype=torch.float32, device=dev)
+    cost_p = torch.empty((b, p), dtype=torch.float32, device=dev) if per_direction else None
+    g1 = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if grad1 else None
+    g2 = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if grad2 else None
+    call(_L.pcc_sliced_wasserstein, 'SlicedWasserstein', dev, b, n, p, ptr(set_d, 'set_d', F32, dev), ptr(set_q, 'set_q', F32, dev),
+         ptr(theta, 'directions', F32, dev), ptr(cost, 'cost', F32, dev), ptr(cost_p, 'cost_p', F32, dev),
+         ptr(g1, 'grad1', F32, dev), ptr(g2, 'grad2', F32, dev))
+    return [cost, cost_p, g1, g2]

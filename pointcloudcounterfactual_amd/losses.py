@@ -192,3 +192,120 @@ def torch_chamfer(t1: torch.Tensor, t2: torch.Tensor) -> torch.Tensor:
     reference's own host path for ``user.cpu`` runs (BASELINE config 1), not a fallback of ``chamfer``."""
     dist = torch_square_distance(t1, t2)
     return torch.min(dist, dim=-1)[0].sum(1) + torch.min(dist, dim=-2)[0].sum(1)
+
+
+def random_directions(p: int, device: torch.device | str, generator: torch.Generator | None = None) -> torch.Tensor:
+    """``[p,3]`` float32 directions on ``device``: Gaussian rows, normalised (uniform on the sphere).  Drawn on the
+    generator's device when one is given."""
+    device = torch.device(device)
+    raw = torch.randn(p, 3, generator=generator, device=device if generator is None else generator.device)
+    return torch.nn.functional.normalize(raw, dim=1).to(device)
+
+
+def _sw_forward(t1: torch.Tensor, t2: torch.Tensor, theta: torch.Tensor) -> tuple[torch.Tensor, ...]:
+    """The contract of ``pcc_sliced_wasserstein`` (include/pcc_structural.h) in torch operations, none of which fuses a
+    product with a sum: -> (cost[B], cost_p[B,P], d[B,P,N], perm1[B,P,N], perm2[B,P,N], inv)."""
+    n, p = t1.size(1), theta.size(0)
+
+    def sorted_projection(t: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        v, th = t[:, None, :, :], theta[None, :, None, :]
+        proj = (v[..., 0] * th[..., 0] + v[..., 1] * th[..., 1]) + v[..., 2] * th[..., 2]
+        proj = torch.where(proj == 0, torch.zeros_like(proj), proj)  # -0 counts as +0
+        return torch.sort(proj, dim=2, stable=True)  # NaN sorts above +inf, equal values by ascending index
+
+    (a, perm1), (b, perm2) = sorted_projection(t1), sorted_projection(t2)
+    d = a - b
+    size = 1 << max(n - 1, 0).bit_length()
+    e = torch.zeros(d.shape[:2] + (size,), dtype=d.dtype)
+    e[..., :n] = d * d
+    while size > 1:  # the halving tree
+        size //= 2
+        e = e[..., :size] + e[..., size:2 * size]
+    cost_p = e[..., 0]
+    total = cost_p[:, 0]
+    for k in range(1, p):
+        total = total + cost_p[:, k]
+    inv = torch.tensor(1.0 / (float(n) * float(p)), dtype=torch.float64).to(torch.float32)
+    return total * inv, cost_p, d, perm1, perm2, inv
+
+
+class TorchSlicedWassersteinFunction(Function):
+    """The CPU path of ``sliced_wasserstein`` as one autograd node: ``(t1, t2, directions) -> cost[B]``; the backward
+    holds the permutations constant, as the library does."""
+
+    @staticmethod
+    def forward(ctx: Any, *args: Any, **kwargs: Any) -> torch.Tensor:
+        t1, t2, theta = args
+        cost, _cost_p, d, perm1, perm2, inv = _sw_forward(t1, t2, theta)
+        ctx.save_for_backward(d, perm1, perm2, theta, inv)
+        return cost
+
+    @staticmethod
+    def backward(ctx: Any, *grad_outputs: Any) -> Any:
+        d, perm1, perm2, theta, inv = ctx.saved_tensors
+        g = grad_outputs[0]
+        scale = ((g if g.dtype == torch.float32 else g.float()) * (2 * inv))[:, None, None]
+
+        def grad(perm: torch.Tensor, diff: torch.Tensor) -> torch.Tensor:
+            by_point = torch.empty_like(diff).scatter_(2, perm, diff)  # [B,P,N]: rank -> point, a permutation
+            return torch.einsum('bpn,pc->bnc', by_point, theta) * scale
+
+        return (grad(perm1, d) if ctx.needs_input_grad[0] else None, grad(perm2, -d) if ctx.needs_input_grad[1] else None, None)
+
+
+def torch_sliced_wasserstein(t1: torch.Tensor, t2: torch.Tensor, directions: torch.Tensor,
+                             return_per_direction: bool = False) -> Any:
+    """Sliced Wasserstein distance ``[B]`` of CPU clouds ``t1[B,N,3]``, ``t2[B,N,3]`` along ``directions[P,3]``: the
+    contract of ``pcc_sliced_wasserstein`` in torch; ``cost`` and, with ``return_per_direction``, ``cost_p[B,P]`` (no
+    gradient) equal the library's word for word."""
+    for name, t in (('t1', t1), ('t2', t2), ('directions', directions)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f'{name} must be torch.float32, found {t.dtype}')
+    if t1.dim() != 3 or t1.size(2) != 3 or t2.shape != t1.shape or t1.size(1) < 1:
+        raise ValueError(f'clouds must be [B,N,3] of one shape with N >= 1, got {tuple(t1.shape)} and {tuple(t2.shape)}')
+    if directions.dim() != 2 or directions.size(1) != 3 or directions.size(0) < 1:
+        raise ValueError(f'directions must be [P,3] with P >= 1, got {tuple(directions.shape)}')
+    cost = TorchSlicedWassersteinFunction.apply(t1, t2, directions)
+    if return_per_direction:
+        with torch.no_grad():
+            return cost, _sw_forward(t1, t2, directions)[1]
+    return cost
+
+
+class SlicedWassersteinFunction(Function):
+    """``(t1[B,N,3], t2[B,N,3], directions[P,3]) -> cost[B]`` on the accelerator, one autograd node: the forward call
+    (``pcc_sliced_wasserstein``) also computes the unscaled gradient of every input that asks for one -- they come out of
+    the sort the cost needs -- and the backward multiplies by the upstream ``g[b]``."""
+
+    @staticmethod
+    def forward(ctx: Any, *args: Any, **kwargs: Any) -> torch.Tensor:
+        t1, t2, theta = args
+        need1, need2 = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        cost, _cost_p, g1, g2 = backend.SlicedWasserstein(t1, t2, theta, need1, need2)
+        ctx.save_for_backward(*(g for g in (g1, g2) if g is not None))
+        ctx.needs = (need1, need2)
+        return cost
+
+    @staticmethod
+    def backward(ctx: Any, *grad_outputs: Any) -> Any:
+        saved = list(ctx.saved_tensors)
+        g = grad_outputs[0]
+        scale = (g if g.dtype == torch.float32 else g.float())[:, None, None]
+        grad1 = saved.pop(0) * scale if ctx.needs[0] else None
+        grad2 = saved.pop(0) * scale if ctx.needs[1] else None
+        return grad1, grad2, None
+
+
+def sliced_wasserstein(t1: torch.Tensor, t2: torch.Tensor, n_projections: int = 128, directions: torch.Tensor | None = None,
+                       generator: torch.Generator | None = None) -> torch.Tensor:
+    """Sliced Wasserstein loss ``[B]`` between clouds of equal size ``t1[B,N,3]`` and ``t2[B,N,3]``: the mean over the
+    directions and the points of the squared difference of the two clouds' sorted projections -- the squared
+    2-Wasserstein distance of the projected clouds, a transport distance whose cost is a sort.  ``directions[P,3]`` is used
+    as given (not normalised); without it ``random_directions(n_projections, t1.device, generator)`` is drawn per call.
+    Gradients flow to the clouds with the sorted order held constant; the directions get none.  CPU tensors take
+    ``torch_sliced_wasserstein``, the same contract in torch (N <= 8192 on the accelerator)."""
+    if directions is None:
+        directions = random_directions(n_projections, t1.device, generator)
+    if t1.device.type == 'cpu':
+        return torch_sliced_wasserstein(t1, t2, directions)
+    return SlicedWassersteinFunction.apply(t1, t2, directions)

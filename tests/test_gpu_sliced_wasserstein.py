@@ -1,0 +1,257 @@
+"""GPU tests of the sliced Wasserstein loss (``pcc_sliced_wasserstein`` through the C ABI with guarded, NaN-prefilled
+buffers, and through ``losses.sliced_wasserstein``) against the numpy reference of tests/sliced_wasserstein_reference.py:
+``cost_p`` and ``cost`` word for word at every size where the kernel changes shape, ties and signed zeros, the gradient
+word for word on inputs whose intermediates are exact and inside the summation bound on Gaussian ones, determinism and
+independence of the batch, every subset of the outputs, aliasing, non-finite input, the refusals, and autograd."""
+
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from pointcloudcounterfactual_amd.losses import sliced_wasserstein, torch_sliced_wasserstein  # noqa: F401  (no feature, no test)
+from tests import sliced_wasserstein_reference as ref
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -1234.5  # what the guard behind every output must keep
+GUARD = 64
+ALL = ('cost', 'cost_p', 'grad_x', 'grad_y')
+PCC_EINVAL = -22
+
+
+def _dev(a, cuda):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+
+
+def _same_words(a, b):
+    return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
+
+
+def _shapes(b, n, p):
+    return {'cost': (b,), 'cost_p': (b, p), 'grad_x': (b, n, 3), 'grad_y': (b, n, 3)}
+
+
+def _call(x, y, theta, want=ALL):
+    """``pcc_sliced_wasserstein`` on device tensors for the outputs named in ``want`` (null pointers for the others):
+    ``{name: numpy}``.  The outputs start as NaN with sentinels behind them: every element must be written, nothing else."""
+    from pointcloudcounterfactual_amd import _lib
+
+    b, n, _ = x.shape
+    p = theta.shape[0]
+    shapes = _shapes(b, n, p)
+    bufs = {}
+    for name in want:
+        size = int(np.prod(shapes[name]))
+        bufs[name] = torch.full((size + GUARD,), SENTINEL, dtype=torch.float32, device=x.device)
+        bufs[name][:size] = float('nan')
+    _lib.call(_lib.lib.pcc_sliced_wasserstein, 'sliced_wasserstein', x.device, b, n, p, x.data_ptr(), y.data_ptr(), theta.data_ptr(),
+              *[bufs[name].data_ptr() if name in bufs else None for name in ALL])
+    out = {}
+    for name in want:
+        host, size = bufs[name].cpu().numpy(), int(np.prod(shapes[name]))
+        assert (host[size:] == np.float32(SENTINEL)).all(), name
+        out[name] = host[:size].reshape(shapes[name]).copy()
+    return out
+
+
+def _run(cuda, x, y, theta, want=ALL):
+    return _call(_dev(x, cuda), _dev(y, cuda), _dev(theta, cuda), want)
+
+
+@pytest.mark.parametrize('n', ref.N_GRID)
+def test_cost_word_for_word(cuda, n):
+    """Every p of the grid; b in {1, 3} and the clouds' scale (unit, 1000 around 300, 1e-3) rotate.  The gradients ride along
+    and must be inside the summation bound."""
+    for j, p in enumerate(ref.P_GRID):
+        b = (1, 3)[j % 2]
+        scale, shift = ((1.0, 0.0), (1000.0, 300.0), (1e-3, 0.0))[j % 3]
+        x, y = ref.clouds(100 * n + p, b, n, scale, shift)
+        theta = ref.unit_directions(n + p, p)
+        want = ref.Forward(x, y, theta)
+        got = _run(cuda, x, y, theta)
+        assert _same_words(got['cost_p'], want.cost_p), (n, p)
+        assert _same_words(got['cost'], want.cost), (n, p)
+        ref.Grad(want, theta).check_bound(got['grad_x'], got['grad_y'])
+
+
+@pytest.mark.parametrize('n', ref.N_GRID)
+def test_every_variant_returns_the_words_of_the_product(cuda, n):
+    """Every (threads, elements per thread) variant that holds n, forced through the ``sw_path`` switch, over the p of the
+    forward grid: all four outputs word for word those of the product's choice, which the test above holds against the
+    reference."""
+    from pointcloudcounterfactual_amd import _lib
+
+    for j, p in enumerate(ref.P_GRID):
+        x, y = ref.clouds(100 * n + p, (1, 3)[j % 2], n)
+        xd, yd, td = _dev(x, cuda), _dev(y, cuda), _dev(ref.unit_directions(n + p, p), cuda)
+        product = _call(xd, yd, td)
+        for variant, capacity in enumerate(ref.VARIANT_CAPACITY, 1):
+            if capacity >= n:
+                with _lib.tuning('sw_path', variant):
+                    got = _call(xd, yd, td)
+                for name in ALL:
+                    assert _same_words(got[name], product[name]), (n, p, variant, name)
+
+
+@pytest.mark.parametrize('n,p', [(64, 8), (256, 4), (128, 128), (1024, 16), (2048, 2), (4096, 32), (8192, 1), (8192, 16), (65, 16), (1000, 9), (5, 3)])
+def test_ties_and_exact_gradient_word_for_word(cuda, n, p):
+    """Integer-lattice clouds (|v| <= 64) with duplicated points and zeros of both signs, directions from {0, +-1/2, +-1}
+    with a row of zeros: the cost word for word, which pins the sorted values; where n p is a power of two every product
+    and partial sum of the gradient is exact, so its words are those of the float64 result, which pins the permutations
+    and the tie-break by index (two duplicates that swapped ranks would swap their gradients' d).  Elsewhere (the last three
+    cases: inv is not a power of two) the gradient is inside the bound."""
+    b = 2
+    x, y = ref.lattice_clouds(n + p, b, n)
+    theta = ref.dyadic_directions(n * p, p)
+    want = ref.Forward(x, y, theta)
+    got = _run(cuda, x, y, theta)
+    assert _same_words(got['cost_p'], want.cost_p) and _same_words(got['cost'], want.cost)
+    grad = ref.Grad(want, theta)
+    if (n * p) & (n * p - 1) == 0:
+        grad.check_exact(got['grad_x'], got['grad_y'])
+    else:
+        grad.check_bound(got['grad_x'], got['grad_y'])
+
+
+def test_gradient_inside_the_summation_bound(cuda):
+    """Gaussian clouds and unit directions: |got - ref64| <= gamma(p + 2) * 2 inv * sum_p |d theta_c| per element."""
+    worst = 0.0
+    for b, n, p in ((3, 65, 7), (2, 1000, 128), (2, 2048, 129), (1, 2049, 17), (1, 8192, 24), (3, 3, 9)):
+        x, y = ref.clouds(n * p, b, n, shift=0.25)
+        theta = ref.unit_directions(n + p, p)
+        grad = ref.Grad(ref.Forward(x, y, theta), theta)
+        got = _run(cuda, x, y, theta, ('grad_x', 'grad_y'))
+        worst = max(worst, grad.ratio(got['grad_x'], got['grad_y']))
+        grad.check_bound(got['grad_x'], got['grad_y'])
+    print(f'gradients: the largest error is {worst:.3f} of the bound')
+
+
+def test_determinism_and_independence_of_the_batch(cuda):
+    """The same call twice, and a cloud alone against the same cloud at position 2 of 3: identical words in all four
+    outputs, with one chunk of directions and with several."""
+    for n, p in ((700, 5), (2048, 40), (5000, 9)):
+        x, y = ref.clouds(n + p, 3, n)
+        theta = ref.unit_directions(p, p)
+        first, second = _run(cuda, x, y, theta), _run(cuda, x, y, theta)
+        alone = _run(cuda, x[2:], y[2:], theta)
+        for name in ALL:
+            assert _same_words(first[name], second[name]), (name, n, p)
+            assert _same_words(first[name][2:], alone[name]), (name, n, p)
+
+
+def test_every_subset_of_the_outputs(cuda):
+    """Each of the 15 non-empty subsets returns the words of the full call (the guards are checked in ``_call``); with no
+    output nothing is written."""
+    for n, p in ((300, 5), (300, 20)):
+        x, y = ref.clouds(n, 2, n)
+        theta = ref.unit_directions(p, p)
+        xd, yd, td = _dev(x, cuda), _dev(y, cuda), _dev(theta, cuda)
+        full = _call(xd, yd, td)
+        for k in range(1, 4):
+            for want in itertools.combinations(ALL, k):
+                got = _call(xd, yd, td, want)
+                for name in want:
+                    assert _same_words(got[name], full[name]), (want, name, p)
+        assert _call(xd, yd, td, ()) == {}
+
+
+def test_aliased_clouds_cost_exactly_zero(cuda):
+    for n, p in ((513, 8), (2048, 24)):
+        x, _ = ref.clouds(n, 2, n)
+        xd, td = _dev(x, cuda), _dev(ref.unit_directions(p, p), cuda)
+        got = _call(xd, xd, td)
+        assert (got['cost'].view(np.uint32) == 0).all() and (got['cost_p'].view(np.uint32) == 0).all()
+        assert (got['grad_x'] == 0).all() and (got['grad_y'] == 0).all()
+
+
+def test_non_finite_input_stays_in_its_cloud(cuda):
+    """One cloud of three has NaN, +inf and -inf coordinates: its cost is NaN, the other clouds' words are unchanged."""
+    n, p = 1000, 20
+    x, y = ref.clouds(77, 3, n)
+    theta = ref.unit_directions(78, p)
+    clean = _run(cuda, x, y, theta)
+    x[1, 3, 0], x[1, 500, 1], y[1, 7, 2], y[1, 999, 0] = np.nan, np.inf, -np.inf, np.nan
+    sick = _run(cuda, x, y, theta)
+    assert np.isnan(sick['cost'][1])
+    for name in ALL:
+        for k in (0, 2):
+            assert _same_words(sick[name][k], clean[name][k]), (name, k)
+    want = ref.Forward(x, y, theta)
+    for k in (0, 2):
+        assert _same_words(sick['cost_p'][k], want.cost_p[k])
+    assert np.array_equal(np.isnan(sick['cost_p'][1]), np.isnan(want.cost_p[1]))
+
+
+def test_refusals_leave_the_buffers_alone(cuda):
+    """``PCC_EINVAL`` for n = 0, n = 8193, p = 0, b = 65536 and each required null pointer; b = 0 is accepted."""
+    from pointcloudcounterfactual_amd import _lib
+
+    L = _lib.lib
+    x = torch.zeros(8, 3, device=cuda)
+    theta = torch.ones(4, 3, device=cuda)
+    outs = [torch.full((64,), SENTINEL, device=cuda) for _ in ALL]
+    stream = torch.cuda.current_stream(cuda).cuda_stream
+
+    def status(b, n, p, ptrs=None):
+        ptrs = [x.data_ptr(), x.data_ptr(), theta.data_ptr()] if ptrs is None else ptrs
+        return L.pcc_sliced_wasserstein(b, n, p, *ptrs, *[o.data_ptr() for o in outs], stream)
+
+    for b, n, p in ((1, 0, 4), (1, 8193, 4), (1, 8, 0), (65536, 8, 4)):
+        assert status(b, n, p) == PCC_EINVAL, (b, n, p)
+    for missing in range(3):
+        ptrs = [x.data_ptr(), x.data_ptr(), theta.data_ptr()]
+        ptrs[missing] = None
+        assert status(1, 8, 4, ptrs) == PCC_EINVAL, missing
+        assert L.pcc_last_error().decode() == 'sliced_wasserstein: null pointer'
+    assert status(0, 8, 4) == 0
+    torch.cuda.synchronize()
+    for o in outs:
+        assert (o.cpu().numpy() == np.float32(SENTINEL)).all()
+
+
+def test_python_layer(cuda):
+    """``loss.backward()`` with a non-uniform upstream gradient, float32 and float64, against the C entry and the CPU
+    path; ``requires_grad`` on one input only; a CPU tensor takes the torch path; a non-contiguous, wrong-dtype or
+    wrong-device tensor raises through ``_lib.ptr``."""
+    from pointcloudcounterfactual_amd import losses
+
+    b, n, p = 3, 600, 20
+    x, y = ref.clouds(91, b, n)
+    theta = ref.unit_directions(92, p)
+    xd, yd, td = _dev(x, cuda), _dev(y, cuda), _dev(theta, cuda)
+    raw = _call(xd, yd, td)
+    up = np.array([1.0, -2.0, 0.5], dtype=np.float32)  # powers of two: scaling by them is exact
+    for dtype in (torch.float32, torch.float64):
+        tx, ty = xd.clone().requires_grad_(True), yd.clone().requires_grad_(True)
+        loss = losses.sliced_wasserstein(tx, ty, directions=td)
+        assert loss.dtype == torch.float32 and _same_words(loss.detach().cpu().numpy(), raw['cost'])
+        (loss.to(dtype) * _dev(up, cuda).to(dtype)).sum().backward()
+        assert tx.grad.dtype == torch.float32
+        assert _same_words(tx.grad.cpu().numpy(), raw['grad_x'] * up[:, None, None])
+        assert _same_words(ty.grad.cpu().numpy(), raw['grad_y'] * up[:, None, None])
+    cx, cy = torch.from_numpy(x).requires_grad_(True), torch.from_numpy(y).requires_grad_(True)
+    cpu_loss = losses.sliced_wasserstein(cx, cy, directions=torch.from_numpy(theta))
+    assert _same_words(cpu_loss.detach().numpy(), raw['cost'])
+    (cpu_loss * torch.from_numpy(up)).sum().backward()
+    grad = ref.Grad(ref.Forward(x, y, theta), theta)
+    grad.check_bound(cx.grad.numpy() / up[:, None, None].astype(np.float64), cy.grad.numpy() / up[:, None, None].astype(np.float64))
+    grad.check_bound(raw['grad_x'].astype(np.float64), raw['grad_y'].astype(np.float64))
+    for needs in ((True, False), (False, True)):
+        tx, ty = xd.clone().requires_grad_(needs[0]), yd.clone().requires_grad_(needs[1])
+        losses.sliced_wasserstein(tx, ty, directions=td).sum().backward()
+        assert (tx.grad is not None, ty.grad is not None) == needs
+        asked, name = (tx, 'grad_x') if needs[0] else (ty, 'grad_y')
+        assert _same_words(asked.grad.cpu().numpy(), raw[name])
+    drawn = losses.sliced_wasserstein(xd, yd, 16, generator=torch.Generator().manual_seed(1))
+    again = losses.sliced_wasserstein(xd, yd, directions=losses.random_directions(16, cuda, torch.Generator().manual_seed(1)))
+    assert drawn.shape == (b,) and torch.equal(drawn, again)
+    with pytest.raises(RuntimeError, match='must be contiguous'):
+        losses.sliced_wasserstein(xd.transpose(0, 1).contiguous().transpose(0, 1), yd, directions=td)
+    with pytest.raises(RuntimeError, match='must be torch.float32'):
+        losses.sliced_wasserstein(xd.double(), yd.double(), directions=td.double())
+    with pytest.raises(RuntimeError, match='must be a CUDA tensor'):
+        losses.sliced_wasserstein(xd, yd, directions=torch.from_numpy(theta))
+    with pytest.raises(RuntimeError, match='must be a CUDA tensor'):
+        losses.sliced_wasserstein(xd, torch.from_numpy(y), directions=td)
