@@ -253,6 +253,45 @@ int pcc_match_cost(int b, int n, int m, const float *xyz1, const float *xyz2, co
 int pcc_sliced_wasserstein(int b, int n, int p, const float *x, const float *y, const float *theta, float *cost,
                            float *cost_p, float *grad_x, float *grad_y, pcc_stream_t stream);
 
+/* ---- Sinkhorn divergence (extension) ---------------------------------------------------------------
+ * The entropic optimal-transport loss between paired clouds, debiased: what GeomLoss's SamplesLoss("sinkhorn", p=2)
+ * computes with uniform weights.  x[b,n,3], y[b,m,3] float32, n and m independent; weights a_i = 1/n, b_j = 1/m; pair cost
+ * C(u,v) = |u - v|^2 / 2.  T = steps, eps_t = eps[t]: a HOST array of T temperatures (squared lengths), read when the call
+ * is enqueued.  No counterpart in the reference.
+ *   smoothed minimum   SM_eps(h; U->V)_i = -eps log sum_j exp(-log|V| + (h_j - C(u_i, v_j)) / eps), evaluated with its
+ *               largest term subtracted: finite for any finite input and any eps > 0.  C is formed from coordinate
+ *               differences, never from the expanded |u|^2 + |v|^2 - 2 u.v.
+ *   potentials  f on x against y, g on y against x, p on x against x, q on y against y; all four are updated at once from
+ *               the previous values (every launch reads one buffer and writes another):
+ *                 initialisation, eps_0:    f = SM(0; x->y), g = SM(0; y->x), p = SM(0; x->x), q = SM(0; y->y)
+ *                 t = 0 .. T-1, eps_t:      f <- (f + SM(g; x->y)) / 2, g <- (g + SM(f_old; y->x)) / 2,
+ *                                           p <- (p + SM(p; x->x)) / 2, q <- (q + SM(q; y->y)) / 2
+ *                 final, eps_{T-1}:         f* = SM(g; x->y), g* = SM(f; y->x), p* = SM(p; x->x), q* = SM(q; y->y)
+ *               (not averaged, all from the pre-final values): T + 2 all-pairs rounds, GeomLoss's symmetric scheme with
+ *               eps[0] used twice.
+ *   outputs     pot_x[b,n] = f* - p*, pot_y[b,m] = g* - q* with debias != 0; f*, g* with debias == 0 (p and q are then never
+ *               computed).  cost[b] = inv_n * tree(pot_x[b,:]) + inv_m * tree(pot_y[b,:]): tree = the halving tree of
+ *               pcc_sliced_wasserstein (pad with +0 to a power of two L, then for h = L/2 .. 1: e_i = e_i + e_{i+h}); inv_n,
+ *               inv_m = the float32 nearest to 1/n, 1/m, formed in double on the host; two products and one sum.
+ *   gradients   of cost[b] with the other cloud and the pre-final potentials held constant (GeomLoss's convention):
+ *               grad_x[b,i,:] = inv_n (sum_j P_ij (x_i - y_j) - sum_k Pxx_ik (x_i - x_k)), P_i. = the softmax row of the
+ *               final x->y round, Pxx that of the final x->x round (dropped with debias == 0); grad_y symmetrically.  They are
+ *               accumulated from coordinate differences inside the final round; no plan is stored.
+ *   words       no float atomics and a fixed order of every sum, which depends on n and m only: the words of a cloud's
+ *               outputs are the same from run to run, at any position of the batch and for any b.
+ * Any subset of the five outputs may be NULL; with all five NULL nothing is enqueued.  x and y may alias: with debias != 0
+ * the cost and both gradients are then exactly +0 (f and p, g and q are the same function of the same words).
+ * Non-finite coordinates: a cloud holding a NaN or an infinite coordinate gets a non-finite cost; the other clouds of
+ * the batch are unaffected.
+ * Requires 1 <= n, m <= 65536, 1 <= steps <= PCC_SINKHORN_MAX_STEPS, every eps[t] finite and > 0, b <= 65535 and non-null x,
+ * y, eps (PCC_EINVAL otherwise, before anything is enqueued); b = 0 enqueues nothing and returns PCC_OK.  64-bit offsets
+ * throughout.  Workspace (two generations of the four potentials, the per-row partial sums of the final round) comes
+ * from the library's private pool (PCC_ENOMEM if that fails). */
+#define PCC_SINKHORN_MAX_STEPS 256
+int pcc_sinkhorn(int b, int n, int m, const float *x, const float *y, int steps, const float *eps /* HOST, [steps] */,
+                 int debias, float *cost /*[b]*/, float *pot_x /*[b,n]*/, float *pot_y /*[b,m]*/, float *grad_x /*[b,n,3]*/,
+                 float *grad_y /*[b,m,3]*/, pcc_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -24,6 +24,8 @@ int pcc_test_inject_approxmatch_failure(void);
  * behaviour).  They replace the PCC_* environment variables earlier rounds read inside the product library: nothing
  * in the product path selects behaviour from the environment any more.  Returns 1 when armed. */
 enum {
+    PCC_TUNE_SINKHORN_SPLIT = 0,   /* pcc_sinkhorn: S >= 1 = the columns of every scan in up to S slices (16 at the most, none shorter than a
+                                      256-column tile); 0 = by n and m.  (Key 0: the last free slot of the table.) */
     PCC_TUNE_SW_PATH = 1,          /* pcc_sliced_wasserstein: 1..10 = the variant (threads, elements per thread) = (64,1) (64,2) (64,4) (128,4)
                                       (256,4) (512,4) (1024,4) (1024,8) (256,8) (512,8); a variant that cannot hold n is ignored.  (Key 1: a
                                       slot a retired switch left free.) */

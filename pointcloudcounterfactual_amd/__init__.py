@@ -13,8 +13,11 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     match_cost,
     nn_distance,
     random_directions,
+    sinkhorn_divergence,
+    sinkhorn_schedule,
     sliced_wasserstein,
     torch_chamfer,
+    torch_sinkhorn,
     torch_sliced_wasserstein,
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
@@ -35,4 +38,4 @@ __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer
            'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'group_points', 'sample_and_group',
            'occupancy_grid', 'jsd_between_sets', 'interpolation_weights', 'interpolate_points', 'feature_propagation',
            'local_covariance', 'local_geometry', 'estimate_normals', 'sliced_wasserstein', 'torch_sliced_wasserstein',
-           'random_directions']
+           'random_directions', 'sinkhorn_divergence', 'sinkhorn_schedule', 'torch_sinkhorn']

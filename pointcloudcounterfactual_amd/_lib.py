@@ -54,6 +54,7 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_matchcostgrad_scaled': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_match_cost': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_sliced_wasserstein': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_sinkhorn': (_int, [_int, _int, _int, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/pcc_neighbour.h
     'pcc_knn': (_int, [_int, _int, _int, _int, _vp, _vp, _vp]),
     'pcc_knn_cross': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
@@ -143,7 +144,7 @@ def call(fn: Any, what: str, device: torch.device, *args: Any) -> None:
 # include/pcc_test_hooks.h: measurement / bit-identity switches (inert unless PCC_TEST_HOOKS=1 is in the environment)
 TUNING = {'am_nocull': 2, 'am_nosplit': 3, 'am_noresident': 4, 'edge_scatter': 5, 'nbrsum_scatter': 6,
           'auction_cluster': 7, 'knn_nosplit': 8, 'knn_wide': 9, 'knn_cross_split': 10, 'fps_path': 11, 'occupancy_path': 12,
-          'ball_path': 13, 'group_path': 14, 'interp_path': 15, 'sw_path': 1}
+          'ball_path': 13, 'group_path': 14, 'interp_path': 15, 'sw_path': 1, 'sinkhorn_split': 0}
 
 
 def set_tuning(name: str, value: int) -> None:

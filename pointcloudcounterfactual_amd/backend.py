@@ -8,6 +8,8 @@ only used for device memory and the stream handle.
 
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from pointcloudcounterfactual_amd import _lib
@@ -252,3 +254,24 @@ def SlicedWasserstein(set_d: torch.Tensor, set_q: torch.Tensor, theta: torch.Ten
          ptr(theta, 'directions', F32, dev), ptr(cost, 'cost', F32, dev), ptr(cost_p, 'cost_p', F32, dev),
          ptr(g1, 'grad1', F32, dev), ptr(g2, 'grad2', F32, dev))
     return [cost, cost_p, g1, g2]
+
+
+def Sinkhorn(set_d: torch.Tensor, set_q: torch.Tensor, eps: list[float], debias: bool = True, grad1: bool = False,
+             grad2: bool = False, potentials: bool = False) -> list[torch.Tensor | None]:
+    """Sinkhorn divergence between paired clouds ``set_d[B,N,3]``, ``set_q[B,M,3]`` along the temperature schedule ``eps``
+    (extension, ``pcc_sinkhorn``) -> [cost[B], pot1[B,N] or None, pot2[B,M] or None, grad1[B,N,3] or None, grad2[B,M,3] or
+    None]: the gradients of ``cost`` (upstream gradient 1), each computed only when asked for."""
+    if set_d.dim() != 3 or set_q.dim() != 3 or set_d.size(2) != 3 or set_q.size(2) != 3 or set_d.size(0) != set_q.size(0):
+        raise ValueError(f'Sinkhorn: clouds must be [B,N,3] and [B,M,3], got {tuple(set_d.shape)} and {tuple(set_q.shape)}')
+    b, n, m = _sizes(set_d, set_q)
+    dev = set_d.device
+    sched = (ctypes.c_float * len(eps))(*eps)  # read by the library before the call returns
+    cost = torch.empty((b,), dtype=torch.float32, device=dev)
+    p1 = torch.empty((b, n), dtype=torch.float32, device=dev) if potentials else None
+    p2 = torch.empty((b, m), dtype=torch.float32, device=dev) if potentials else None
+    g1 = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if grad1 else None
+    g2 = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if grad2 else None
+    call(_L.pcc_sinkhorn, 'Sinkhorn', dev, b, n, m, ptr(set_d, 'set_d', F32, dev), ptr(set_q, 'set_q', F32, dev), len(eps),
+         ctypes.cast(sched, ctypes.c_void_p), int(bool(debias)), ptr(cost, 'cost', F32, dev), ptr(p1, 'pot1', F32, dev),
+         ptr(p2, 'pot2', F32, dev), ptr(g1, 'grad1', F32, dev), ptr(g2, 'grad2', F32, dev))
+    return [cost, p1, p2, g1, g2]

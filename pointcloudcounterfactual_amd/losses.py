@@ -9,6 +9,7 @@ computes with PyKeOps (``src/train/metrics_and_losses.py:21-41``), expressed thr
 
 from __future__ import annotations
 
+import math
 from typing import Any
 
 import torch
@@ -309,3 +310,162 @@ def sliced_wasserstein(t1: torch.Tensor, t2: torch.Tensor, n_projections: int = 
     if t1.device.type == 'cpu':
         return torch_sliced_wasserstein(t1, t2, directions)
     return SlicedWassersteinFunction.apply(t1, t2, directions)
+
+
+def sinkhorn_schedule(blur: float, scaling: float, diameter: float) -> list[float]:
+    """GeomLoss's epsilon-scaling for the cost ``|u - v|^2 / 2``: the temperatures ``[diameter^2]``, then ``exp(v)`` for ``v`` in
+    ``arange(2 log diameter, 2 log blur, 2 log scaling)``, then ``[blur^2]``.  (0.05, 0.5, 2.0) gives 4, 4, 1, 0.25, 0.0625,
+    0.015625, 0.00390625, 0.0025: 8 steps, 10 all-pairs rounds."""
+    if not (blur > 0 and diameter > 0 and 0 < scaling < 1) or not all(math.isfinite(v) for v in (blur, scaling, diameter)):
+        raise ValueError(f'sinkhorn_schedule: need blur > 0, diameter > 0 and 0 < scaling < 1, got {blur}, {scaling}, {diameter}')
+    start, stop, step = 2 * math.log(diameter), 2 * math.log(blur), 2 * math.log(scaling)
+    count = max(0, math.ceil((stop - start) / step))  # (numpy's arange)
+    return [diameter**2] + [math.exp(start + i * step) for i in range(count)] + [blur**2]
+
+
+def _halving_tree(e: torch.Tensor) -> torch.Tensor:
+    """The contract's tree over the last axis: pad with +0 to a power of two, then ``e_i += e_{i+h}`` for h = L/2 .. 1."""
+    n = e.size(-1)
+    size = 1 << max(n - 1, 0).bit_length()
+    pad = torch.zeros(e.shape[:-1] + (size,), dtype=e.dtype, device=e.device)
+    pad[..., :n] = e
+    while size > 1:
+        size //= 2
+        pad = pad[..., :size] + pad[..., size:2 * size]
+    return pad[..., 0]
+
+
+def _sk_forward(t1: torch.Tensor, t2: torch.Tensor, eps: list[float], debias: bool) -> tuple[torch.Tensor, ...]:
+    """The contract of ``pcc_sinkhorn`` (include/pcc_structural.h) in float32 torch, dense: -> (cost[B], pot1[B,N], pot2[B,M],
+    grad1[B,N,3], grad2[B,M,3]), the gradients for an upstream gradient of 1."""
+    n, m = t1.size(1), t2.size(1)
+
+    def pairs(u: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        diff = u[:, :, None, :] - v[:, None, :, :]  # coordinate differences, never the expanded form
+        return diff, 0.5 * (diff * diff).sum(-1)
+
+    def softmin(e: float, cost: torch.Tensor, h: torch.Tensor | None) -> torch.Tensor:
+        arg = -cost / e if h is None else (h[:, None, :] - cost) / e
+        return -e * torch.logsumexp(arg - math.log(cost.size(2)), dim=2)  # (subtracts the largest term)
+
+    (dxy, cxy), (dyx, cyx) = pairs(t1, t2), pairs(t2, t1)  # (each its own tensor: the four scans are one function of their arguments)
+    f, g = softmin(eps[0], cxy, None), softmin(eps[0], cyx, None)
+    if debias:
+        dxx, cxx = pairs(t1, t1)
+        dyy, cyy = pairs(t2, t2)
+        p, q = softmin(eps[0], cxx, None), softmin(eps[0], cyy, None)
+    for e in eps:
+        f, g = 0.5 * (f + softmin(e, cxy, g)), 0.5 * (g + softmin(e, cyx, f))
+        if debias:
+            p, q = 0.5 * (p + softmin(e, cxx, p)), 0.5 * (q + softmin(e, cyy, q))
+    e = eps[-1]
+
+    def plan_grad(cost: torch.Tensor, diff: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+        return torch.einsum('bij,bijc->bic', torch.softmax((h[:, None, :] - cost) / e, dim=2), diff)
+
+    pot1, pot2 = softmin(e, cxy, g), softmin(e, cyx, f)
+    grad1, grad2 = plan_grad(cxy, dxy, g), plan_grad(cyx, dyx, f)
+    if debias:
+        pot1, pot2 = pot1 - softmin(e, cxx, p), pot2 - softmin(e, cyy, q)
+        grad1, grad2 = grad1 - plan_grad(cxx, dxx, p), grad2 - plan_grad(cyy, dyy, q)
+    inv_n = torch.tensor(1.0 / n, dtype=torch.float64).to(torch.float32)
+    inv_m = torch.tensor(1.0 / m, dtype=torch.float64).to(torch.float32)
+    cost = inv_n * _halving_tree(pot1) + inv_m * _halving_tree(pot2)
+    return cost, pot1, pot2, inv_n * grad1, inv_m * grad2
+
+
+def _sk_check(t1: torch.Tensor, t2: torch.Tensor, eps: list[float] | None) -> None:
+    for name, t in (('t1', t1), ('t2', t2)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f'{name} must be torch.float32, found {t.dtype}')
+    if t1.dim() != 3 or t2.dim() != 3 or t1.size(2) != 3 or t2.size(2) != 3 or t1.size(0) != t2.size(0) or t1.size(1) < 1 or t2.size(1) < 1:
+        raise ValueError(f'clouds must be [B,N,3] and [B,M,3] with N, M >= 1, got {tuple(t1.shape)} and {tuple(t2.shape)}')
+    if eps is not None and (not 1 <= len(eps) <= 256 or not all(math.isfinite(e) and e > 0 for e in eps)):
+        raise ValueError('eps must hold 1 to 256 finite temperatures > 0')
+
+
+class _SinkhornBase(Function):
+    """``(t1[B,N,3], t2[B,M,3], eps, debias, potentials, grad_mode) -> (cost[B], pot1, pot2)``, one autograd node: the forward
+    call also computes the unscaled gradient of every input that asks for one (the closed form needs the final round's
+    softmax rows, no stored plan), and the backward multiplies by the upstream ``g[b]``.  ``grad_mode`` is the caller's
+    ``torch.is_grad_enabled()``: inside ``forward`` it always reads False, and ``needs_input_grad`` stays True under
+    ``no_grad``, where no gradient will ever be asked for.  The potentials carry no gradient."""
+
+    @staticmethod
+    def run(t1: torch.Tensor, t2: torch.Tensor, eps: list[float], debias: bool, need1: bool, need2: bool, potentials: bool) -> Any:
+        raise NotImplementedError
+
+    @classmethod
+    def forward(cls, ctx: Any, *args: Any, **kwargs: Any) -> Any:
+        t1, t2, eps, debias, potentials, grad_mode = args
+        need1, need2 = bool(grad_mode and ctx.needs_input_grad[0]), bool(grad_mode and ctx.needs_input_grad[1])
+        cost, p1, p2, g1, g2 = cls.run(t1, t2, eps, debias, need1, need2, potentials)
+        ctx.save_for_backward(*(g for g in (g1, g2) if g is not None))
+        ctx.needs = (need1, need2)
+        if potentials:
+            ctx.mark_non_differentiable(p1, p2)
+        return cost, p1, p2
+
+    @staticmethod
+    def backward(ctx: Any, *grad_outputs: Any) -> Any:
+        saved = list(ctx.saved_tensors)
+        g = grad_outputs[0]
+        scale = (g if g.dtype == torch.float32 else g.float())[:, None, None]
+        grad1 = saved.pop(0) * scale if ctx.needs[0] else None
+        grad2 = saved.pop(0) * scale if ctx.needs[1] else None
+        return grad1, grad2, None, None, None, None
+
+
+class TorchSinkhornFunction(_SinkhornBase):
+    """The CPU path of ``sinkhorn_divergence``: the same contract and the same gradient convention in dense float32 torch."""
+
+    @staticmethod
+    def run(t1: torch.Tensor, t2: torch.Tensor, eps: list[float], debias: bool, need1: bool, need2: bool, potentials: bool) -> Any:
+        cost, p1, p2, g1, g2 = _sk_forward(t1, t2, eps, debias)
+        return cost, p1 if potentials else None, p2 if potentials else None, g1 if need1 else None, g2 if need2 else None
+
+
+class SinkhornFunction(_SinkhornBase):
+    """``sinkhorn_divergence`` on the accelerator (``pcc_sinkhorn``)."""
+
+    @staticmethod
+    def run(t1: torch.Tensor, t2: torch.Tensor, eps: list[float], debias: bool, need1: bool, need2: bool, potentials: bool) -> Any:
+        return backend.Sinkhorn(t1, t2, eps, debias, need1, need2, potentials)
+
+
+def torch_sinkhorn(t1: torch.Tensor, t2: torch.Tensor, eps: list[float], debias: bool = True, return_potentials: bool = False) -> Any:
+    """Sinkhorn divergence ``[B]`` of CPU clouds ``t1[B,N,3]``, ``t2[B,M,3]`` along the temperatures ``eps``: the contract of
+    ``pcc_sinkhorn`` in dense float32 torch (``torch.logsumexp``; four ``[B,N,M]``-sized tensors), with the library's
+    gradient convention as an explicit autograd node.  With ``return_potentials``: ``(cost, pot1[B,N], pot2[B,M])``."""
+    eps = [float(e) for e in eps]
+    _sk_check(t1, t2, eps)
+    cost, p1, p2 = TorchSinkhornFunction.apply(t1, t2, eps, bool(debias), bool(return_potentials), torch.is_grad_enabled())
+    return (cost, p1, p2) if return_potentials else cost
+
+
+def sinkhorn_divergence(t1: torch.Tensor, t2: torch.Tensor, blur: float = 0.05, scaling: float = 0.5, diameter: float | None = None,
+                        eps: list[float] | None = None, debias: bool = True, return_potentials: bool = False) -> Any:
+    """Debiased Sinkhorn divergence ``[B]`` between clouds ``t1[B,N,3]`` and ``t2[B,M,3]`` (N and M independent) with uniform
+    weights and the cost ``|u - v|^2 / 2``: GeomLoss's ``SamplesLoss("sinkhorn", p=2, blur, scaling)``.  ``blur`` is a length:
+    the resolution below which the loss stops telling points apart; ``scaling`` is the ratio between successive
+    temperatures' lengths (closer to 1: more rounds, closer to the converged value).  The loss is exactly 0 between a cloud
+    and itself.  ``eps``, when given, is the list of temperatures (squared lengths) and is used as is; otherwise it is
+    ``sinkhorn_schedule(blur, scaling, diameter)``.  ``diameter=None`` takes the largest per-axis extent over both clouds
+    and the whole batch, which costs ONE HOST SYNCHRONISATION per call: pass a constant (the data's known extent) when
+    training.  ``debias=False`` returns the plain entropic cost OT_eps.  One autograd node: the gradients hold the other
+    cloud and the pre-final potentials constant (GeomLoss's convention) and come out of the forward call.  With
+    ``return_potentials``: ``(cost, pot1[B,N], pot2[B,M])``, ``cost[b] = mean(pot1[b]) + mean(pot2[b])``; the potentials carry no
+    gradient.  CPU tensors take ``torch_sinkhorn``, the same contract in dense torch."""
+    _sk_check(t1, t2, None)
+    if eps is None:
+        if diameter is None:
+            both = torch.cat((t1.detach().reshape(-1, t1.size(-1)), t2.detach().reshape(-1, t2.size(-1))))
+            diameter = float((both.max(0).values.double() - both.min(0).values.double()).max())  # (the host synchronisation)
+            if not diameter > 0:
+                diameter = float(blur)  # (all points equal: one temperature, blur^2, twice)
+        eps = sinkhorn_schedule(float(blur), float(scaling), float(diameter))
+    eps = [float(e) for e in eps]
+    _sk_check(t1, t2, eps)
+    fn = TorchSinkhornFunction if t1.device.type == 'cpu' else SinkhornFunction
+    cost, p1, p2 = fn.apply(t1, t2, eps, bool(debias), bool(return_potentials), torch.is_grad_enabled())
+    return (cost, p1, p2) if return_potentials else cost
