@@ -204,6 +204,52 @@ int pcc_local_geometry(int b, int n, int m, int k, const float *xyz, const int64
 int pcc_local_covariance_bwd(int b, int n, int m, int k, const float *xyz, const int64_t *idx, const float *mean,
                              const float *grad_cov, const float *grad_mean, float *grad_xyz, pcc_stream_t stream);
 
+/* The point-voxel branch (PVCNN): point features averaged into a dense grid of res^3 cells per cloud, and a grid read back
+ * at the points by trilinear interpolation.  No counterpart in the reference; what a user writes in torch instead is an
+ * index_add_ mean and eight gathers of [b, c, n].  The grid is pcc_occupancy_grid's (include/pcc_structural.h): res points
+ * per axis over [lo, lo + extent]^3, inv = (float)(res - 1) / extent rounded once on the host.
+ *   layouts     x[b, c, n], out[b, c, n] channels-major; xyz[b, n, 3]; grid[b, c, res, res, res] with the flat cell
+ *               (i * res + j) * res + k; cell[b, n], order[b, n], counts[b, res^3] int32.  float32 and 64-bit offsets
+ *               throughout.  Coordinates carry no gradient in any of the five functions.
+ *   pcc_voxel_index   cell[b, p]: the flat cell of pcc_occupancy_grid with in_sphere = 0, rounding by rounding (t = (x - lo) *
+ *               inv, floorf(t + 0.5f) clamped to [0, res - 1] as a float: a midpoint goes up), -1 for a point with a NaN or
+ *               infinite coordinate.  counts[b, cell]: the points of cloud b in the cell, every element written, word for
+ *               word what pcc_occupancy_grid(per_cloud = 1) returns.  order[b, :]: a permutation of 0 .. n - 1, the finite
+ *               points first, ascending by (cell, point index), the non-finite ones behind them in index order.  Every word
+ *               of the three outputs is fixed by the cloud alone: not by b, the position in the batch, the variant or the run.
+ *               n <= 16384 (a cloud is sorted by one workgroup in LDS).
+ *   pcc_voxelize      for every cell and channel acc = +0.0f, then acc = acc + x[b, ch, p] over the cell's points in ascending
+ *               point index, then grid = acc / (float)count: one IEEE division.  An empty cell is +0.0, a NaN result the word
+ *               0x7fc00000.  Every word of the dense grid is written exactly once and there are no float atomics, so the
+ *               words are fixed.  cell, order and counts are those of pcc_voxel_index for the same cloud and res.  Takes
+ *               b * res^3 * 4 bytes from the library's stream-ordered workspace.
+ *   pcc_voxelize_bwd  grad_x[b, ch, p] = grad_grid[b, ch, cell] / (float)counts[cell], one division; +0.0 for cell = -1.  A
+ *               gather: the words are fixed.
+ *   pcc_devoxelize    per axis of a finite point t = fminf(fmaxf((x - lo) * inv, 0), res - 1) (two roundings, then the
+ *               clamp: a point outside the cube reads the border), i0 = min((int)floorf(t), res - 2), f = t - (float)i0
+ *               (exact), w1 = f, w0 = 1.f - f.  The weight of corner (di, dj, dk) is (wx * wy) * wz, two rounded products.
+ *               out[b, ch, p]: acc = +0.0f, then over the corners 000, 001, 010, ... 111 acc = acc + (w * grid[corner]), a
+ *               rounded product and a rounded sum each, not an fmaf.  A NaN result is the word 0x7fc00000; a non-finite
+ *               point gives +0.0 and carries no gradient.  Every word is fixed by the point, the grid row and the scalars.
+ *   pcc_devoxelize_bwd  grad_grid[b, ch, cell] = sum of w * grad_out[b, ch, p] (one rounded product, the forward's w) over
+ *               the finite points and their corners; every element is written, +0.0 where nothing points.  The products are
+ *               accumulated with float atomics (LDS bins streamed out whole for res <= 32, a zero fill and global atomics
+ *               above): as in pcc_group_points_bwd the float summation order of this one output is not fixed.
+ * Requires c >= 1, n >= 1, 2 <= res <= 128, extent finite and > 0 with a finite positive inv, lo finite, b <= 65535,
+ * b * n <= INT_MAX, b * res^3 <= INT_MAX and non-null pointers (PCC_EINVAL otherwise, under "voxel_index:", "voxelize:",
+ * "voxelize_bwd:", "devoxelize:", "devoxelize_bwd:", before anything is enqueued).  b = 0 enqueues nothing and returns
+ * PCC_OK.  No host synchronisation: the calls can be captured into a graph. */
+int pcc_voxel_index(int b, int n, const float *xyz, int res, float lo, float extent, int32_t *cell, int32_t *order,
+                    int32_t *counts, pcc_stream_t stream);
+int pcc_voxelize(int b, int c, int n, int res, const float *x, const int32_t *cell, const int32_t *order,
+                 const int32_t *counts, float *grid, pcc_stream_t stream);
+int pcc_voxelize_bwd(int b, int c, int n, int res, const int32_t *cell, const int32_t *counts, const float *grad_grid,
+                     float *grad_x, pcc_stream_t stream);
+int pcc_devoxelize(int b, int c, int n, int res, float lo, float extent, const float *grid, const float *xyz, float *out,
+                   pcc_stream_t stream);
+int pcc_devoxelize_bwd(int b, int c, int n, int res, float lo, float extent, const float *xyz, const float *grad_out,
+                       float *grad_grid, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

@@ -21,7 +21,9 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     torch_sliced_wasserstein,
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
+    VoxelIndex,
     ball_query,
+    devoxelize,
     estimate_normals,
     farthest_point_sample,
     feature_propagation,
@@ -30,7 +32,10 @@ from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     interpolation_weights,
     local_covariance,
     local_geometry,
+    point_voxel,
     sample_and_group,
+    voxel_index,
+    voxelize,
 )
 from pointcloudcounterfactual_amd.set_metrics import jsd_between_sets, occupancy_grid  # noqa: F401
 
@@ -38,4 +43,5 @@ __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer
            'backend', 'set_metrics', 'farthest_point_sample', 'ball_query', 'group_points', 'sample_and_group',
            'occupancy_grid', 'jsd_between_sets', 'interpolation_weights', 'interpolate_points', 'feature_propagation',
            'local_covariance', 'local_geometry', 'estimate_normals', 'sliced_wasserstein', 'torch_sliced_wasserstein',
-           'random_directions', 'sinkhorn_divergence', 'sinkhorn_schedule', 'torch_sinkhorn']
+           'random_directions', 'sinkhorn_divergence', 'sinkhorn_schedule', 'torch_sinkhorn', 'VoxelIndex', 'voxel_index',
+           'voxelize', 'devoxelize', 'point_voxel']

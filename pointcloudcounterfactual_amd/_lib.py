@@ -66,6 +66,11 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_interpolate_bwd': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     'pcc_local_geometry': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_local_covariance_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_voxel_index': (_int, [_int, _int, _vp, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    'pcc_voxelize': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_voxelize_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_devoxelize': (_int, [_int, _int, _int, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    'pcc_devoxelize_bwd': (_int, [_int, _int, _int, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_graph_features': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
