@@ -92,7 +92,13 @@ int pcc_chamfer_loss_grad(int b, int n, const float *xyz1, int m, const float *x
 
 /* Forward of the reference's ChamferEMD reconstruction loss (src/train/metrics_and_losses.py:70-79: Chamfer and
  * match_cost on the same pair of clouds) in one call: pcc_chamfer_loss + pcc_match_cost, same outputs, same bits.
- * emd_grad1 / emd_grad2: both or neither (NULL: cost only). */
+ * emd_grad1 / emd_grad2: both or neither (NULL: cost only).
+ * Non-finite coordinates: the VALUES are specified for finite coordinates only (the chunk quirks of pcc_nndistance above
+ * are not reproduced).  For ANY input, every index written to idx1 lies in [0, m) and every index written to idx2 in
+ * [0, n), so the backward below never gathers outside a cloud.  A query point with a NaN coordinate -- and any query
+ * whose every candidate distance is NaN -- gets distance NaN / index 0, as in pcc_nndistance, which makes the sample's
+ * chamfer_loss NaN.  The samples of the batch without a non-finite coordinate are unaffected: same bits as without the
+ * others. */
 int pcc_chamfer_emd(int b, int n, const float *xyz1, int m, const float *xyz2, int mean, float *chamfer_loss,
                     float *dist1, int *idx1, float *dist2, int *idx2, float *emd_cost, float *emd_grad1,
                     float *emd_grad2, pcc_stream_t stream);

@@ -11,7 +11,7 @@ namespace {
 // Spatial sort: one workgroup per (sample, cloud) orders the points along a 30-bit Hilbert curve with a
 // bitonic sort of (code << 32 | index) keys in LDS and writes the sorted SoA coordinates, the inverse
 // permutation (rank) and one bounding box per 16 consecutive sorted points.  Clouds too large for the LDS
-// sort (> 16384 points) keep their original order: culling then simply finds little to skip.
+// sort (> 32768 points = 64 keys per thread) keep their original order: culling then simply finds little to skip.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned part1by2(unsigned v) {
     v &= 0x3ff;
@@ -338,7 +338,10 @@ __global__ __launch_bounds__(kSortT) void am_sort_kernel(SortArgs a) {
 }
 
 void launch_sort(const SortArgs &a, int slots, dim3 grid, hipStream_t st) {
-    pcc::ProfScope prof("am_sort_kernel", st);
+    // (the profiler names the instantiation; the prefix "am_sort_kernel" still counts them all)
+    const char *name = slots == 4 ? "am_sort_kernel<4>" : slots == 8 ? "am_sort_kernel<8>" : slots == 16 ? "am_sort_kernel<16>"
+                     : slots == 32 ? "am_sort_kernel<32>" : "am_sort_kernel<64>";
+    pcc::ProfScope prof(name, st);
     switch (slots) {
     case 4: hipLaunchKernelGGL((am_sort_kernel<4>), grid, dim3(kSortT), 0, st, a); break;
     case 8: hipLaunchKernelGGL((am_sort_kernel<8>), grid, dim3(kSortT), 0, st, a); break;
@@ -369,7 +372,7 @@ int sort_clouds(const AmDims &L, const WsView &v, int bc, const float *xyz1, con
     for (int w = 0; w < 2; w++) {
         int npad = 4 * kSortT;
         while (npad < nn[w]) npad <<= 1;
-        if (npad > 64 * kSortT) npad = 0;  // > 16384 points: keep the original order (nothing is culled)
+        if (npad > 64 * kSortT) npad = 0;  // > 32768 points: keep the original order (nothing is culled)
         a.n[w] = nn[w];
         a.npad[w] = npad;
         slots = std::max(slots, npad / kSortT);
@@ -392,7 +395,7 @@ int sort_cloud_cmajor(int b, int c, int n, const float *x, float4 *aos, float *b
     SortArgs a{};
     int npad = 4 * kSortT;
     while (npad < n) npad <<= 1;
-    if (npad > 64 * kSortT) npad = 0;  // > 16384 points: original order
+    if (npad > 64 * kSortT) npad = 0;  // > 32768 points: original order (the k-NN graph stops at kSortedMaxN = 16384 and never gets here)
     a.n[0] = n; a.npad[0] = npad; a.n4[0] = (n + 3) & ~3; a.nb[0] = pcc::ceil_div(n, kBox);
     a.xyz[0] = x; a.sstride[0] = (long long)c * n; a.pstride[0] = 1; a.cstride[0] = n; a.nch[0] = c;
     a.aos[0] = aos; a.box[0] = box16; a.perm[0] = perm;

@@ -20,22 +20,30 @@ struct SmallLayout {
     static constexpr int bytes = (cand_bytes + buf_bytes) > merge_bytes ? (cand_bytes + buf_bytes) : merge_bytes;
 };
 
-// Merge S sorted K-lists per lane (LDS layout [s][slot][lane]) and write the first k indices as int64.
+// Merge S sorted K-lists per lane (LDS layout [s][slot][lane]) and write the first k indices as int64.  Equal distances
+// go to the lower candidate index: a wave's list is in (distance, index) order, but the waves' candidate ranges
+// interleave (wave w takes the w-th quarter of EVERY 2048-candidate chunk), so from the second chunk on "the earlier
+// wave" is not "the lower index".
 template <int K, int S>
 __device__ __forceinline__ void merge_and_store(const float *md, const int *mi, int lane, int k, int64_t *dst, int n) {
+    // heads as 64-bit keys (distance bits : index): the distances are non-negative and never NaN, so they order like
+    // unsigned integers and one compare is "smaller distance, then lower index"; a list that has run out heads kKeyInf
+    const auto entry = [&](int s, int pos) -> unsigned long long {
+        return ((unsigned long long)__float_as_uint(md[(s * K + pos) * 64 + lane]) << 32) | (unsigned)mi[(s * K + pos) * 64 + lane];
+    };
     int p[S];
-    float h[S];
+    unsigned long long h[S];
 #pragma unroll
     for (int s = 0; s < S; s++) {
         p[s] = 0;
-        h[s] = md[(s * K) * 64 + lane];
+        h[s] = entry(s, 0);
     }
     for (int o = 0; o < k; o++) {
         int best = 0;
-        float bv = h[0];
+        unsigned long long bv = h[0];
 #pragma unroll
         for (int s = 1; s < S; s++) {
-            const bool lt = h[s] < bv;  // strict: the earlier candidate range wins ties
+            const bool lt = h[s] < bv;
             bv = lt ? h[s] : bv;
             best = lt ? s : best;
         }
@@ -43,9 +51,9 @@ __device__ __forceinline__ void merge_and_store(const float *md, const int *mi, 
 #pragma unroll
         for (int s = 0; s < S; s++) pos = (best == s) ? p[s] : pos;
         // (a list can run out only when distances are NaN: never emit an index outside the cloud)
-        dst[o] = (int64_t)min(mi[(best * K + pos) * 64 + lane], n - 1);
+        dst[o] = (int64_t)min((int)(bv & 0xffffffffull), n - 1);
         const int np = pos + 1;
-        const float nh = np < K ? md[(best * K + np) * 64 + lane] : __builtin_inff();
+        const unsigned long long nh = np < K ? entry(best, np) : pcc::kKeyInf;
 #pragma unroll
         for (int s = 0; s < S; s++) {
             const bool sel = best == s;

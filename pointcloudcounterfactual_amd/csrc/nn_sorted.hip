@@ -160,8 +160,12 @@ __global__ __launch_bounds__(64 * kNNWaves) void nn_sorted_kernel(NNSortedArgs a
             const int qs = grp * kBox + quad * kNNQ + j;
             if (qs < a.n_q) {
                 const int orig = a.q_perm[(size_t)smp * a.n_q + qs];
-                a.out_d[(size_t)smp * a.n_q + orig] = __uint_as_float((unsigned)(bk[j] >> 32));
-                a.out_i[(size_t)smp * a.n_q + orig] = (int)(bk[j] & 0xffffffffu);
+                // A key that still holds kKeyInf's index found no candidate: every distance of the query was NaN (its
+                // bits sort above +inf).  It gets what the reference and pcc_nndistance give a NaN query, NaN / index 0:
+                // no index outside the other cloud is ever written (the backward gathers through these indices).
+                const bool found = (unsigned)(bk[j] & 0xffffffffu) != 0x7fffffffu;
+                a.out_d[(size_t)smp * a.n_q + orig] = __uint_as_float(found ? (unsigned)(bk[j] >> 32) : 0x7fc00000u);
+                a.out_i[(size_t)smp * a.n_q + orig] = found ? (int)(bk[j] & 0xffffffffu) : 0;
             }
         }
     }

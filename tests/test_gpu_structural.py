@@ -96,7 +96,9 @@ def test_nn_distance_autograd_matches_torch(cuda):
 
 AM_SHAPES = [(1, 1, 1), (2, 3, 5), (2, 64, 64), (2, 257, 130), (2, 128, 256), (1, 513, 512), (2, 1024, 1024),
              (1, 2100, 2300), (1, 4099, 100), (2, 70, 2050),  # these three span several 2048-candidate chunks
-             (1, 60, 16500)]  # more than 512 words of live bits per sample (two per thread in the owner-compacted passes)
+             (1, 60, 16500),  # more than 512 words of live bits per sample (two per thread in the owner-compacted passes)
+             (1, 9000, 40),   # rank / soa of am_sort_kernel<32> (8193 .. 16384 points)
+             (1, 40, 33000)]  # more than 32768 points: the cloud keeps its order, nothing is culled
 
 
 @pytest.mark.parametrize('b,n,m', AM_SHAPES)
@@ -759,8 +761,8 @@ CE_SHAPES = NN_SHAPES + [(2, 40, 1200), (1, 5000, 3000), (1, 17000, 300), (33, 2
 def test_chamfer_emd_neighbours_are_the_exhaustive_ones(cuda, b, n, m, kind):
     """pcc_chamfer_emd finds the nearest neighbours on the clouds the EMD has sorted, visiting only the candidate blocks
     that can hold one (nn_sorted_kernel): indices and distances carry the bits of the exhaustive pcc_nndistance -- also
-    across candidate chunks (> 2048), for clouds too large for the sort (> 16384: original order, nothing culled) and for
-    batches that run as two lanes."""
+    across candidate chunks (> 2048), for clouds of more than 16384 points (17000: am_sort_kernel<64>; the clouds too large
+    for the sort, > 32768 points, are in tests/test_gpu_sorted_search.py) and for batches that run as two lanes."""
     from pointcloudcounterfactual_amd import backend
 
     a, c = pair(4000 + n + m, b, n, m, kind)
