@@ -4,7 +4,7 @@
 
 namespace {  // (per translation unit on purpose: LevelConsts is a parameter type of am_materialise_kernel, whose name stays)
 
-typedef float v4f __attribute__((ext_vector_type(4)));  // for __builtin_nontemporal_load/store
+using pcc::v4f;  // for __builtin_nontemporal_load/store
 
 constexpr int kLevels = 9;       // j = 7 .. -1, level = -4^j            (approxmatch.cu:24-25)
 constexpr float kLog2e = 1.44269504088896340736f;

@@ -1,6 +1,7 @@
-// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip): a workgroup owns CB channels of one
-// sample and keeps their rows of x, or their gradient bins, in LDS.  How the ids are dealt, how much LDS a workgroup may
-// take, how CB is chosen and how the kernel template is picked for it.
+// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip, interpolate.hip): a workgroup owns CB
+// channels of one sample and keeps their rows of x, or their gradient bins, in LDS.  How the ids are dealt, how much LDS a
+// workgroup may take, how CB is chosen, how the kernel template is picked for it, and how the list of a sample is split
+// over several such workgroups.
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -40,6 +41,74 @@ void dispatch_cb(int cb, F &&f) {
         if (cb < CB_MAX) return dispatch_cb<CB_MAX / 2>(cb, f);
     }
     f(std::integral_constant<int, CB_MAX>{});
+}
+
+// ---- CB channels of a sample x a split of a per-sample list (grouping.hip: the m * k slots; interpolate.hip: the m dense
+// points) ----
+constexpr int kWgThreads = 1024;         // threads of such a workgroup at the most
+constexpr int kCbDirect = 8;             // channels per workgroup of the direct path (nothing to fit)
+constexpr long long kMaxGrid = 1 << 20;  // workgroups per launch; the kernels stride over the units beyond
+inline unsigned grid_for(long long units) { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
+
+// What one pass of a workgroup covers: channels c0 .. c0 + cb - 1 of sample smp, entries lo .. hi - 1 of its list of `len`.
+// Unit u of b * nblk * nsplit, the splits of a channel block innermost; consecutive units share an XCD (xcd_contiguous).
+struct ListUnit {
+    int smp, c0, cb;
+    unsigned lo, hi;
+};
+template <int CB>
+__device__ __forceinline__ ListUnit list_unit(long long u, int c, unsigned len, int nsplit, unsigned chunk) {
+    const int nblk = (c + CB - 1) / CB;
+    const long long blk = u / nsplit;
+    const unsigned s = (unsigned)(u - blk * nsplit);
+    const int smp = (int)(blk / nblk), c0 = (int)(blk - (long long)smp * nblk) * CB;
+    const unsigned lo = s * chunk;  // (< len: no overflow, len < 2^31 and chunk <= len + 63)
+    return {smp, c0, min(CB, c - c0), lo, min(len, lo + chunk)};
+}
+
+// How a call is cut into such workgroups: the path, CB, and into how many pieces the list of a sample is split.
+struct ListPlan {
+    bool lds;
+    int cb, nsplit;
+    unsigned chunk;
+    size_t lds_bytes;
+    long long units;
+    unsigned grid() const { return grid_for(units); }
+    // Threads per workgroup where they are not simply kWgThreads: one per `per` entries of a unit, or one per 8 words of
+    // its LDS tile (staged, or zeroed and written out) if that is more; whole waves.  A unit shorter than a full
+    // workgroup's reach (len = 512: 128 lanes with four entries each) would otherwise hold a CU's wave slots with waves
+    // that have nothing to do.
+    unsigned threads(unsigned len, unsigned per) const {
+        const unsigned ents = chunk < len ? chunk : len, by_entries = (ents + per - 1) / per, by_tile = (unsigned)(lds_bytes / 32);
+        const unsigned t = ((by_entries > by_tile ? by_entries : by_tile) + 63) / 64 * 64;
+        return t < 64 ? 64 : t > (unsigned)kWgThreads ? (unsigned)kWgThreads : t;
+    }
+};
+
+// LDS wherever the rows (or bins) of at least one channel of n floats fit a workgroup, the direct path otherwise;
+// `forced_path` is the caller's tuning switch (PCC_TUNE_..._PATH): 2 forces the direct path, and a forced LDS path that
+// cannot hold n is ignored.  `split_lds`: the entries of a channel block may go to several workgroups (a
+// forward, and a backward's direct path: LDS bins cannot be shared) -- used while the call would leave compute units
+// idle, down to `min_chunk` entries per workgroup.
+inline ListPlan make_list_plan(int b, int c, int n, unsigned len, bool split_lds, unsigned min_chunk, int forced_path) {
+    ListPlan p;
+    const int cb_lds = fit_cb(8, (size_t)n * sizeof(float));
+    const bool fits = (size_t)cb_lds * n * sizeof(float) <= kLdsWg;
+    p.lds = fits && forced_path != 2;
+    p.cb = p.lds ? cb_lds : kCbDirect;
+    p.lds_bytes = p.lds ? (size_t)p.cb * n * sizeof(float) : 0;
+    const long long blocks = (long long)b * ceil_div(c, p.cb);
+    long long want = 1;
+    if (!p.lds || split_lds) {
+        want = (2LL * device_cus_or(256) + blocks - 1) / blocks;  // two workgroups per compute unit
+        const long long most = (len + min_chunk - 1) / min_chunk;
+        want = want < most ? want : most;
+        want = want < 1 ? 1 : want;
+    }
+    p.chunk = (unsigned)(((len + want - 1) / want + 63) / 64 * 64);  // (a multiple of 64: whole waves, whole float4 groups)
+    p.nsplit = p.chunk ? (int)((len + p.chunk - 1) / p.chunk) : 1;
+    p.units = blocks * p.nsplit;
+    return p;
 }
 
 }  // namespace pcc

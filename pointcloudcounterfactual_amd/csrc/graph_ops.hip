@@ -20,7 +20,7 @@ namespace {
 // A neighbour index outside [0, n) (an index array built for another cloud size, a padding slot) must never become an
 // LDS address: it is replaced by the point itself (torch.gather would raise; a kernel cannot).  Memory safety only --
 // the Python layer documents that indices must lie in [0, n).
-__device__ __forceinline__ int nbr(long long v, int n, int self) { return (unsigned long long)v < (unsigned long long)n ? (int)v : self; }
+__device__ __forceinline__ int nbr(long long v, int n, int self) { return pcc::in_range(v, n) ? (int)v : self; }
 
 // The k neighbours of the 64 points a wave works on, for the per-point modes (max / sum / min-max over k).  A lane that
 // walks its own row of the [n][k] int64 list reads 8 bytes every 8k bytes: 64 cache lines per wave-load, and every channel
@@ -66,6 +66,8 @@ using pcc::fit_cb;
 using pcc::kLdsHalfCu;
 using pcc::kLdsWg;
 using pcc::kLdsWgDyn;
+using pcc::v2l;
+using pcc::v4f;
 
 // The n counts in cur[] become their exclusive prefix sums (the write cursors of a counting sort), copied to start[] too
 // if START.  Every thread of a 1024-thread workgroup calls it, between two barriers of its own: after the counts are
@@ -202,8 +204,6 @@ __global__ __launch_bounds__(1024) void gather_lds_kernel(int c, int n, int k, c
         if ((nk & 3) == 0 && k >= 4 && ((reinterpret_cast<uintptr_t>(ib) | reinterpret_cast<uintptr_t>(ob)) & 15) == 0) {
             // four consecutive edges per thread: the output is a write-only stream many times the L2 (838 MB at C=64,
             // k=25, B=32), stored as 16 bytes per lane; the index list as two 16-byte loads
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            typedef long long v2l __attribute__((ext_vector_type(2)));
             for (size_t e4 = (size_t)tid * 4; e4 < nk; e4 += (size_t)T * 4) {
                 const v2l ia = *reinterpret_cast<const v2l *>(ib + e4), ic = *reinterpret_cast<const v2l *>(ib + e4 + 2);
                 const long long raw[4] = {ia.x, ia.y, ic.x, ic.y};
@@ -477,7 +477,6 @@ __global__ __launch_bounds__(1024) void edge_chunk_sort_kernel(int n, int k, int
 constexpr int kSelfPts = 256;
 __global__ __launch_bounds__(256) void edge_self_sum_kernel(int c, int n, int k, const float *__restrict__ g, float *__restrict__ grad_x) {
     extern __shared__ __attribute__((aligned(16))) float ss_buf[];  // [kSelfPts * k]
-    typedef float v4f __attribute__((ext_vector_type(4)));
     const int tiles = (n + kSelfPts - 1) / kSelfPts;
     const int row = (int)(blockIdx.x / (unsigned)tiles);  // b * c + channel
     const int smp = row / c, ch = row - smp * c;
@@ -510,7 +509,6 @@ __global__ __launch_bounds__(kEsT, 8) void edge_stream_bwd_kernel(int c, int n, 
                                                                 const float *__restrict__ g, float *__restrict__ grad_x) {
     extern __shared__ __attribute__((aligned(16))) float es_f[];  // buf[CB][kEsCE] | bins[CB][n]
     float *buf = es_f, *bins = es_f + (size_t)CB * kEsCE;
-    typedef float v4f __attribute__((ext_vector_type(4)));
     const auto [smp, c0] = chan_block<CB>(c);
     const int tid = threadIdx.x, T = kEsT, lane = tid & 63, w = tid >> 6;
     const size_t nk = (size_t)n * k;
@@ -629,8 +627,6 @@ __global__ __launch_bounds__(kEsT, 8) void edge_stream_bwd_kernel(int c, int n, 
 // 256 MiB at B=32, N=2048): rows are streamed with 16-byte non-temporal loads, eight in flight per lane before the first
 // use; a lane's indices only grow, so inside a lane the strict compare already keeps the first maximum and the index
 // tie-break is needed only when the lanes meet.
-typedef float gp_v4f __attribute__((ext_vector_type(4)));
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void global_pool_kernel(int rows, int n, const float *__restrict__ x,
                                                            float *__restrict__ out_max, int32_t *__restrict__ argmax,
@@ -644,15 +640,15 @@ __global__ __launch_bounds__(256) void global_pool_kernel(int rows, int n, const
     float sum = 0.f;
     if (VEC) {
         constexpr int U = 8;
-        const gp_v4f *r4 = reinterpret_cast<const gp_v4f *>(r);
+        const v4f *r4 = reinterpret_cast<const v4f *>(r);
         const int n4 = n >> 2;
         for (int i0 = lane; i0 < n4; i0 += 64 * U) {
-            gp_v4f v[U];
+            v4f v[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int i = i0 + 64 * u;
                 v[u] = i < n4 ? __builtin_nontemporal_load(r4 + i)
-                              : gp_v4f{-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+                              : v4f{-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {

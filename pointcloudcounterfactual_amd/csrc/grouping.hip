@@ -27,32 +27,15 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef long long v2l __attribute__((ext_vector_type(2)));
+// (a workgroup's unit -- its channels and its slots lo .. hi - 1 of the sample's m * k -- and the plan: chan_block.hpp.
+// A slot that is not pcc::in_range is +0 forward and carries no gradient.)
+using pcc::in_range;
+using pcc::kCbDirect;
+using pcc::v2l;
+using pcc::v4f;
 
-constexpr int kT = 1024;                  // threads per workgroup
-constexpr int kCbDirect = 8;              // channels per workgroup of the direct path (nothing to fit)
-constexpr unsigned kMinChunk = 8192;      // slots per workgroup below which the list of a sample is not split further
-constexpr long long kMaxGrid = 1 << 20;   // workgroups per launch; the kernels stride over the units beyond
-
-// What one pass of a workgroup covers: channels c0 .. c0 + cb - 1 of sample smp, slots e0 .. e1 - 1 of its list.  Unit u
-// of b * nblk * nsplit, the splits of a channel block innermost; consecutive units share an XCD (pcc::xcd_contiguous).
-struct Unit {
-    int smp, c0, cb;
-    unsigned e0, e1;
-};
-template <int CB>
-__device__ __forceinline__ Unit unit_of(long long u, int c, unsigned mk, int nsplit, unsigned chunk) {
-    const int nblk = (c + CB - 1) / CB;
-    const long long blk = u / nsplit;
-    const unsigned s = (unsigned)(u - blk * nsplit);
-    const int smp = (int)(blk / nblk), c0 = (int)(blk - (long long)smp * nblk) * CB;
-    const unsigned e0 = s * chunk;  // (< mk: no overflow, mk < 2^31 and chunk <= mk + 63)
-    return {smp, c0, min(CB, c - c0), e0, min(mk, e0 + chunk)};
-}
-
-// An index outside [0, n) is no point (the -1 of PCC_BALL_PAD_NONE): the slot is +0 forward and carries no gradient.
-__device__ __forceinline__ bool in_range(long long v, int n) { return (unsigned long long)v < (unsigned long long)n; }
+constexpr int kT = pcc::kWgThreads;   // threads per workgroup
+constexpr unsigned kMinChunk = 8192;  // slots per workgroup below which the list of a sample is not split further
 
 // Forward.  LDS path: rows[cc][p] = x[smp, c0 + cc, p], staged from either layout; direct path: x read in place.
 template <int CB, bool DIRECT>
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(kT) void group_fwd_kernel(int c, int n, int m, int 
     const int tid = threadIdx.x;
     const unsigned mk = (unsigned)m * (unsigned)k;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
-        const Unit w = unit_of<CB>(u, c, mk, nsplit, chunk);
+        const pcc::ListUnit w = pcc::list_unit<CB>(u, c, mk, nsplit, chunk);
         const float *xb = x + (size_t)w.smp * c * n;
         if (!DIRECT) {
             __syncthreads();  // (the previous unit's gathers are done)
@@ -96,9 +79,9 @@ __global__ __launch_bounds__(kT) void group_fwd_kernel(int c, int n, int m, int 
         const int64_t *ib = idx + (size_t)w.smp * mk;
         float *ob = out + ((size_t)w.smp * out_c + out_c0 + w.c0) * mk;  // channel c0 + cc of the slice: ob + cc * mk
         if ((mk & 3) == 0 && ((reinterpret_cast<uintptr_t>(ib) | reinterpret_cast<uintptr_t>(ob)) & 15) == 0) {
-            // four consecutive slots per thread (e0, e1 and mk are multiples of 4): the output is a write-only stream many
+            // four consecutive slots per thread (lo, hi and mk are multiples of 4): the output is a write-only stream many
             // times the L2, stored as 16 bytes per lane; the index list as two 16-byte loads
-            for (unsigned e4 = w.e0 + (unsigned)tid * 4; e4 < w.e1; e4 += kT * 4) {
+            for (unsigned e4 = w.lo + (unsigned)tid * 4; e4 < w.hi; e4 += kT * 4) {
                 const v2l ia = *reinterpret_cast<const v2l *>(ib + e4), ic = *reinterpret_cast<const v2l *>(ib + e4 + 2);
                 const long long raw[4] = {ia.x, ia.y, ic.x, ic.y};
                 int t[4];
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(kT) void group_fwd_kernel(int c, int n, int m, int 
                 }
             }
         } else {
-            for (unsigned e = w.e0 + (unsigned)tid; e < w.e1; e += kT) {
+            for (unsigned e = w.lo + (unsigned)tid; e < w.hi; e += kT) {
                 const long long raw = ib[e];
                 const bool ok = in_range(raw, n);
                 const int t = ok ? (int)raw : 0;
@@ -164,7 +147,7 @@ __global__ __launch_bounds__(kT) void group_bwd_kernel(int c, int n, int m, int 
     const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15;
     const unsigned mk = (unsigned)m * (unsigned)k;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
-        const Unit w = unit_of<CB>(u, c, mk, nsplit, chunk);
+        const pcc::ListUnit w = pcc::list_unit<CB>(u, c, mk, nsplit, chunk);
         if (!DIRECT) {
             __syncthreads();  // (the previous unit's bins are written out)
             for (int i = tid; i < w.cb * n; i += kT) bins[i] = 0.f;
@@ -173,10 +156,10 @@ __global__ __launch_bounds__(kT) void group_bwd_kernel(int c, int n, int m, int 
         const int64_t *ib = idx + (size_t)w.smp * mk;
         const float *gb = g + ((size_t)w.smp * out_c + out_c0 + w.c0) * mk;
         float *gx = grad_x + (size_t)w.smp * c * n;
-        // whole waves walk the list (e0 is a multiple of 64, the bound is wave-uniform): DPP and ballot need every lane
-        for (unsigned base = w.e0 + (unsigned)(tid & ~63); base < w.e1; base += kT) {
+        // whole waves walk the list (lo is a multiple of 64, the bound is wave-uniform): DPP and ballot need every lane
+        for (unsigned base = w.lo + (unsigned)(tid & ~63); base < w.hi; base += kT) {
             const unsigned e = base + (unsigned)lane;
-            const bool valid = e < w.e1;
+            const bool valid = e < w.hi;
             const long long raw = valid ? ib[e] : -1;
             const int t = in_range(raw, n) ? (int)raw : -1;  // (slots without a point form runs of -1: summed, never added)
             float v[CB];
@@ -242,49 +225,15 @@ __global__ __launch_bounds__(256) void group_centre_bwd_kernel(int c, int n, int
     }
 }
 
-// How a call is cut into workgroups: the path, CB, and into how many pieces the list of a sample is split.
-struct Plan {
-    bool lds;
-    int cb, nsplit;
-    unsigned chunk;
-    size_t lds_bytes;
-    long long units;
-    unsigned grid() const { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
-};
-
-// LDS wherever the rows (or bins) of at least one channel fit a workgroup; the group_path switch forces either path (a
-// forced LDS path that cannot hold n is ignored).  `split`: the slots of a channel block may go to several workgroups
-// (the forward, and the backward's direct path: LDS bins cannot be shared) -- used while the call would leave compute
-// units idle, down to kMinChunk slots per workgroup.
-Plan make_plan(int b, int c, int n, unsigned mk, bool split_lds) {
-    Plan p;
-    const int forced = pcc::tuning(PCC_TUNE_GROUP_PATH);
-    const int cb_lds = pcc::fit_cb(8, (size_t)n * sizeof(float));
-    const bool fits = (size_t)cb_lds * n * sizeof(float) <= pcc::kLdsWg;
-    p.lds = fits && forced != 2;
-    p.cb = p.lds ? cb_lds : kCbDirect;
-    p.lds_bytes = p.lds ? (size_t)p.cb * n * sizeof(float) : 0;
-    const long long blocks = (long long)b * pcc::ceil_div(c, p.cb);
-    long long want = 1;
-    if (!p.lds || split_lds) {
-        want = (2LL * pcc::device_cus_or(256) + blocks - 1) / blocks;  // two workgroups per compute unit
-        const long long most = (mk + kMinChunk - 1) / kMinChunk;
-        want = want < most ? want : most;
-        want = want < 1 ? 1 : want;
-    }
-    p.chunk = (unsigned)(((mk + want - 1) / want + 63) / 64 * 64);  // (a multiple of 64: whole waves, whole float4 groups)
-    p.nsplit = p.chunk ? (int)((mk + p.chunk - 1) / p.chunk) : 1;
-    p.units = blocks * p.nsplit;
-    return p;
+// The plan of a call over the m * k slots of a sample (the group_path switch forces either path)
+pcc::ListPlan make_plan(int b, int c, int n, int m, int k, bool split_lds) {
+    return pcc::make_list_plan(b, c, n, (unsigned)m * (unsigned)k, split_lds, kMinChunk, pcc::tuning(PCC_TUNE_GROUP_PATH));
 }
 
 int check_sizes(const char *name, int b, int c, int n, int m, int k, int point_major, int out_c, int out_c0) {
     pcc::clear_error();
-    if (b < 0 || c < 1 || n < 1 || m < 0 || k < 1) return pcc::invalidf("%s: bad size", name);
-    if (b > 65535) return pcc::invalidf("%s: batch too large", name);
-    if ((long long)m * k > 0x7fffffffLL) return pcc::invalidf("%s: list too long (m * k >= 2^31)", name);
-    if (out_c0 < 0 || (long long)out_c0 + c > out_c)
-        return pcc::invalidf("%s: channels out_c0 .. out_c0 + c - 1 are not inside out_c", name);
+    if (int rc = pcc::check_list_sizes(name, b, c, n, m, k)) return rc;
+    if (int rc = pcc::check_out_slice(name, c, out_c, out_c0)) return rc;
     if (point_major != 0 && point_major != 1) return pcc::invalidf("%s: point_major must be 0 or 1", name);
     return PCC_OK;
 }
@@ -299,7 +248,7 @@ int pcc_group_points(int b, int c, int n, int m, int k, int point_major, const f
     if (b == 0 || m == 0) return PCC_OK;
     if (!x || !idx || !out) return pcc::invalid("group_points: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Plan p = make_plan(b, c, n, (unsigned)m * (unsigned)k, true);
+    const pcc::ListPlan p = make_plan(b, c, n, m, k, true);
     if (p.lds) {
         pcc::ProfScope prof("group_fwd_kernel<lds>", st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
@@ -326,7 +275,7 @@ int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, con
         return grad_x ? pcc::zero_async(grad_x, gx_bytes, st, cannot_zero) : PCC_OK;
     if (!idx || !grad_out) return pcc::invalid("group_points_bwd: null pointer");
     if (grad_x) {
-        const Plan p = make_plan(b, c, n, (unsigned)m * (unsigned)k, false);
+        const pcc::ListPlan p = make_plan(b, c, n, m, k, false);
         if (p.lds) {
             pcc::ProfScope prof("group_bwd_kernel<lds>", st);
             pcc::dispatch_cb(p.cb, [&](auto CB) {
@@ -344,8 +293,7 @@ int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, con
     if (grad_centre) {
         const long long rows = (long long)b * m, wgs = (rows + 3) / 4;
         pcc::ProfScope prof("group_centre_bwd_kernel", st);
-        hipLaunchKernelGGL(group_centre_bwd_kernel, dim3((unsigned)(wgs < kMaxGrid ? wgs : kMaxGrid)), dim3(256), 0, st, c, n, m, k,
-                           point_major, rows, idx, grad_out, out_c, out_c0, grad_centre);
+        hipLaunchKernelGGL(group_centre_bwd_kernel, dim3(pcc::grid_for(wgs)), dim3(256), 0, st, c, n, m, k, point_major, rows, idx, grad_out, out_c, out_c0, grad_centre);
     }
     return pcc::check_launch("group_points_bwd");
 }

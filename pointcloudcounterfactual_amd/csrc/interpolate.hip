@@ -12,8 +12,6 @@
 // (four consecutive points, non-temporal) where m % 4 == 0 and the bases are 16-byte aligned, a scalar loop otherwise.
 // The rows of a k-NN list hold distinct indices, so the backward adds every slot on its own (no run merging as in
 // group_bwd_kernel).  grad_w is a thread per slot walking the channels in ascending order: a fixed order, no atomics.
-// Unit / Plan are copies of grouping.hip's, over the m dense points instead of the m * k slots; the kernels of
-// grouping.hip are untouched.
 #include "chan_block.hpp"
 #include "pcc_common.hpp"
 
@@ -24,38 +22,19 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
+// (a workgroup's unit -- its channels and its dense points lo .. hi - 1 of the sample's m -- and the plan: chan_block.hpp.
+// A slot that is not pcc::in_range adds nothing and carries no gradient.)
+using pcc::canonical_nan;
+using pcc::in_range;
+using pcc::kCbDirect;
+using pcc::v4f;
 
-constexpr int kT = 1024;                 // threads per workgroup at the most (Plan::threads)
-constexpr int kCbDirect = 8;             // channels per workgroup of the direct path (nothing to fit)
-constexpr unsigned kMinChunk = 1024;     // dense points per workgroup below which the points of a sample are not split further
-constexpr long long kMaxGrid = 1 << 20;  // workgroups per launch; the kernels stride over the units beyond
-
-// What one pass of a workgroup covers: channels c0 .. c0 + cb - 1 of sample smp, dense points i0 .. i1 - 1.  Unit u of
-// b * nblk * nsplit, the splits of a channel block innermost; consecutive units share an XCD (pcc::xcd_contiguous).
-struct Unit {
-    int smp, c0, cb;
-    unsigned i0, i1;
-};
-template <int CB>
-__device__ __forceinline__ Unit unit_of(long long u, int c, unsigned m, int nsplit, unsigned chunk) {
-    const int nblk = (c + CB - 1) / CB;
-    const long long blk = u / nsplit;
-    const unsigned s = (unsigned)(u - blk * nsplit);
-    const int smp = (int)(blk / nblk), c0 = (int)(blk - (long long)smp * nblk) * CB;
-    const unsigned i0 = s * chunk;  // (< m: no overflow, m < 2^31 and chunk <= m + 63)
-    return {smp, c0, min(CB, c - c0), i0, min(m, i0 + chunk)};
-}
-
-// An index outside [0, n) is no point (the pad of a short list): the slot adds nothing and carries no gradient.
-__device__ __forceinline__ bool in_range(long long v, int n) { return (unsigned long long)v < (unsigned long long)n; }
-
-// The sign and payload of a generated NaN are the implementation's; the contract fixes the word.
-__device__ __forceinline__ float canonical(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
+constexpr int kT = pcc::kWgThreads;   // threads per workgroup at the most (ListPlan::threads)
+constexpr unsigned kMinChunk = 1024;  // dense points per workgroup below which the points of a sample are not split further
 
 // Forward.  LDS path: rows[cc][p] = x[smp, c0 + cc, p]; direct path: x read in place.  P dense points per thread (4 with
 // the 16-byte stores, 1 otherwise); per slot j in order, acc = acc + (w * x): a rounded product, then a rounded sum.
-// FULL: the workgroup has kT threads (Plan::threads), a compile-time stride: measurably faster in the long loops.
+// FULL: the workgroup has kT threads (ListPlan::threads), a compile-time stride: measurably faster in the long loops.
 template <int CB, bool DIRECT, bool FULL>
 __global__ __launch_bounds__(kT) void interp_fwd_kernel(int c, int n, int m, int k, long long units, int nsplit, unsigned chunk,
                                                         const float *__restrict__ x, const int64_t *__restrict__ idx,
@@ -65,7 +44,7 @@ __global__ __launch_bounds__(kT) void interp_fwd_kernel(int c, int n, int m, int
     const int tid = threadIdx.x, nt = FULL ? kT : (int)blockDim.x;
     const unsigned um = (unsigned)m;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
-        const Unit w = unit_of<CB>(u, c, um, nsplit, chunk);
+        const pcc::ListUnit w = pcc::list_unit<CB>(u, c, um, nsplit, chunk);
         const float *xb = x + ((size_t)w.smp * c + w.c0) * n;  // channel c0 + cc: xb + cc * n
         if (!DIRECT) {
             __syncthreads();  // (the previous unit's gathers are done)
@@ -83,8 +62,8 @@ __global__ __launch_bounds__(kT) void interp_fwd_kernel(int c, int n, int m, int
         const float *wb = wgt + (size_t)w.smp * um * k;
         float *ob = out + ((size_t)w.smp * out_c + out_c0 + w.c0) * um;  // channel c0 + cc of the slice: ob + cc * m
         if ((um & 3) == 0 && (reinterpret_cast<uintptr_t>(ob) & 15) == 0) {
-            // four consecutive dense points per thread (i0, i1 and m are multiples of 4)
-            for (unsigned i4 = w.i0 + (unsigned)tid * 4; i4 < w.i1; i4 += (unsigned)nt * 4) {
+            // four consecutive dense points per thread (lo, hi and m are multiples of 4)
+            for (unsigned i4 = w.lo + (unsigned)tid * 4; i4 < w.hi; i4 += (unsigned)nt * 4) {
                 float acc[CB][4];
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++)
@@ -117,13 +96,14 @@ __global__ __launch_bounds__(kT) void interp_fwd_kernel(int c, int n, int m, int
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++) {
                     if (cc < w.cb) {
-                        const v4f o = {canonical(acc[cc][0]), canonical(acc[cc][1]), canonical(acc[cc][2]), canonical(acc[cc][3])};
+                        const v4f o = {canonical_nan(acc[cc][0]), canonical_nan(acc[cc][1]), canonical_nan(acc[cc][2]),
+                                       canonical_nan(acc[cc][3])};
                         __builtin_nontemporal_store(o, reinterpret_cast<v4f *>(ob + (size_t)cc * um + i4));
                     }
                 }
             }
         } else {
-            for (unsigned i = w.i0 + (unsigned)tid; i < w.i1; i += (unsigned)nt) {
+            for (unsigned i = w.lo + (unsigned)tid; i < w.hi; i += (unsigned)nt) {
                 float acc[CB];
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++) acc[cc] = 0.f;
@@ -143,7 +123,7 @@ __global__ __launch_bounds__(kT) void interp_fwd_kernel(int c, int n, int m, int
                 }
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++)
-                    if (cc < w.cb) ob[(size_t)cc * um + i] = canonical(acc[cc]);
+                    if (cc < w.cb) ob[(size_t)cc * um + i] = canonical_nan(acc[cc]);
             }
         }
     }
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(kT) void interp_bwd_x_kernel(int c, int n, int m, i
     const int tid = threadIdx.x, nt = FULL ? kT : (int)blockDim.x;
     const unsigned um = (unsigned)m;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
-        const Unit w = unit_of<CB>(u, c, um, nsplit, chunk);
+        const pcc::ListUnit w = pcc::list_unit<CB>(u, c, um, nsplit, chunk);
         if (!DIRECT) {
             __syncthreads();  // (the previous unit's bins are written out)
             for (int i = tid; i < w.cb * n; i += nt) bins[i] = 0.f;
@@ -172,7 +152,7 @@ __global__ __launch_bounds__(kT) void interp_bwd_x_kernel(int c, int n, int m, i
         const float *wb = wgt + (size_t)w.smp * um * k;
         const float *gb = g + ((size_t)w.smp * out_c + out_c0 + w.c0) * um;
         float *gx = grad_x + ((size_t)w.smp * c + w.c0) * n;
-        for (unsigned i = w.i0 + (unsigned)tid; i < w.i1; i += (unsigned)nt) {
+        for (unsigned i = w.lo + (unsigned)tid; i < w.hi; i += (unsigned)nt) {
             float gv[CB];
 #pragma unroll
             for (int cc = 0; cc < CB; cc++) gv[cc] = cc < w.cb ? gb[(size_t)cc * um + i] : 0.f;
@@ -225,48 +205,9 @@ __global__ __launch_bounds__(256) void interp_bwd_w_kernel(int c, int n, int m, 
     }
 }
 
-// How a call is cut into workgroups: the path, CB, and into how many pieces the dense points of a sample are split.
-struct Plan {
-    bool lds;
-    int cb, nsplit;
-    unsigned chunk;
-    size_t lds_bytes;
-    long long units;
-    unsigned grid() const { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
-    // Threads per workgroup: one per `per` dense points of a unit, or one per 8 words of its LDS tile (staged, or zeroed
-    // and written out) if that is more; whole waves, kT at the most.  A unit shorter than a full workgroup's reach (m = 512:
-    // 128 lanes with four points each) would otherwise hold a CU's wave slots with waves that have nothing to do.
-    unsigned threads(unsigned m, unsigned per) const {
-        const unsigned pts = chunk < m ? chunk : m, by_points = (pts + per - 1) / per, by_tile = (unsigned)(lds_bytes / 32);
-        const unsigned t = ((by_points > by_tile ? by_points : by_tile) + 63) / 64 * 64;
-        return t < 64 ? 64 : t > (unsigned)kT ? (unsigned)kT : t;
-    }
-};
-
-// LDS wherever the rows (or bins) of at least one channel fit a workgroup; the interp_path switch forces either path (a
-// forced LDS path that cannot hold n is ignored).  `split_lds`: the dense points of a channel block may go to several
-// workgroups (the forward, and the backward's direct path: LDS bins cannot be shared) -- used while the call would leave
-// compute units idle, down to kMinChunk points per workgroup.
-Plan make_plan(int b, int c, int n, unsigned m, bool split_lds) {
-    Plan p;
-    const int forced = pcc::tuning(PCC_TUNE_INTERP_PATH);
-    const int cb_lds = pcc::fit_cb(8, (size_t)n * sizeof(float));
-    const bool fits = (size_t)cb_lds * n * sizeof(float) <= pcc::kLdsWg;
-    p.lds = fits && forced != 2;
-    p.cb = p.lds ? cb_lds : kCbDirect;
-    p.lds_bytes = p.lds ? (size_t)p.cb * n * sizeof(float) : 0;
-    const long long blocks = (long long)b * pcc::ceil_div(c, p.cb);
-    long long want = 1;
-    if (!p.lds || split_lds) {
-        want = (2LL * pcc::device_cus_or(256) + blocks - 1) / blocks;  // two workgroups per compute unit
-        const long long most = (m + kMinChunk - 1) / kMinChunk;
-        want = want < most ? want : most;
-        want = want < 1 ? 1 : want;
-    }
-    p.chunk = (unsigned)(((m + want - 1) / want + 63) / 64 * 64);  // (a multiple of 64: whole waves, whole float4 groups)
-    p.nsplit = p.chunk ? (int)((m + p.chunk - 1) / p.chunk) : 1;
-    p.units = blocks * p.nsplit;
-    return p;
+// The plan of a call over the m dense points of a sample (the interp_path switch forces either path)
+pcc::ListPlan make_plan(int b, int c, int n, int m, bool split_lds) {
+    return pcc::make_list_plan(b, c, n, (unsigned)m, split_lds, kMinChunk, pcc::tuning(PCC_TUNE_INTERP_PATH));
 }
 
 // f(std::bool_constant<the workgroup has kT threads>)
@@ -278,12 +219,8 @@ void full_or_not(const dim3 &block, F &&f) {
 
 int check_sizes(const char *name, int b, int c, int n, int m, int k, int out_c, int out_c0) {
     pcc::clear_error();
-    if (b < 0 || c < 1 || n < 1 || m < 0 || k < 1) return pcc::invalidf("%s: bad size", name);
-    if (b > 65535) return pcc::invalidf("%s: batch too large", name);
-    if ((long long)m * k > 0x7fffffffLL) return pcc::invalidf("%s: list too long (m * k >= 2^31)", name);
-    if (out_c0 < 0 || (long long)out_c0 + c > out_c)
-        return pcc::invalidf("%s: channels out_c0 .. out_c0 + c - 1 are not inside out_c", name);
-    return PCC_OK;
+    if (int rc = pcc::check_list_sizes(name, b, c, n, m, k)) return rc;
+    return pcc::check_out_slice(name, c, out_c, out_c0);
 }
 
 }  // namespace
@@ -296,7 +233,7 @@ int pcc_interpolate(int b, int c, int n, int m, int k, const float *x, const int
     if (b == 0 || m == 0) return PCC_OK;
     if (!x || !idx || !w || !out) return pcc::invalid("interpolate: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Plan p = make_plan(b, c, n, (unsigned)m, true);
+    const pcc::ListPlan p = make_plan(b, c, n, m, true);
     // (four points per thread where the kernel takes its 16-byte stores: the same test as there, every channel row of the
     // slice is aligned when the base is and m % 4 == 0)
     const dim3 block(p.threads((unsigned)m, (m & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 4 : 1));
@@ -330,7 +267,7 @@ int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const
         return grad_x ? pcc::zero_async(grad_x, gx_bytes, st, cannot_zero) : PCC_OK;
     if (!idx || !w || !grad_out || (grad_w && !x)) return pcc::invalid("interpolate_bwd: null pointer");
     if (grad_x) {
-        const Plan p = make_plan(b, c, n, (unsigned)m, false);
+        const pcc::ListPlan p = make_plan(b, c, n, m, false);
         const dim3 block(p.threads((unsigned)m, 1));
         if (p.lds) {
             pcc::ProfScope prof("interp_bwd_x_kernel<lds>", st);
@@ -353,8 +290,8 @@ int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const
     if (grad_w) {
         const long long slots = (long long)b * m * k, wgs = (slots + 255) / 256;
         pcc::ProfScope prof("interp_bwd_w_kernel", st);
-        hipLaunchKernelGGL(interp_bwd_w_kernel, dim3((unsigned)(wgs < kMaxGrid ? wgs : kMaxGrid)), dim3(256), 0, st, c, n, m, k, slots, x,
-                           idx, grad_out, out_c, out_c0, grad_w);
+        hipLaunchKernelGGL(interp_bwd_w_kernel, dim3(pcc::grid_for(wgs)), dim3(256), 0, st, c, n, m, k, slots, x, idx, grad_out, out_c,
+                           out_c0, grad_w);
     }
     return pcc::check_launch("interpolate_bwd");
 }

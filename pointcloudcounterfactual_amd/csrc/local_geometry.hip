@@ -14,6 +14,7 @@
 // beside the tile (flushed to the zero-filled grad_xyz with global atomics, so that several workgroups can share a sample),
 // straight into global memory otherwise; a lane first sums the run of equal consecutive indices of its row (the padding of
 // a PCC_BALL_PAD_FIRST list) in registers.  DESIGN.md section 4i.
+#include "chan_block.hpp"
 #include "pcc_common.hpp"
 #include "sym3_eigen.hpp"
 
@@ -23,19 +24,16 @@
 
 namespace {
 
-typedef long long v2l __attribute__((ext_vector_type(2)));
+using pcc::canonical_nan;
+using pcc::v2l;
 
 constexpr int kRows = 256;               // rows of the list per tile = threads per workgroup
 constexpr int kChunk = 32;               // slots of a row held in LDS at a time
 constexpr int kStride = kChunk + 1;      // words between the rows of a tile: odd
-constexpr long long kMaxGrid = 1 << 20;  // workgroups per launch; the kernels stride over the units beyond
 constexpr size_t kBinBytes = 96 * 1024;  // the backward's LDS bins of one sample at the most (12 n bytes: n <= 8192)
 
-// The sign and payload of a generated NaN are the implementation's; the contract fixes the word.
-__device__ __forceinline__ float canonical(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
-
 // An index outside [0, n) is no point (the -1 of PCC_BALL_PAD_NONE): -1 in the tile.
-__device__ __forceinline__ int slot_of(long long raw, int n) { return (unsigned long long)raw < (unsigned long long)n ? (int)raw : -1; }
+__device__ __forceinline__ int slot_of(long long raw, int n) { return pcc::in_range(raw, n) ? (int)raw : -1; }
 
 // tile[row][j] = slot c0 + j of row `row`, for the kc slots from c0 of the `nrows` rows at ib (k slots each).  Whole rows
 // (kc == k) are one contiguous piece of the list: 16 bytes per lane where the piece is aligned.
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(kRows) void local_geometry_kernel(int n, int m, int
         }
         if (live && mean) {
             float *o = mean + (size_t)r * 3;
-            o[0] = canonical(mx), o[1] = canonical(my), o[2] = canonical(mz);
+            o[0] = canonical_nan(mx), o[1] = canonical_nan(my), o[2] = canonical_nan(mz);
         }
         if (!want_cov) continue;  // (uniform)
         float c00 = 0.f, c01 = 0.f, c02 = 0.f, c11 = 0.f, c12 = 0.f, c22 = 0.f;
@@ -128,8 +126,8 @@ __global__ __launch_bounds__(kRows) void local_geometry_kernel(int n, int m, int
         if (!live) continue;  // (no barrier is left in this pass)
         if (cov) {
             float *o = cov + (size_t)r * 9;
-            const float s00 = canonical(c00), s01 = canonical(c01), s02 = canonical(c02), s11 = canonical(c11),
-                        s12 = canonical(c12), s22 = canonical(c22);
+            const float s00 = canonical_nan(c00), s01 = canonical_nan(c01), s02 = canonical_nan(c02), s11 = canonical_nan(c11),
+                        s12 = canonical_nan(c12), s22 = canonical_nan(c22);
             o[0] = s00, o[1] = s01, o[2] = s02;
             o[3] = s01, o[4] = s11, o[5] = s12;
             o[6] = s02, o[7] = s12, o[8] = s22;
@@ -232,10 +230,7 @@ __global__ __launch_bounds__(kRows) void local_covariance_bwd_kernel(int n, int 
 
 int check_sizes(const char *name, int b, int n, int m, int k) {
     pcc::clear_error();
-    if (b < 0 || n < 1 || m < 0 || k < 1) return pcc::invalidf("%s: bad size", name);
-    if (b > 65535) return pcc::invalidf("%s: batch too large", name);
-    if ((long long)m * k > 0x7fffffffLL) return pcc::invalidf("%s: list too long (m * k >= 2^31)", name);
-    return PCC_OK;
+    return pcc::check_list_sizes(name, b, 1, n, m, k);  // (no channels)
 }
 
 }  // namespace
@@ -250,8 +245,8 @@ int pcc_local_geometry(int b, int n, int m, int k, const float *xyz, const int64
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long rows = (long long)b * m, tiles = (rows + kRows - 1) / kRows;
     pcc::ProfScope prof("local_geometry_kernel", st);
-    hipLaunchKernelGGL(local_geometry_kernel, dim3((unsigned)(tiles < kMaxGrid ? tiles : kMaxGrid)), dim3(kRows), 0, st, n, m, k, rows,
-                       tiles, xyz, idx, mean, cov, eval, evec, curv);
+    hipLaunchKernelGGL(local_geometry_kernel, dim3(pcc::grid_for(tiles)), dim3(kRows), 0, st, n, m, k, rows, tiles, xyz, idx, mean, cov,
+                       eval, evec, curv);
     return pcc::check_launch("local_geometry");
 }
 
@@ -271,7 +266,7 @@ int pcc_local_covariance_bwd(int b, int n, int m, int k, const float *xyz, const
     const unsigned chunk = (unsigned)(((m + want - 1) / want + kRows - 1) / kRows * kRows);  // (whole tiles)
     const int nsplit = (int)(((unsigned)m + chunk - 1) / chunk);
     const long long units = (long long)b * nsplit;
-    const dim3 grid((unsigned)(units < kMaxGrid ? units : kMaxGrid));
+    const dim3 grid(pcc::grid_for(units));
     if (bin_bytes <= kBinBytes) {
         pcc::ProfScope prof("local_covariance_bwd_kernel<lds>", st);
         (void)pcc::allow_lds<local_covariance_bwd_kernel<true>>(kBinBytes);

@@ -37,11 +37,8 @@ struct Grid {
     float lo, inv, step, top;  // inv = (res - 1) / extent, step = extent / (res - 1), top = res - 1
 };
 
-// nearest grid index on one axis: two roundings (the file is built with -ffp-contract=off), clamped as a float
-__device__ __forceinline__ int axis_cell(float x, const Grid &g) {
-    const float t = (x - g.lo) * g.inv;
-    return (int)fminf(fmaxf(floorf(t + 0.5f), 0.f), g.top);
-}
+// nearest grid index on one axis: the rule pcc_voxel_index shares
+__device__ __forceinline__ int axis_cell(float x, const Grid &g) { return pcc::axis_cell(x, g.lo, g.inv, g.top); }
 
 __device__ __forceinline__ bool in_sphere(int i, int j, int k, int r1) {
     const int a = 2 * i - r1, b = 2 * j - r1, c = 2 * k - r1;

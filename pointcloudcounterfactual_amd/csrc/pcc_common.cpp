@@ -59,6 +59,17 @@ int invalidf(const char *fmt, ...) {
     va_end(args);
     return invalid(buf);
 }
+int check_list_sizes(const char *name, int b, int c, int n, int m, int k) {
+    if (b < 0 || c < 1 || n < 1 || m < 0 || k < 1) return invalidf("%s: bad size", name);
+    if (b > 65535) return invalidf("%s: batch too large", name);
+    if ((long long)m * k > 0x7fffffffLL) return invalidf("%s: list too long (m * k >= 2^31)", name);
+    return PCC_OK;
+}
+int check_out_slice(const char *name, int c, int out_c, int out_c0) {
+    if (out_c0 < 0 || (long long)out_c0 + c > out_c)
+        return invalidf("%s: channels out_c0 .. out_c0 + c - 1 are not inside out_c", name);
+    return PCC_OK;
+}
 int zero_async(void *p, size_t bytes, hipStream_t st, const char *what) {
     const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
     if (e == hipSuccess) return PCC_OK;

@@ -38,8 +38,18 @@ inline int invalid(const char *what) {
 // ... with a printf-style message (256 bytes at the most), for checks shared under several entry points' names
 __attribute__((format(printf, 1, 2))) int invalidf(const char *fmt, ...);
 
+// The size checks of the ops along an index list idx[b,m,k] into n points with c channels (c = 1 where there are none),
+// under the entry point's name: "bad size", "batch too large", "list too long (m * k >= 2^31)", in that order ...
+int check_list_sizes(const char *name, int b, int c, int n, int m, int k);
+// ... and of the channel slice out_c0 .. out_c0 + c - 1 of an output with out_c channels
+int check_out_slice(const char *name, int c, int out_c, int out_c0);
+
 // Stream-ordered zero fill.  PCC_OK, or the HIP error with `what` as the error message (the sticky error is cleared).
 int zero_async(void *p, size_t bytes, hipStream_t st, const char *what);
+
+// 16 bytes per lane: four floats for __builtin_nontemporal_load / store, two indices of an int64 list
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef long long v2l __attribute__((ext_vector_type(2)));
 
 // No coordinate is an infinity or a NaN.
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
@@ -52,6 +62,20 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
 // -ffp-contract=off, so `y * y` stays a rounded multiply and nothing else is fused.
 __device__ __forceinline__ float sq3(float x, float y, float z) {
     return __builtin_fmaf(z, z, __builtin_fmaf(x, x, y * y));
+}
+
+// An index outside [0, n) is no point (the -1 of PCC_BALL_PAD_NONE, the pad of a short list): what the slot becomes is
+// the caller's.
+__device__ __forceinline__ bool in_range(long long v, int n) { return (unsigned long long)v < (unsigned long long)n; }
+
+// The sign and payload of a generated NaN are the implementation's; the contracts fix the word.
+__device__ __forceinline__ float canonical_nan(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
+
+// Nearest grid index on one axis of the grid of pcc_occupancy_grid and pcc_voxel_index (inv = (res - 1) / extent,
+// top = res - 1): two roundings (the files are built with -ffp-contract=off), the clamp taken on the float.
+__device__ __forceinline__ int axis_cell(float x, float lo, float inv, float top) {
+    const float t = (x - lo) * inv;
+    return (int)fminf(fmaxf(floorf(t + 0.5f), 0.f), top);
 }
 
 // pcc_knn's c <= 3 distance of the point (x, y, z) to (sx, sy, sz): df = x - s per coordinate, acc = df0 * df0, then

@@ -1,6 +1,6 @@
 // The point-voxel branch (pcc_voxel_index, pcc_voxelize / _bwd, pcc_devoxelize / _bwd, include/pcc_neighbour.h), gfx950,
 // wave64: point features averaged into a dense res^3 grid and read back at the points by trilinear interpolation.  The
-// grid is pcc_occupancy_grid's (occupancy.hip: axis_cell there and here are the same three lines).
+// grid is pcc_occupancy_grid's (occupancy.hip: both take their cells from pcc::axis_cell).
 //   * vox_index_wave_kernel / vox_index_lds_kernel: one workgroup per cloud sorts the 64-bit keys (cell << 32 | point) --
 //     distinct, so every sorting network gives one answer -- in registers (n <= kWaveSort, one wave, wave_sort.hpp) or in
 //     LDS (the next power of two of keys, up to kMaxPoints: every wave sorts 64 E keys in registers and only the merge
@@ -31,7 +31,8 @@
 namespace {
 
 typedef unsigned long long u64;
-typedef float v4f __attribute__((ext_vector_type(4)));
+using pcc::canonical_nan;
+using pcc::v4f;
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));  // two k-adjacent corners: any 4-byte alignment
 
@@ -55,14 +56,8 @@ struct Grid {
     float lo, inv, top;  // inv = (res - 1) / extent, top = res - 1
 };
 
-// nearest grid index on one axis: pcc_occupancy_grid's rule (two roundings, the clamp taken on the float)
-__device__ __forceinline__ int axis_cell(float x, const Grid &g) {
-    const float t = (x - g.lo) * g.inv;
-    return (int)fminf(fmaxf(floorf(t + 0.5f), 0.f), g.top);
-}
-
-// The sign and payload of a generated NaN are the implementation's; the contract fixes the word.
-__device__ __forceinline__ float canonical(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
+// nearest grid index on one axis: pcc_occupancy_grid's rule
+__device__ __forceinline__ int axis_cell(float x, const Grid &g) { return pcc::axis_cell(x, g.lo, g.inv, g.top); }
 
 // The sort key of point p of the cloud at `xyz`; writes cell[p] and, if COUNT, adds the point to its cell's count.
 template <bool COUNT>
@@ -238,7 +233,7 @@ __global__ __launch_bounds__(kT) void vox_fwd_kernel(int c, int n, int bins, con
             }
             const float d = (float)cnt[q];
 #pragma unroll
-            for (int cc = 0; cc < kCb; cc++) acc[cc][q] = canonical(acc[cc][q] / d);
+            for (int cc = 0; cc < kCb; cc++) acc[cc][q] = canonical_nan(acc[cc][q] / d);
         }
         float *gb = grid + (smp * c + c0) * bins + v0;
         if (P == 4 && !any_long) {
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(64) void vox_long_kernel(int c, int n, int bins, co
             for (int u = 0; u < 2 * kAhead; u++)
                 if (p[u] < (unsigned)n) acc = acc + xv[u];
         }
-        grid[(smp * c + ch) * bins + v] = canonical(acc / (float)cnt);
+        grid[(smp * c + ch) * bins + v] = canonical_nan(acc / (float)cnt);
     }
 }
 
@@ -364,7 +359,7 @@ __global__ __launch_bounds__(kT) void devox_fwd_kernel(int c, int n, Grid g, con
                     acc = acc + t1;
                 }
             }
-            ob[(size_t)cc * n] = canonical(acc);
+            ob[(size_t)cc * n] = canonical_nan(acc);
         }
     }
 }

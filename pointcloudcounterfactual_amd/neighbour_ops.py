@@ -21,6 +21,7 @@ from torch.autograd import Function
 from pointcloudcounterfactual_amd import _lib
 from pointcloudcounterfactual_amd._float32 import fma32
 from pointcloudcounterfactual_amd._lib import call, ptr
+from pointcloudcounterfactual_amd.set_metrics import _grid_args
 
 _L = _lib.lib
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
@@ -38,6 +39,52 @@ def _float32(name: str, t: torch.Tensor) -> None:
     """``t`` is float32, or the ``RuntimeError`` of ``_lib.ptr``."""
     if t.dtype != F32:
         raise RuntimeError(f'{name} must be {F32}, found {t.dtype}')
+
+
+def _cloud_arg(what: str, name: str, xyz: torch.Tensor, b: int | None = None, min_n: int = 1, axis: str = 'N') -> tuple[int, int]:
+    """``xyz[B,N,3]`` with ``N >= min_n`` (and the given ``B``), or the ``ValueError`` of ``what``: ``(b, n)``.  ``name`` and
+    ``axis`` are what the message calls the tensor and its point axis."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < min_n or (b is not None and xyz.shape[0] != b):
+        lay = f'{name}[B,{axis},3]' if b is None else f'{name}[B = {b},{axis},3]'
+        raise ValueError(f'{what}: expected {lay}{f" with {axis} >= {min_n}" if min_n else ""}, got {tuple(xyz.shape)}')
+    return xyz.shape[0], xyz.shape[1]
+
+
+def _features_arg(what: str, features: torch.Tensor, name: str = 'features') -> tuple[int, int, int]:
+    """``features[B,C,N]`` with ``C >= 1`` and ``N >= 1``, or the ``ValueError`` of ``what``: ``(b, c, n)``."""
+    if features.dim() != 3 or features.shape[1] < 1 or features.shape[2] < 1:
+        raise ValueError(f'{what}: expected {name}[B,C,N] with C >= 1 and N >= 1, got {tuple(features.shape)}')
+    b, c, n = features.shape
+    return b, c, n
+
+
+def _list_arg(what: str, idx: torch.Tensor, b: int) -> tuple[int, int]:
+    """The shape of an index list ``idx[B,M,k]`` with ``k >= 1`` and ``M * k < 2^31``, or the ``ValueError`` of ``what``:
+    ``(m, k)``.  Its dtype and device are ``_list_on``'s: every caller checks other shapes in between."""
+    if idx.dim() != 3 or idx.shape[0] != b or idx.shape[2] < 1:
+        raise ValueError(f'{what}: expected idx[B = {b},M,k] with k >= 1, got {tuple(idx.shape)}')
+    m, k = idx.shape[1], idx.shape[2]
+    if m * k >= 1 << 31:
+        raise ValueError(f'{what}: idx[B,M,k] with M * k >= 2^31, got {tuple(idx.shape)}')
+    return m, k
+
+
+def _list_on(idx: torch.Tensor, dev: torch.device) -> None:
+    """``idx`` is int64 and on ``dev``, or the ``RuntimeError`` of ``_lib.ptr``."""
+    if idx.dtype != I64:
+        raise RuntimeError(f'idx must be {I64}, found {idx.dtype}')
+    _same_device('idx', idx, dev)
+
+
+def _k_arg(what: str, k: Any) -> None:
+    """``k`` is an integer in ``[1, 128]`` (what ``knn`` and ``knn_cross`` search), or the ``ValueError`` of ``what``."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 128:
+        raise ValueError(f'{what}: k must be an integer in [1, 128], got {k!r}')
+
+
+def _canonical_nan(t: torch.Tensor) -> torch.Tensor:
+    """A NaN becomes the word 0x7fc00000."""
+    return torch.where(torch.isnan(t), torch.full((), float('nan'), dtype=t.dtype, device=t.device), t)
 
 
 # ---- squared distances (reference neighbour_ops.py:16-50) -----------------------------------------------------------------
@@ -173,10 +220,8 @@ def knn_cross(q: torch.Tensor, x: torch.Tensor, k: int, return_distance: bool = 
 
 def _fps_args(xyz: torch.Tensor, m: int, start: Any) -> tuple[torch.Tensor, int, torch.Tensor | None]:
     """The checks ``farthest_point_sample`` makes before anything runs: ``(xyz detached, m, start as a tensor or None)``."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3:
-        raise ValueError(f'farthest_point_sample: expected xyz[B,N,3], got {tuple(xyz.shape)}')
+    b, n = _cloud_arg('farthest_point_sample', 'xyz', xyz, min_n=0)
     _float32('xyz', xyz)
-    b, n = xyz.shape[:2]
     if isinstance(m, bool) or not isinstance(m, int) or m < 1 or m > n:
         raise ValueError(f'farthest_point_sample: m must be an int in [1, N = {n}], got {m!r}')
     if start is None or isinstance(start, torch.Tensor):
@@ -251,10 +296,8 @@ BALL_PAD = {'first': 0, 'none': 1}  # PCC_BALL_PAD_FIRST / PCC_BALL_PAD_NONE (in
 def _ball_args(xyz: torch.Tensor, centres: torch.Tensor, radius: Any, nsample: int, pad: str) -> tuple[torch.Tensor, torch.Tensor, float, int]:
     """The checks ``ball_query`` makes before anything runs: ``(xyz detached, centres detached, radius as the float32 the
     library receives, pad as the C constant)``."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < 1:
-        raise ValueError(f'ball_query: expected xyz[B,N,3] with N >= 1, got {tuple(xyz.shape)}')
-    if centres.dim() != 3 or centres.shape[2] != 3 or centres.shape[0] != xyz.shape[0]:
-        raise ValueError(f'ball_query: expected centres[B = {xyz.shape[0]},M,3], got {tuple(centres.shape)}')
+    b, _ = _cloud_arg('ball_query', 'xyz', xyz)
+    _cloud_arg('ball_query', 'centres', centres, b, min_n=0, axis='M')
     _float32('xyz', xyz)
     _float32('centres', centres)
     _same_device('centres', centres, xyz.device)
@@ -340,17 +383,11 @@ def _group_args(x: torch.Tensor, idx: torch.Tensor, centres: torch.Tensor | None
         raise ValueError(f'{what}: expected {lay} with C >= 1 and N >= 1, got {tuple(x.shape)}')
     b = x.shape[0]
     n, c = (x.shape[1], x.shape[2]) if point_major else (x.shape[2], x.shape[1])
-    if idx.dim() != 3 or idx.shape[0] != b or idx.shape[2] < 1:
-        raise ValueError(f'{what}: expected idx[B = {b},M,k] with k >= 1, got {tuple(idx.shape)}')
-    m, k = idx.shape[1], idx.shape[2]
-    if m * k >= 1 << 31:
-        raise ValueError(f'{what}: idx[B,M,k] with M * k >= 2^31, got {tuple(idx.shape)}')
+    m, k = _list_arg(what, idx, b)
     if centres is not None and tuple(centres.shape) != ((b, m, c) if point_major else (b, c, m)):
         raise ValueError(f'{what}: expected {clay} = {(b, m, c) if point_major else (b, c, m)}, got {tuple(centres.shape)}')
     _float32('x', x)
-    if idx.dtype != I64:
-        raise RuntimeError(f'idx must be {I64}, found {idx.dtype}')
-    _same_device('idx', idx, x.device)
+    _list_on(idx, x.device)
     if centres is not None:
         _float32('centres', centres)
         _same_device('centres', centres, x.device)
@@ -499,20 +536,12 @@ def interpolation_weights(dist: torch.Tensor, eps: float = 1e-8) -> torch.Tensor
 
 def _interp_args(x: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor, what: str = 'interpolate_points') -> tuple[int, int, int, int, int]:
     """The checks ``interpolate_points`` makes before anything runs: ``(b, c, n, m, k)``."""
-    if x.dim() != 3 or x.shape[1] < 1 or x.shape[2] < 1:
-        raise ValueError(f'{what}: expected x[B,C,N] with C >= 1 and N >= 1, got {tuple(x.shape)}')
-    b, c, n = x.shape
-    if idx.dim() != 3 or idx.shape[0] != b or idx.shape[2] < 1:
-        raise ValueError(f'{what}: expected idx[B = {b},M,k] with k >= 1, got {tuple(idx.shape)}')
-    m, k = idx.shape[1], idx.shape[2]
-    if m * k >= 1 << 31:
-        raise ValueError(f'{what}: idx[B,M,k] with M * k >= 2^31, got {tuple(idx.shape)}')
+    b, c, n = _features_arg(what, x, 'x')
+    m, k = _list_arg(what, idx, b)
     if tuple(weights.shape) != (b, m, k):
         raise ValueError(f'{what}: expected weights[B,M,k] = {(b, m, k)}, got {tuple(weights.shape)}')
     _float32('x', x)
-    if idx.dtype != I64:
-        raise RuntimeError(f'idx must be {I64}, found {idx.dtype}')
-    _same_device('idx', idx, x.device)
+    _list_on(idx, x.device)
     _float32('weights', weights)
     _same_device('weights', weights, x.device)
     return b, c, n, m, k
@@ -532,7 +561,7 @@ def torch_interpolate_points(x: torch.Tensor, idx: torch.Tensor, weights: torch.
         wj = torch.where(valid, weights[:, :, j], torch.zeros((), dtype=weights.dtype, device=weights.device))
         term = wj[:, None] * torch.gather(x, 2, safe[:, None, :].expand(-1, c, -1))  # (a masked NaN weight would reach x.grad as 0 * NaN)
         out = torch.where(valid[:, None], out + term, out)
-    return torch.where(torch.isnan(out), torch.full((), float('nan'), dtype=out.dtype, device=out.device), out)
+    return _canonical_nan(out)
 
 
 class Interpolated(Function):
@@ -612,18 +641,13 @@ def feature_propagation(xyz_dense: torch.Tensor, xyz_sparse: torch.Tensor, featu
     the torch formulas of the three functions (the search's expanded-form distances clamped at 0).  The arguments are
     checked before anything runs."""
     what = 'feature_propagation'
-    if xyz_dense.dim() != 3 or xyz_dense.shape[2] != 3:
-        raise ValueError(f'{what}: expected xyz_dense[B,M,3], got {tuple(xyz_dense.shape)}')
-    b, m = xyz_dense.shape[:2]
-    if xyz_sparse.dim() != 3 or xyz_sparse.shape[0] != b or xyz_sparse.shape[2] != 3 or xyz_sparse.shape[1] < 1:
-        raise ValueError(f'{what}: expected xyz_sparse[B = {b},N,3] with N >= 1, got {tuple(xyz_sparse.shape)}')
-    n = xyz_sparse.shape[1]
+    b, m = _cloud_arg(what, 'xyz_dense', xyz_dense, min_n=0, axis='M')
+    _, n = _cloud_arg(what, 'xyz_sparse', xyz_sparse, b)
     if features.dim() != 3 or features.shape[0] != b or features.shape[2] != n or features.shape[1] < 1:
         raise ValueError(f'{what}: expected features[B = {b},C,N = {n}] with C >= 1, got {tuple(features.shape)}')
     if skip is not None and (skip.dim() != 3 or skip.shape[0] != b or skip.shape[2] != m):
         raise ValueError(f'{what}: expected skip[B = {b},C2,M = {m}], got {tuple(skip.shape)}')
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 128:
-        raise ValueError(f'{what}: k must be an integer in [1, 128], got {k!r}')
+    _k_arg(what, k)
     dev = xyz_dense.device
     for name, t in (('xyz_dense', xyz_dense), ('xyz_sparse', xyz_sparse), ('features', features), ('skip', skip)):
         if t is not None:
@@ -653,10 +677,6 @@ class VoxelIndex(NamedTuple):
     cell: torch.Tensor    # [B,N] int32 flat cell (i * R + j) * R + k of every point, -1 for a non-finite point
     order: torch.Tensor   # [B,N] int32 permutation: the finite points by (cell, point index), then the non-finite ones
     counts: torch.Tensor  # [B,R,R,R] int32 points per cell
-
-
-def _canonical_nan32(t: torch.Tensor) -> torch.Tensor:
-    return torch.where(torch.isnan(t), torch.full((), float('nan'), dtype=t.dtype, device=t.device), t)
 
 
 def _voxel_cloud_args(xyz: torch.Tensor, what: str, b: int | None = None, n: int | None = None) -> tuple[int, int]:
@@ -714,7 +734,7 @@ def torch_voxelize(features: torch.Tensor, index: VoxelIndex) -> torch.Tensor:
     counts = index.counts.reshape(b, 1, bins)
     grid = torch.where(counts > 0, acc / torch.where(counts > 0, counts, torch.ones((), dtype=I32)).to(features.dtype),
                        torch.zeros((), dtype=features.dtype))
-    return _canonical_nan32(grid).view(b, c, res, res, res)
+    return _canonical_nan(grid).view(b, c, res, res, res)
 
 
 def _trilinear(xyz: torch.Tensor, res: int, lo32: torch.Tensor, inv: torch.Tensor) -> tuple[torch.Tensor, list[torch.Tensor], list[torch.Tensor]]:
@@ -747,7 +767,7 @@ def torch_devoxelize(grid: torch.Tensor, xyz: torch.Tensor, lo32: torch.Tensor, 
     for off, w in zip(offs, weights):
         out = out + w[:, None, :] * torch.gather(rows, 2, off[:, None, :].expand(b, c, n))
     out = torch.where(finite[:, None, :], out, torch.zeros((), dtype=grid.dtype, device=grid.device))
-    return _canonical_nan32(out)
+    return _canonical_nan(out)
 
 
 def voxel_index(xyz: torch.Tensor, resolution: int, lo: float = -0.5, extent: float = 1.0) -> VoxelIndex:
@@ -757,8 +777,6 @@ def voxel_index(xyz: torch.Tensor, resolution: int, lo: float = -0.5, extent: fl
     counted nowhere and comes last in ``order``.  ``N <= 16384``.  Every word is fixed by the cloud alone
     (``pcc_voxel_index``, include/pcc_neighbour.h); CPU tensors take the same rule in torch and give the same integers.
     Carries no gradient."""
-    from pointcloudcounterfactual_amd.set_metrics import _grid_args
-
     what = 'voxel_index'
     b, n = _voxel_cloud_args(xyz, what)
     lo32, inv, _ = _grid_args(resolution, False, lo, extent)
@@ -867,9 +885,7 @@ def voxelize(features: torch.Tensor, index_or_xyz: Any, resolution: int | None =
     divided by their number.  The HIP kernels on the accelerator, the same rule as a torch composition for CPU tensors: the
     forwards agree word for word."""
     what = 'voxelize'
-    if features.dim() != 3 or features.shape[1] < 1 or features.shape[2] < 1:
-        raise ValueError(f'{what}: expected features[B,C,N] with C >= 1 and N >= 1, got {tuple(features.shape)}')
-    b, c, n = features.shape
+    b, c, n = _features_arg(what, features)
     _float32('features', features)
     dev = features.device
     if isinstance(index_or_xyz, VoxelIndex):
@@ -902,17 +918,13 @@ def devoxelize(grid: torch.Tensor, xyz: torch.Tensor, lo: float = -0.5, extent: 
     summation order of that gradient is not fixed); ``xyz`` carries no gradient and may hold any number of points, not only
     those the grid was voxelised from.  The HIP kernels on the accelerator, the
     same rule as a torch composition for CPU tensors: the forwards agree word for word."""
-    from pointcloudcounterfactual_amd.set_metrics import _grid_args
-
     what = 'devoxelize'
     if grid.dim() != 5 or grid.shape[1] < 1 or not (grid.shape[2] == grid.shape[3] == grid.shape[4]):
         raise ValueError(f'{what}: expected grid[B,C,R,R,R] with C >= 1, got {tuple(grid.shape)}')
     b, c, res = grid.shape[:3]
     lo32, inv, _ = _grid_args(res, False, lo, extent)
     _float32('grid', grid)
-    if xyz.dim() != 3 or xyz.shape[0] != b or xyz.shape[2] != 3 or xyz.shape[1] < 1:  # (any N: only the index sort limits it)
-        raise ValueError(f'{what}: expected xyz[B = {b},N,3] with N >= 1, got {tuple(xyz.shape)}')
-    n = xyz.shape[1]
+    _, n = _cloud_arg(what, 'xyz', xyz, b)  # (any N: only the index sort limits it)
     _float32('xyz', xyz)
     _same_device('xyz', xyz, grid.device)
     _voxel_size_args(what, b, n, res)
@@ -931,9 +943,7 @@ def point_voxel(features: torch.Tensor, xyz: torch.Tensor, resolution: int, voxe
     ``devoxelize`` of its result at the same points: ``[B,C2,N]``.  Gradients reach ``features`` and the parameters of
     ``voxel_net``; ``xyz`` is a constant of the graph.  The arguments are checked before anything runs."""
     what = 'point_voxel'
-    if features.dim() != 3 or features.shape[1] < 1 or features.shape[2] < 1:
-        raise ValueError(f'{what}: expected features[B,C,N] with C >= 1 and N >= 1, got {tuple(features.shape)}')
-    b, _, n = features.shape
+    b, _, n = _features_arg(what, features)
     _voxel_cloud_args(xyz, what, b, n)
     _float32('features', features)
     _same_device('xyz', xyz, features.device)
@@ -952,24 +962,11 @@ def point_voxel(features: torch.Tensor, xyz: torch.Tensor, resolution: int, voxe
 
 def _geometry_args(xyz: torch.Tensor, idx: torch.Tensor, what: str) -> tuple[int, int, int, int]:
     """The checks ``local_covariance`` / ``local_geometry`` make before anything runs: ``(b, n, m, k)``."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < 1:
-        raise ValueError(f'{what}: expected xyz[B,N,3] with N >= 1, got {tuple(xyz.shape)}')
-    b, n = xyz.shape[:2]
-    if idx.dim() != 3 or idx.shape[0] != b or idx.shape[2] < 1:
-        raise ValueError(f'{what}: expected idx[B = {b},M,k] with k >= 1, got {tuple(idx.shape)}')
-    m, k = idx.shape[1], idx.shape[2]
-    if m * k >= 1 << 31:
-        raise ValueError(f'{what}: idx[B,M,k] with M * k >= 2^31, got {tuple(idx.shape)}')
+    b, n = _cloud_arg(what, 'xyz', xyz)
+    m, k = _list_arg(what, idx, b)
     _float32('xyz', xyz)
-    if idx.dtype != I64:
-        raise RuntimeError(f'idx must be {I64}, found {idx.dtype}')
-    _same_device('idx', idx, xyz.device)
+    _list_on(idx, xyz.device)
     return b, n, m, k
-
-
-def _canonical_nan(t: torch.Tensor) -> torch.Tensor:
-    """A NaN becomes the word 0x7fc00000."""
-    return torch.where(torch.isnan(t), torch.full((), float('nan'), dtype=t.dtype, device=t.device), t)
 
 
 def torch_local_covariance(xyz: torch.Tensor, idx: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -1141,13 +1138,10 @@ def estimate_normals(xyz: torch.Tensor, k: int = 16, idx: torch.Tensor | None = 
     ``return_curvature`` also the surface variation ``[B,N]``.  The inputs are detached: the outputs are constants of the
     graph."""
     what = 'estimate_normals'
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < 1:
-        raise ValueError(f'{what}: expected xyz[B,N,3] with N >= 1, got {tuple(xyz.shape)}')
-    b, n = xyz.shape[:2]
+    b, n = _cloud_arg(what, 'xyz', xyz)
     xyz = xyz.detach()
     if idx is None:
-        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 128:
-            raise ValueError(f'{what}: k must be an integer in [1, 128], got {k!r}')
+        _k_arg(what, k)
         _float32('xyz', xyz)
         idx = knn(xyz.transpose(1, 2).contiguous(), min(int(k), n))
     if viewpoint is not None:

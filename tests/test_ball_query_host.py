@@ -149,3 +149,16 @@ def test_the_switch_of_the_variants_is_bound():
 
     hooks = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'pcc_test_hooks.h')).read()
     assert re.search(r'PCC_TUNE_BALL_PATH = %d\b' % _lib.TUNING['ball_path'], hooks) and _lib.TUNING['ball_path'] == 13
+
+
+def test_cloud_shape_messages_word_for_word():
+    """The shape refusals of ``ball_query``, in their words, xyz before centres and both ahead of the dtypes."""
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests.util import raised
+
+    xyz, centres = torch.zeros(2, 10, 3), torch.zeros(2, 4, 3)
+    for bad, shown in ((xyz[0], '(10, 3)'), (xyz[:, :, :2], '(2, 10, 2)'), (xyz[:, :0], '(2, 0, 3)')):
+        assert raised(ValueError, ops.ball_query, bad.double(), centres[:1], 1.0, 4) == f'ball_query: expected xyz[B,N,3] with N >= 1, got {shown}'
+    for bad, shown in ((centres[0], '(4, 3)'), (centres[:, :, :2], '(2, 4, 2)'), (centres[:1], '(1, 4, 3)')):
+        assert raised(ValueError, ops.ball_query, xyz.double(), bad, 1.0, 4) == f'ball_query: expected centres[B = 2,M,3], got {shown}'
+    assert ops.ball_query(xyz, centres[:, :0], 1.0, 4).shape == (2, 0, 4)  # (no centre is no error)

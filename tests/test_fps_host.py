@@ -108,3 +108,15 @@ def test_c_abi_argument_checks_need_no_device():
                               (1, 8, 4, None, p), (1, 8, 4, p, None)):
         assert L.pcc_fps(b, n, m, xyz, None, idx, None, None) != 0, (b, n, m)
         assert L.pcc_last_error().decode().startswith('fps:')
+
+
+def test_cloud_shape_message_word_for_word():
+    """The shape refusal of ``farthest_point_sample``, in its words and ahead of the dtype."""
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests.util import raised
+
+    xyz = torch.zeros(2, 10, 3)
+    for bad, shown in ((xyz[0], '(10, 3)'), (xyz[:, :, :2], '(2, 10, 2)'), (xyz.transpose(1, 2), '(2, 3, 10)')):
+        assert raised(ValueError, ops.farthest_point_sample, bad.double(), 2) == f'farthest_point_sample: expected xyz[B,N,3], got {shown}'
+    assert raised(ValueError, ops.farthest_point_sample, xyz[:, :0], 1) == 'farthest_point_sample: m must be an int in [1, N = 0], got 1'
+    assert raised(RuntimeError, ops.farthest_point_sample, xyz[:, :0].double(), 1) == 'xyz must be torch.float32, found torch.float64'

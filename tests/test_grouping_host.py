@@ -202,3 +202,48 @@ def test_the_switch_of_the_paths_is_bound():
 
     hooks = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'pcc_test_hooks.h')).read()
     assert re.search(r'PCC_TUNE_GROUP_PATH = %d\b' % _lib.TUNING['group_path'], hooks) and _lib.TUNING['group_path'] == 14
+
+
+def test_messages_word_for_word():
+    """Every refusal ``group_points`` and ``pcc_group_points`` / ``_bwd`` share with the other list ops, in their words and in
+    the order in which a call with several bad arguments reports them."""
+    from pointcloudcounterfactual_amd import _lib
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests.util import c_status, raised
+
+    x, idx = torch.zeros(2, 4, 10), torch.zeros(2, 5, 3, dtype=torch.int64)
+    huge = torch.zeros(2, 1 << 16, 1 << 15, dtype=torch.int64, device='meta')
+    val = [((x[0], idx), 'expected x[B,C,N] with C >= 1 and N >= 1, got (4, 10)'),
+           ((x, idx[0]), 'expected idx[B = 2,M,k] with k >= 1, got (5, 3)'),
+           ((x, idx[:1]), 'expected idx[B = 2,M,k] with k >= 1, got (1, 5, 3)'),
+           ((x, idx[:, :, :0]), 'expected idx[B = 2,M,k] with k >= 1, got (2, 5, 0)'),
+           ((x, huge), 'idx[B,M,k] with M * k >= 2^31, got (2, 65536, 32768)'),
+           ((x.double(), idx.int()[:1]), 'expected idx[B = 2,M,k] with k >= 1, got (1, 5, 3)'),  # (shapes before dtypes)
+           ((x, idx, torch.zeros(2, 4, 4)), 'expected centres[B,C,M] = (2, 4, 5), got (2, 4, 4)')]
+    for args, text in val:
+        assert raised(ValueError, ops.group_points, *args) == 'group_points: ' + text
+    assert raised(RuntimeError, ops.group_points, x, idx.int()) == 'idx must be torch.int64, found torch.int32'
+    assert raised(RuntimeError, ops.group_points, x.double(), idx.int()) == 'x must be torch.float32, found torch.float64'
+    assert raised(RuntimeError, ops.group_points, x, idx.to('meta')) == 'idx is on meta, expected cpu'
+
+    L = _lib.lib
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.addressof(buf)
+    EINVAL = -22  # PCC_EINVAL (include/pcc_structural.h)
+    # (b, c, n, m, k, point_major, out_c, out_c0): the first refusal in the order of the checks wins
+    cases = [((-1, 3, 8, 4, 2, 0, 3, 0), 'bad size'), ((1, 0, 8, 4, 2, 0, 3, 0), 'bad size'), ((1, 3, 0, 4, 2, 0, 3, 0), 'bad size'),
+             ((1, 3, 8, -1, 2, 0, 3, 0), 'bad size'), ((1, 3, 8, 4, 0, 0, 3, 0), 'bad size'), ((65536, 0, 8, 4, 2, 0, 3, 0), 'bad size'),
+             ((65536, 3, 8, 4, 2, 0, 3, 0), 'batch too large'), ((65536, 3, 8, 1 << 16, 1 << 15, 0, 2, 0), 'batch too large'),
+             ((1, 3, 8, 1 << 16, 1 << 15, 0, 3, 0), 'list too long (m * k >= 2^31)'),
+             ((1, 3, 8, 1 << 16, 1 << 15, 2, 2, 0), 'list too long (m * k >= 2^31)'),
+             ((1, 3, 8, 4, 2, 0, 2, 0), 'channels out_c0 .. out_c0 + c - 1 are not inside out_c'),
+             ((1, 3, 8, 4, 2, 0, 3, 1), 'channels out_c0 .. out_c0 + c - 1 are not inside out_c'),
+             ((1, 3, 8, 4, 2, 0, 3, -1), 'channels out_c0 .. out_c0 + c - 1 are not inside out_c'),
+             ((1, 3, 8, 4, 2, 2, 3, 1), 'channels out_c0 .. out_c0 + c - 1 are not inside out_c'),
+             ((1, 3, 8, 4, 2, 2, 3, 0), 'point_major must be 0 or 1'), ((0, 3, 8, 0, 2, -1, 3, 0), 'point_major must be 0 or 1')]
+    for (b, c, n, m, k, pm, out_c, out_c0), text in cases:
+        assert c_status(L, L.pcc_group_points, b, c, n, m, k, pm, p, p, p, p, out_c, out_c0, None) == (EINVAL, 'group_points: ' + text)
+        assert c_status(L, L.pcc_group_points_bwd, b, c, n, m, k, pm, p, p, out_c, out_c0, p, p, None) == \
+            (EINVAL, 'group_points_bwd: ' + text)
+    assert c_status(L, L.pcc_group_points, 1, 3, 8, 4, 2, 0, None, p, p, p, 3, 0, None) == (EINVAL, 'group_points: null pointer')
+    assert c_status(L, L.pcc_group_points, 0, 3, 8, 4, 2, 0, None, None, None, None, 3, 0, None) == (0, '')  # (the error is cleared)

@@ -267,3 +267,52 @@ def test_the_abi_is_bound_and_no_tuning_key_was_added():
     assert len(_lib.ABI['pcc_local_geometry'][1]) == 12 and len(_lib.ABI['pcc_local_covariance_bwd'][1]) == 11
     assert re.search(r'PCC_TUNE_KEYS = 16\b', open(os.path.join(root, 'include', 'pcc_test_hooks.h')).read())
     assert max(_lib.TUNING.values()) == 15
+
+
+def test_messages_word_for_word():
+    """Every refusal ``local_covariance`` / ``local_geometry`` / ``estimate_normals`` and ``pcc_local_geometry`` /
+    ``pcc_local_covariance_bwd`` share with the other list ops, in their words and in the order in which a call with several
+    bad arguments reports them."""
+    from pointcloudcounterfactual_amd import _lib
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests.util import c_status, raised
+
+    xyz, idx = torch.zeros(2, 20, 3), torch.zeros(2, 7, 6, dtype=torch.int64)
+    huge = torch.zeros(2, 1 << 16, 1 << 15, dtype=torch.int64, device='meta')
+    val = [((xyz[0], idx), 'expected xyz[B,N,3] with N >= 1, got (20, 3)'),
+           ((xyz[:, :, :2], idx[:1]), 'expected xyz[B,N,3] with N >= 1, got (2, 20, 2)'),
+           ((xyz[:, :0], idx), 'expected xyz[B,N,3] with N >= 1, got (2, 0, 3)'),
+           ((xyz, idx[0]), 'expected idx[B = 2,M,k] with k >= 1, got (7, 6)'),
+           ((xyz, idx[:1]), 'expected idx[B = 2,M,k] with k >= 1, got (1, 7, 6)'),
+           ((xyz.double(), idx.int()[:, :, :0]), 'expected idx[B = 2,M,k] with k >= 1, got (2, 7, 0)'),  # (shapes before dtypes)
+           ((xyz, huge), 'idx[B,M,k] with M * k >= 2^31, got (2, 65536, 32768)')]
+    for what, fn in (('local_covariance', ops.local_covariance), ('local_geometry', ops.local_geometry)):
+        for args, text in val:
+            assert raised(ValueError, fn, *args) == f'{what}: {text}'
+        assert raised(RuntimeError, fn, xyz, idx.int()) == 'idx must be torch.int64, found torch.int32'
+        assert raised(RuntimeError, fn, xyz.double(), idx.int()) == 'xyz must be torch.float32, found torch.float64'
+        assert raised(RuntimeError, fn, xyz, idx.int().to('meta')) == 'idx must be torch.int64, found torch.int32'
+        assert raised(RuntimeError, fn, xyz, idx.to('meta')) == 'idx is on meta, expected cpu'
+    for bad, shown in ((xyz[0], '(20, 3)'), (xyz[:, :, :2], '(2, 20, 2)'), (xyz[:, :0], '(2, 0, 3)')):
+        assert raised(ValueError, ops.estimate_normals, bad, k='x') == f'estimate_normals: expected xyz[B,N,3] with N >= 1, got {shown}'
+    for k, shown in ((0, '0'), (129, '129'), (2.0, '2.0'), (True, 'True'), (None, 'None')):
+        assert raised(ValueError, ops.estimate_normals, xyz.double(), k=k) == \
+            f'estimate_normals: k must be an integer in [1, 128], got {shown}'  # (k before the dtype)
+    assert raised(RuntimeError, ops.estimate_normals, xyz.double()) == 'xyz must be torch.float32, found torch.float64'
+    assert raised(ValueError, ops.estimate_normals, xyz, k=0, idx=idx[:1]) == \
+        'local_geometry: expected idx[B = 2,M,k] with k >= 1, got (1, 7, 6)'  # (k is not looked at beside a list)
+
+    L = _lib.lib
+    buf = (ctypes.c_char * 128)()
+    p = ctypes.addressof(buf)
+    EINVAL = -22  # PCC_EINVAL (include/pcc_structural.h)
+    # (b, n, m, k): the first refusal in the order of the checks wins
+    cases = [((-1, 8, 4, 2), 'bad size'), ((1, 0, 4, 2), 'bad size'), ((1, -1, 4, 2), 'bad size'), ((1, 8, -1, 2), 'bad size'),
+             ((1, 8, 4, 0), 'bad size'), ((0, 8, 4, 0), 'bad size'), ((1, 0, 0, 2), 'bad size'), ((65536, 0, 4, 2), 'bad size'),
+             ((65536, 8, 4, 2), 'batch too large'), ((65536, 8, 1 << 16, 1 << 15), 'batch too large'),
+             ((1, 8, 1 << 16, 1 << 15), 'list too long (m * k >= 2^31)'), ((0, 8, 1 << 16, 1 << 15), 'list too long (m * k >= 2^31)')]
+    for s, text in cases:
+        assert c_status(L, L.pcc_local_geometry, *s, p, p, p, p, p, p, p, None) == (EINVAL, 'local_geometry: ' + text)
+        assert c_status(L, L.pcc_local_covariance_bwd, *s, p, p, p, p, p, p, None) == (EINVAL, 'local_covariance_bwd: ' + text)
+    assert c_status(L, L.pcc_local_geometry, 1, 8, 4, 2, None, p, p, p, p, p, p, None) == (EINVAL, 'local_geometry: null pointer')
+    assert c_status(L, L.pcc_local_geometry, 0, 8, 4, 2, None, None, p, p, p, p, p, None) == (0, '')  # (the error is cleared)

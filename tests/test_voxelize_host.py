@@ -226,6 +226,28 @@ def test_argument_errors():
             ops.point_voxel(*args, torch.nn.Identity())
 
 
+def test_messages_word_for_word():
+    """The refusals of ``voxelize``, ``devoxelize`` and ``point_voxel`` whose checks other ops share, in their words and in
+    the order in which a call with several bad arguments reports them."""
+    from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests.util import raised
+
+    xyz, x, grid = torch.rand(2, 10, 3), torch.zeros(2, 4, 10), torch.zeros(2, 4, 5, 5, 5)
+    index = ops.voxel_index(xyz, 5)
+    for bad, shown in ((x[0], '(4, 10)'), (x[:, :0], '(2, 0, 10)'), (x[:, :, :0], '(2, 4, 0)')):
+        text = f'expected features[B,C,N] with C >= 1 and N >= 1, got {shown}'
+        assert raised(ValueError, ops.voxelize, bad.double(), index) == 'voxelize: ' + text  # (the shape before the dtype)
+        assert raised(ValueError, ops.point_voxel, bad.double(), xyz[:1], 5, None) == 'point_voxel: ' + text
+    assert raised(RuntimeError, ops.voxelize, x.double(), None) == 'features must be torch.float32, found torch.float64'
+    assert raised(ValueError, ops.point_voxel, x.double(), xyz[:1], 5, None) == 'point_voxel: expected xyz[B = 2,N = 10,3], got (1, 10, 3)'
+    for bad, shown in ((xyz[:1], '(1, 10, 3)'), (xyz[0], '(10, 3)'), (xyz[:, :, :2], '(2, 10, 2)'), (xyz[:, :0], '(2, 0, 3)')):
+        assert raised(ValueError, ops.devoxelize, grid, bad.double()) == f'devoxelize: expected xyz[B = 2,N,3] with N >= 1, got {shown}'
+    assert raised(RuntimeError, ops.devoxelize, grid.double(), xyz[:1]) == 'grid must be torch.float32, found torch.float64'
+    assert raised(RuntimeError, ops.devoxelize, grid, xyz.double().to('meta')) == 'xyz must be torch.float32, found torch.float64'
+    assert raised(RuntimeError, ops.devoxelize, grid, xyz.to('meta')) == 'xyz is on meta, expected cpu'
+    assert raised(ValueError, ops.devoxelize, grid, xyz[:1], 0.0, 0.0) == 'extent must be finite and > 0, got 0.0'  # (the grid first)
+
+
 def _entry_points(L, p):
     """name -> call(b, c, n, res, lo, extent, q): the five functions with every pointer ``q``."""
     return {

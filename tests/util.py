@@ -43,6 +43,22 @@ def pair(seed: int, b: int, n: int, m: int | None = None, kind: str = 'recon'):
     return recon_cloud(rng, ref, n), ref
 
 
+def raised(kind: type, fn, *args, **kwargs) -> str:
+    """The message of the exception ``fn(*args, **kwargs)`` raises, which must be exactly a ``kind``."""
+    try:
+        fn(*args, **kwargs)
+    except Exception as e:
+        assert type(e) is kind, (type(e), kind, str(e))
+        return str(e)
+    raise AssertionError(f'{getattr(fn, "__name__", fn)} raised nothing')
+
+
+def c_status(lib, fn, *args) -> tuple[int, str]:
+    """``(return code, pcc_last_error())`` of one call into the C ABI."""
+    rc = fn(*args)
+    return rc, lib.pcc_last_error().decode()
+
+
 class host_independent_math:
     """Context manager: ``torch.sqrt`` / ``torch.exp`` of float32 tensors rounded from float64 while it is active.  Torch
     hands float32 sqrt / exp on the CPU to a vector-math library whose code path, and last bit, depends on the CPU
