@@ -157,6 +157,61 @@ int pcc_interpolate(int b, int c, int n, int m, int k, const float *x, const int
 int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const int64_t *idx, const float *w,
                         const float *grad_out, int out_c, int out_c0, float *grad_x, float *grad_w, pcc_stream_t stream);
 
+/* Vector attention (Point Transformer; the aggregation published implementations ship as pointops.aggregation): a softmax
+ * over the k slots of every row of a list that leaves out the slots the list has padded, and a weighted sum over the
+ * neighbourhood in which S = c / g consecutive channels share one weight and the values are gathered inside the kernel.
+ * No counterpart in the reference; what a user writes in torch instead materialises the gathered values, their sum with
+ * the position encoding and the product, three tensors of [b, c, m, k], and a masked_fill in front of the softmax.
+ *   layouts     x[b, c, n] and grad_x[b, c, n] channels-major; idx[b, m, k] int64 into the n points (m != n allowed: the list
+ *               of pcc_knn, pcc_knn_cross or pcc_ball_query); w, logits, attn and their gradients [b, g, m, k]; rel and
+ *               grad_rel [b, c, m, k], the layout pcc_group_points writes; out and grad_out [b, c, m].  float32 throughout.
+ *               The group of channel ch is ch / S: the S channels of a group are consecutive.
+ *   valid slots a slot is valid iff its index is in [0, n).  An invalid slot (the -1 of PCC_BALL_PAD_NONE) takes no part
+ *               in any sum, carries no gradient, whatever its weight, logit or rel word (a NaN included), and is +0.0
+ *               wherever a per-slot output is written.  A NaN result is written as the word 0x7fc00000.
+ *   pcc_neighbour_softmax      per row (b, gi, i): mx = the largest logit over the valid slots, e_j = exp(l_j - mx) in
+ *               float32 (one rounded difference), s = the sum of the e_j over the valid slots in slot order from +0.0,
+ *               attn_j = e_j / s, one division.  A row without a valid slot is all +0.0.  Non-finite logits behave as
+ *               torch.softmax restricted to the valid slots: a NaN, or a +inf maximum, makes the row's valid slots NaN, a
+ *               -inf slot beside a finite maximum is 0, a row whose valid logits are all -inf is NaN.  The words of exp are
+ *               not fixed by this contract (the device library's expf, 1 ulp); the order of the sum is, so every variant
+ *               returns the same words.  The tests bound attn against float64: |attn_j - ref_j| <= ((k + 8 + 4 |l_j - mx|)
+ *               2^-24) ref_j + 2^-126.
+ *   pcc_neighbour_softmax_bwd  d = the sum of (attn_j * grad_attn_j) over the valid slots in slot order from +0.0, a rounded
+ *               product and a rounded sum each; grad_logits_j = attn_j * (grad_attn_j - d), a rounded difference and a
+ *               rounded product.  The words are fixed.
+ *   pcc_aggregate_points       out[b, ch, i]: acc = +0.0f, then for every valid slot j in order v = x[b, ch, idx[b, i, j]]
+ *               (with a non-null rel v = x[b, ch, idx[b, i, j]] + rel[b, ch, i, j], one rounded sum) and acc = acc +
+ *               (w[b, ch / S, i, j] * v): a rounded product, then a rounded sum, not an fmaf.  The words are fixed; with
+ *               g = 1 and a null rel they are those of pcc_interpolate.  The weights are any numbers, not only the
+ *               output of the softmax.
+ *   pcc_aggregate_points_bwd   any subset of the three outputs; a null one costs nothing, all three null enqueue nothing.
+ *               grad_rel[b, ch, i, j] = w[b, ch / S, i, j] * grad_out[b, ch, i], one rounded product; every word is written,
+ *               the words are fixed; rel is not read.  grad_x[b, ch, t] = the sum of those same products over the valid
+ *               slots with idx[b, i, j] == t; every element is written, +0.0 where nothing points.  It is accumulated
+ *               with float atomics (LDS bins, or global memory where a cloud's bins do not fit LDS) after the runs of
+ *               equal consecutive indices have been summed inside a wave, as in pcc_group_points_bwd: the float summation
+ *               order of grad_x is not fixed.  grad_w[b, gi, i, j]: acc = +0.0f, then over the channels ch of the group in
+ *               ascending order acc = acc + (grad_out[b, ch, i] * v) with v as in the forward; the words are fixed.  x and
+ *               rel are read for grad_w only: x may be null when grad_w is.
+ * Every output word depends on the row's own inputs only: not on b, m, the position in the batch or the variant that ran.
+ * Requires c >= 1, g >= 1, c % g == 0, n >= 1, 1 <= k <= 128 (what the searches return), m >= 0, b <= 65535, m * k < 2^31
+ * (PCC_EINVAL otherwise, under "neighbour_softmax:" / "neighbour_softmax_bwd:" / "aggregate_points:" /
+ * "aggregate_points_bwd:", sizes before pointers, before anything is enqueued) and non-null idx, logits, attn / idx, attn,
+ * grad_attn, grad_logits / x, idx, w, out / idx, w, grad_out; rel may be null.  b = 0 enqueues nothing and returns PCC_OK;
+ * m = 0: the forwards enqueue nothing, the backward zero-fills grad_x.  64-bit offsets throughout, no workspace, no host
+ * synchronisation, and no n is refused: where a channel row of a cloud does not fit a workgroup's LDS beside the forward's
+ * tile (n > 39424; for the bins of grad_x n > 40960) the gathers and the atomics go to global memory. */
+int pcc_neighbour_softmax(int b, int g, int n, int m, int k, const int64_t *idx, const float *logits, float *attn,
+                          pcc_stream_t stream);
+int pcc_neighbour_softmax_bwd(int b, int g, int n, int m, int k, const int64_t *idx, const float *attn, const float *grad_attn,
+                              float *grad_logits, pcc_stream_t stream);
+int pcc_aggregate_points(int b, int c, int g, int n, int m, int k, const float *x, const int64_t *idx, const float *w,
+                         const float *rel, float *out, pcc_stream_t stream);
+int pcc_aggregate_points_bwd(int b, int c, int g, int n, int m, int k, const float *x, const int64_t *idx, const float *w,
+                             const float *rel, const float *grad_out, float *grad_x, float *grad_w, float *grad_rel,
+                             pcc_stream_t stream);
+
 /* Local surface geometry: for every row of an index list idx[b, m, k] int64 into the cloud xyz[b, n, 3] (point-major float32,
  * the layout of pcc_fps and pcc_ball_query; m != n allowed: the list of pcc_knn, pcc_knn_cross or pcc_ball_query) the mean of
  * the points it names, their scatter matrix, its eigen-decomposition and the surface variation: mean[b, m, 3],

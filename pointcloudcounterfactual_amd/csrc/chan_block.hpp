@@ -1,7 +1,7 @@
-// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip, interpolate.hip): a workgroup owns CB
-// channels of one sample and keeps their rows of x, or their gradient bins, in LDS.  How the ids are dealt, how much LDS a
-// workgroup may take, how CB is chosen, how the kernel template is picked for it, and how the list of a sample is split
-// over several such workgroups.
+// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip, interpolate.hip, attention.hip): a
+// workgroup owns CB channels of one sample and keeps their rows of x, or their gradient bins, in LDS.  How the ids are
+// dealt, how much LDS a workgroup may take, how CB is chosen, how the kernel template is picked for it, and how the list of
+// a sample is split over several such workgroups.
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -44,7 +44,7 @@ void dispatch_cb(int cb, F &&f) {
 }
 
 // ---- CB channels of a sample x a split of a per-sample list (grouping.hip: the m * k slots; interpolate.hip: the m dense
-// points) ----
+// points; attention.hip: the dense points forward, the slots backward) ----
 constexpr int kWgThreads = 1024;         // threads of such a workgroup at the most
 constexpr int kCbDirect = 8;             // channels per workgroup of the direct path (nothing to fit)
 constexpr long long kMaxGrid = 1 << 20;  // workgroups per launch; the kernels stride over the units beyond
