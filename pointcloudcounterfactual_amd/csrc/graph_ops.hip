@@ -140,8 +140,12 @@ __global__ __launch_bounds__(1024) void gather_lds_kernel(int c, int n, int k, c
                         if (MODE == kNbrSum) {
                             acc[cc] += v;
                         } else {
-                            const bool gt = (j == 0) || v > acc[cc];
-                            const bool lt = (j == 0) || v < lo[cc];
+                            // NaN wins both and sticks, as in kMaxPool below and torch.max / torch.min: the first NaN's
+                            // target is kept ("not <=" is "greater, or v is NaN").  A NaN enters acc and lo at the same j,
+                            // so one test serves both: with it an accumulator that is NaN no longer moves
+                            const bool live = acc[cc] == acc[cc];
+                            const bool gt = (j == 0) || (!(v <= acc[cc]) && live);
+                            const bool lt = (j == 0) || (!(v >= lo[cc]) && live);
                             acc[cc] = gt ? v : acc[cc];
                             tb[cc] = gt ? t : tb[cc];
                             lo[cc] = lt ? v : lo[cc];

@@ -14,10 +14,28 @@ and, because BatchNorm is a per-channel affine map and the activation is increas
     max_j act(bn(z_j)) = act(bn(max_j z_j))  if the BatchNorm scale of the channel is >= 0, act(bn(min_j z_j)) otherwise,
     max_j z_j = max_j y1[idx[n,j]] + y2[n]   (y2 does not depend on j).
 
-Training-mode BatchNorm statistics over (b,n,j) are exact sums of ``[B,C',N]`` quantities:
+In float32 the products must not carry what ``x_j`` and ``x_n`` share: a cloud that sits at distance D from the origin
+would round ``Wa x_j`` and ``Wa x_n`` at ``u D |Wa|`` each before the difference is formed, where the unfused block rounds
+``x_j - x_n`` at ``u |x_j - x_n|``.  For ANY constant ``mu`` (per sample and channel)
 
-    sum z   = sum_t deg[t] y1[t] + k sum_n y2[n]
-    sum z^2 = sum_t deg[t] y1[t]^2 + k sum_n y2[n]^2 + 2 sum_n y2[n] S1[n],      S1[n] = sum_j y1[idx[n,j]]
+    z[b,:,n,j] = Wa (xc_j - xc_n) + Wb (xc_n + mu) = y1[b,:,idx[n,j]] + y2[b,:,n] + c0[b,:],
+    xc = x - mu,   y1 = Wa xc,   y2 = (Wb - Wa) xc,   c0 = Wb mu
+
+is the same function of ``x``, so ``mu`` is a detached number: the sample's own mean over n with non-finite entries
+counted as 0 (per sample: eval mode must not couple the samples of a batch; finite: one NaN or inf point must not reach
+the other points through ``mu``).  The gradients are those of the unfused block whatever ``mu`` is.  ``c0`` is the only
+large term left and BatchNorm takes most of it away again, so it never enters a float32 sum: ``c0 - mean`` is formed in
+double, and the output is ``act((y1[t] + y2[n] + (c0 - mean)) scale + beta)``.
+
+Training-mode BatchNorm statistics over (b,n,j) are exact sums of ``[B,C',N]`` quantities, taken in double:
+
+    sum z          = sum_t deg[t] y1[t] + k sum_n (y2[n] + c0)
+    sum (z - m)^2  = sum_t deg[t] y1[t]^2 + k sum_n y2m[n]^2 + 2 sum_n y2m[n] S1[n],
+                     y2m = y2 + c0 - m,   m = sum z / (B N k),   S1[n] = sum_j y1[idx[n,j]]
+
+The variance is centred, not ``E[z^2] - m^2``: in the backward of the latter the edge terms ``2 (y2[n] + c0) / M`` reach the
+float32 neighbour-sum scatter before ``2 m deg[t] / M`` cancels them, which cost the input gradient a factor 5 off the
+origin (tests/edgeconv_reference.py holds every output, gradient and statistic to float64; DESIGN.md 4n has the table).
 
 (``deg[t]`` = in-degree of t in the kNN graph).  Everything is differentiable PyTorch on ``[B,C',N]`` tensors plus three
 small HIP kernels (neighbour sum and its scatter backward, min/max neighbour selection), so autograd gives the exact
@@ -80,33 +98,38 @@ class FusedEdgeConv(nn.Module):
         k = idx.shape[2]
         w = self.conv.weight[:, :, 0, 0]
         wa, wb = w[:, :c], w[:, c:]
-        y1 = torch.matmul(wa, x)                                          # [B,C',N]
-        y2 = torch.matmul(wb - wa, x)
+        # a constant per (sample, channel) near the cloud's centre (module docstring); non-finite points count as 0, so one
+        # of them cannot poison its sample, and no other sample enters, so eval does not couple the samples of a batch
+        mu = torch.nan_to_num(x.detach(), nan=0.0, posinf=0.0, neginf=0.0).mean(dim=2, keepdim=True)
+        xc = x - mu
+        y1 = torch.matmul(wa, xc)                                         # [B,C',N]
+        y2 = torch.matmul(wb - wa, xc)
+        c0 = torch.matmul(wb, mu).double()                                # [B,C',1]: z = y1[t] + y2[n] + c0
         if self.training or not self.bn.track_running_stats:
             m = float(b * n * k)
             deg = torch.zeros((b, n), dtype=torch.float32, device=x.device)
             deg.scatter_add_(1, idx.reshape(b, -1), torch.ones((b, n * k), dtype=torch.float32, device=x.device))
             s1 = neighbour_sum(y1, idx)
-            y1d, y2d, s1d, degd = y1.double(), y2.double(), s1.double(), deg.double()[:, None, :]
-            sum_z = (degd * y1d).sum((0, 2)) + k * y2d.sum((0, 2))
-            sum_z2 = (degd * y1d * y1d).sum((0, 2)) + k * (y2d * y2d).sum((0, 2)) + 2.0 * (y2d * s1d).sum((0, 2))
-            mean = sum_z / m
-            var = (sum_z2 / m - mean * mean).clamp_min(0.0)                # biased, as BatchNorm normalises with
+            y1d, y2d, s1d, degd = y1.double(), y2.double() + c0, s1.double(), deg.double()[:, None, :]
+            mean = ((degd * y1d).sum((0, 2)) + k * y2d.sum((0, 2))) / m
+            y2m = y2d - mean[None, :, None]
+            sum_d2 = (degd * y1d * y1d).sum((0, 2)) + k * (y2m * y2m).sum((0, 2)) + 2.0 * (y2m * s1d).sum((0, 2))
+            var = (sum_d2 / m).clamp_min(0.0)                              # biased, as BatchNorm normalises with
             if self.training and self.bn.track_running_stats:
                 with torch.no_grad():
                     mom = self.bn.momentum
                     self.bn.running_mean.mul_(1 - mom).add_(mom * mean.float())
                     self.bn.running_var.mul_(1 - mom).add_(mom * (var * m / max(m - 1.0, 1.0)).float())
                     self.bn.num_batches_tracked += 1
-            mean, var = mean.float(), var.float()
+            var = var.float()
         else:
-            mean, var = self.bn.running_mean, self.bn.running_var
+            mean, var = self.bn.running_mean.double(), self.bn.running_var
         scale = self.bn.weight * torch.rsqrt(var + self.bn.eps)
-        shift = self.bn.bias - mean * scale
+        off = (c0 - mean[None, :, None]).float()                          # [B,C',1]
         tsel = neighbour_minmax_target(y1, idx)                           # [B,2,C',N]
         pick = torch.where((scale >= 0)[None, :, None], tsel[:, 0], tsel[:, 1])
-        z = torch.gather(y1, 2, pick) + y2                                # the edge that survives max over k
-        return self.act(z * scale[None, :, None] + shift[None, :, None])
+        z = torch.gather(y1, 2, pick) + y2 + off                          # the edge that survives max over k, minus the mean
+        return self.act(z * scale[None, :, None] + self.bn.bias[None, :, None])
 
 
 def reference_edgeconv(x: torch.Tensor, idx: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, act: nn.Module) -> torch.Tensor:
