@@ -212,6 +212,49 @@ int pcc_aggregate_points_bwd(int b, int c, int g, int n, int m, int k, const flo
                              const float *rel, const float *grad_out, float *grad_x, float *grad_w, float *grad_rel,
                              pcc_stream_t stream);
 
+/* Kernel point convolution (rigid KPConv, Thomas et al. 2019): the features of the neighbours a list names, weighted by the
+ * influence of each of kp kernel points on each neighbour and summed per kernel point.  The convolution proper is then
+ * W.view(O, kp * c) @ out, one batched GEMM that stays with the caller.  No counterpart in the reference; what a user writes
+ * in torch instead gathers [b, c, m, k] and [b, m, k, 3], forms [b, m, k, kp, 3] differences and a matmul per centre.
+ *   layouts     xyz[b, n, 3] and centres[b, m, 3] point-major (the layout of pcc_fps and pcc_ball_query); idx[b, m, k] int64
+ *               into the n points (m != n allowed); x[b, c, n] and grad_x[b, c, n] channels-major; kernel_points[kp, 3],
+ *               shared by the batch; out and grad_out [b, kp * c, m], channel t * c + ch belonging to kernel point t.
+ *               float32 throughout.
+ *   valid slots a slot is valid iff its index is in [0, n): the -1 of PCC_BALL_PAD_NONE and KPConv's shadow index n are
+ *               not.  An invalid slot takes no part in anything.
+ *   influence   inv = 1.0f / sigma, computed once on the host in float32.  For a valid slot j of centre i and kernel point
+ *               t, every operation float32 and rounded, no fmaf (the file is built with -ffp-contract=off):
+ *               r_a = xyz[b, idx[b, i, j], a] - centres[b, i, a]; e_a = r_a - kernel_points[t, a];
+ *               d2 = (e_x * e_x + e_y * e_y) + e_z * e_z; d = sqrtf(d2), correctly rounded; v = 1.0f - d * inv;
+ *               h = v > 0 ? v : +0.0 (KPConv's "linear" influence).  A NaN or infinite distance therefore gives h = +0.0.
+ *               The words of h are fixed.
+ *   forward     out[b, t * c + ch, i]: acc = +0.0f, then over the valid slots in slot order, for every pair with h > 0,
+ *               acc = acc + (h * x[b, ch, idx[b, i, j]]): a rounded product, then a rounded sum.  A pair with h = +0.0 is
+ *               skipped by definition, whatever the feature word, a NaN included.  Elsewhere IEEE holds; a NaN result is
+ *               written as the word 0x7fc00000.  The words are fixed: every output word depends on the row's own inputs
+ *               only, not on b, m, the position in the batch or the variant that ran.
+ *   backward    per valid slot and channel p = +0.0f, then over t ascending, for the pairs with h > 0,
+ *               p = p + (h * grad_out[b, t * c + ch, i]).  grad_x[b, ch, u] = the sum of the words p over the valid slots
+ *               with idx[b, i, j] == u; every element is written, +0.0 where nothing points.  It is accumulated with float
+ *               atomics (LDS bins, or global memory where a cloud's bins do not fit LDS) after the runs of equal
+ *               consecutive indices have been summed inside a wave, as in pcc_aggregate_points_bwd: only this order is not
+ *               fixed.  Coordinates and kernel points carry no gradient.
+ * Other contracts, not this one: deformable KPConv (kernel points per centre, gradients in the coordinates), the Gaussian
+ * and constant influences, the division by the neighbour count, and the GEMM fused into the kernel.
+ * Requires c >= 1, n >= 1, k >= 1, m >= 0, b <= 65535, m * k < 2^31 (the messages of the other list ops), then 1 <= kp <= 32
+ * ("kernel points must be 1..32"), k <= 128 ("k > 128"), sigma finite and > 0 ("sigma must be finite and > 0"), then
+ * non-null pointers ("null pointer"): PCC_EINVAL otherwise, under "kpconv_aggregate:" / "kpconv_aggregate_bwd:", sizes before
+ * pointers, before anything is enqueued.  b = 0 enqueues nothing and returns PCC_OK; m = 0: the forward enqueues nothing, the
+ * backward zero-fills grad_x.  64-bit offsets throughout, no workspace, no host synchronisation, and no n is refused: the
+ * forward gathers the features of the pairs with h > 0 from global memory for every n, and where the bins of a channel of
+ * grad_x do not fit a workgroup's LDS (n > 40960) the backward's atomics go to global memory. */
+int pcc_kpconv_aggregate(int b, int c, int n, int m, int k, int kp, const float *xyz, const float *centres,
+                         const int64_t *idx, const float *x, const float *kernel_points, float sigma, float *out,
+                         pcc_stream_t stream);
+int pcc_kpconv_aggregate_bwd(int b, int c, int n, int m, int k, int kp, const float *xyz, const float *centres,
+                             const int64_t *idx, const float *kernel_points, float sigma, const float *grad_out,
+                             float *grad_x, pcc_stream_t stream);
+
 /* Local surface geometry: for every row of an index list idx[b, m, k] int64 into the cloud xyz[b, n, 3] (point-major float32,
  * the layout of pcc_fps and pcc_ball_query; m != n allowed: the list of pcc_knn, pcc_knn_cross or pcc_ball_query) the mean of
  * the points it names, their scatter matrix, its eigen-decomposition and the surface variation: mean[b, m, 3],

@@ -46,9 +46,9 @@ enum {
                                       staged through LDS, 4 queries x tiles of 1024 / 16 queries x tiles of 4096 (the product's choice) */
     PCC_TUNE_GROUP_PATH = 14,      /* pcc_group_points / _bwd: 1 = the LDS path (ignored where not one channel row of n points fits a
                                       workgroup's LDS), 2 = the direct path (global gathers, global float atomics) */
-    PCC_TUNE_INTERP_PATH = 15,     /* pcc_interpolate / _bwd and pcc_aggregate_points / _bwd (forward and grad_x): 1 = the LDS path (ignored
-                                      where not one channel row of n points fits a workgroup's LDS), 2 = the direct path (global gathers,
-                                      global float atomics) */
+    PCC_TUNE_INTERP_PATH = 15,     /* pcc_interpolate / _bwd, pcc_aggregate_points / _bwd (forward and grad_x) and
+                                      pcc_kpconv_aggregate_bwd: 1 = the LDS path (ignored where not one channel row of n points fits a
+                                      workgroup's LDS), 2 = the direct path (global gathers, global float atomics) */
     PCC_TUNE_KEYS = 16            /* keys are 0 .. PCC_TUNE_KEYS - 1 */
 };
 int pcc_test_set_tuning(int key, int value);

@@ -21,6 +21,7 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     torch_sliced_wasserstein,
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
+    KernelPointConv,
     VoxelIndex,
     aggregate_points,
     attention_aggregate,
@@ -32,6 +33,10 @@ from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     group_points,
     interpolate_points,
     interpolation_weights,
+    kernel_point_conv,
+    kernel_point_influence,
+    kernel_point_layout,
+    kpconv_aggregate,
     local_covariance,
     local_geometry,
     neighbour_softmax,
@@ -49,4 +54,5 @@ __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer
            'local_covariance', 'local_geometry', 'estimate_normals', 'sliced_wasserstein', 'torch_sliced_wasserstein',
            'random_directions', 'sinkhorn_divergence', 'sinkhorn_schedule', 'torch_sinkhorn', 'VoxelIndex', 'voxel_index',
            'voxelize', 'devoxelize', 'point_voxel', 'neighbour_softmax', 'aggregate_points', 'attention_aggregate',
-           'vector_attention']
+           'vector_attention', 'kernel_point_layout', 'kernel_point_influence', 'kpconv_aggregate', 'kernel_point_conv',
+           'KernelPointConv']

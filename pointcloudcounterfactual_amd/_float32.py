@@ -1,5 +1,5 @@
 """Float32 arithmetic of the HIP kernels restated exactly in torch, for the CPU paths that promise the kernels' bits
-(``set_metrics.occupancy_grid``, ``neighbour_ops.ball_query``)."""
+(``set_metrics.occupancy_grid``, ``neighbour_ops.ball_query``, ``neighbour_ops.kernel_point_influence``)."""
 
 from __future__ import annotations
 
@@ -17,3 +17,10 @@ def fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     bits = s.view(torch.int64)
     odd = (torch.where(err < 0, bits - 1, bits) | 1).view(torch.float64)  # truncate towards 0 (s > 0 here), then the sticky bit
     return torch.where(torch.isfinite(s) & (err != 0), odd, s).float()
+
+
+def sqrt32(a: torch.Tensor) -> torch.Tensor:
+    """``sqrtf(a)`` of a float32 tensor, correctly rounded.  Torch hands the float32 square root on the CPU to a vector-math
+    library that may be an ulp off; the float64 root rounded to float32 is the correctly rounded one (53 >= 2 * 24 + 2 bits:
+    the second rounding cannot move it)."""
+    return torch.sqrt(a.double()).float()

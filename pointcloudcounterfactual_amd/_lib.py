@@ -68,6 +68,8 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_neighbour_softmax_bwd': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_aggregate_points': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_aggregate_points_bwd': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_kpconv_aggregate': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    'pcc_kpconv_aggregate_bwd': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
     'pcc_local_geometry': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_local_covariance_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_voxel_index': (_int, [_int, _int, _vp, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
