@@ -29,7 +29,8 @@ extern "C" {
  *            (the reference CPU path's formula, self_square_distance :53-60): (-2*dot + |x_j|^2) + |x_i|^2 with
  *            dot and |x|^2 sequential fma chains over the channel index
  * Any c >= 1; requires 1 <= k <= min(n, 128) (k > 128: PCC_EINVAL).  A NaN distance never enters a list; a list that
- * runs short because of NaN distances is padded with the in-range index n - 1. */
+ * runs short because of NaN distances is padded with the in-range index n - 1.  A +inf distance (a norm or a squared
+ * difference that overflows) is a distance like any other: it is listed, behind the finite ones, in index order. */
 int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_stream_t stream);
 
 /* k-NN between two clouds: for every query q[b, :, i] (q[b, c, nq], channels-major like x) its k nearest candidates of
@@ -39,7 +40,7 @@ int pcc_knn(int b, int c, int n, int k, const float *x, int64_t *indices, pcc_st
  *   c >= 4 : expanded form (-2*dot + |x_j|^2) + |q_i|^2, dot and both norms sequential fma chains over the channel index
  * Per query the k candidates ascending by (distance, index); -0 equals +0 (and is reported as +0); a NaN distance never
  * enters a list; a list that runs short because of NaN distances is padded with index n - 1, and dist of a padded slot is
- * NaN.  Requires c >= 1, 1 <= k <= min(n, 128), b <= 65535, b * nq < 2^31, and n <= 65535 * 128 when c >= 4
+ * NaN; a +inf distance is listed like any other and reported as +inf.  Requires c >= 1, 1 <= k <= min(n, 128), b <= 65535, b * nq < 2^31, and n <= 65535 * 128 when c >= 4
  * (PCC_EINVAL otherwise); nq = 0 or b = 0 enqueues nothing and returns PCC_OK.  64-bit offsets throughout.  Workspace
  * comes from the library's private pool; the distance rows of c >= 4 are capped at 256 MB per launch pair (larger calls
  * run in chunks of samples or of queries).  With few queries and many candidates the candidate axis is searched in slices

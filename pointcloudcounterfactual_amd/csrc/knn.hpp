@@ -15,6 +15,32 @@ __device__ __forceinline__ f32x16 zero16() {
     return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 }
 
+// The +inf tail of a list.  The exhaustive k <= 32 kernels (knn_small_kernel, knn_mfma_kernel, knn_mfma_split_kernel) take a
+// candidate with a strict `x < threshold`, the threshold starting at +inf, and use +inf as their "no candidate" value: a
+// +inf distance (a norm or a squared difference that overflows) never enters their lists, though the contract lists it
+// like any other distance -- only NaN is left out.  So when the scan ends with fewer than k entries, everything still
+// missing is at +inf or NaN, and the row's owner completes it here: the candidates whose distance is exactly +inf, in
+// index order, into the slots filled .. k - 1.  dist(j) is the kernel's own distance expression, store(slot, j) writes a
+// slot.  Finite clouds never get here; the loop is a plain walk over the cloud in global memory.  -> slots filled.
+template <class DistF, class StoreF>
+__device__ __forceinline__ int fill_inf_tail(int filled, int k, int n, DistF &&dist, StoreF &&store) {
+    for (int j = 0; j < n && filled < k; j++) {
+        if (dist(j) == __builtin_inff()) {
+            store(filled, j);
+            filled++;
+        }
+    }
+    return filled;
+}
+
+// the expanded-form distance of candidate j to query q of one cloud xb[c][n], as the MFMA kernels round it: the inner
+// product one fma chain in channel order, then (-2 dot + |x_j|^2) + |x_q|^2
+__device__ __forceinline__ float expanded_dist(const float *xb, const float *sqb, int c, int n, int q, float sq_q, int j) {
+    float dot = 0.f;
+    for (int ch = 0; ch < c; ch++) dot = __builtin_fmaf(xb[(size_t)ch * n + j], xb[(size_t)ch * n + q], dot);
+    return __builtin_fmaf(-2.0f, dot, sqb[j]) + sq_q;
+}
+
 // list slots of the instantiations for k <= 32
 constexpr int kSlots[] = {4, 8, 16, 20, 25, 32};
 

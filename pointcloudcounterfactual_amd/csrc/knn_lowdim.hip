@@ -24,8 +24,9 @@ struct SmallLayout {
 // go to the lower candidate index: a wave's list is in (distance, index) order, but the waves' candidate ranges
 // interleave (wave w takes the w-th quarter of EVERY 2048-candidate chunk), so from the second chunk on "the earlier
 // wave" is not "the lower index".
+// -> the slots that took a list entry; the others are padded with n - 1.
 template <int K, int S>
-__device__ __forceinline__ void merge_and_store(const float *md, const int *mi, int lane, int k, int64_t *dst, int n) {
+__device__ __forceinline__ int merge_and_store(const float *md, const int *mi, int lane, int k, int64_t *dst, int n) {
     // heads as 64-bit keys (distance bits : index): the distances are non-negative and never NaN, so they order like
     // unsigned integers and one compare is "smaller distance, then lower index"; a list that has run out heads kKeyInf
     const auto entry = [&](int s, int pos) -> unsigned long long {
@@ -33,6 +34,7 @@ __device__ __forceinline__ void merge_and_store(const float *md, const int *mi, 
     };
     int p[S];
     unsigned long long h[S];
+    int filled = 0;
 #pragma unroll
     for (int s = 0; s < S; s++) {
         p[s] = 0;
@@ -50,8 +52,9 @@ __device__ __forceinline__ void merge_and_store(const float *md, const int *mi, 
         int pos = 0;
 #pragma unroll
         for (int s = 0; s < S; s++) pos = (best == s) ? p[s] : pos;
-        // (a list can run out only when distances are NaN: never emit an index outside the cloud)
+        // (the lists run out when fewer than k distances are finite: never emit an index outside the cloud)
         dst[o] = (int64_t)min((int)(bv & 0xffffffffull), n - 1);
+        filled += (unsigned)bv != 0x7fffffffu ? 1 : 0;
         const int np = pos + 1;
         const unsigned long long nh = np < K ? entry(best, np) : pcc::kKeyInf;
 #pragma unroll
@@ -61,6 +64,7 @@ __device__ __forceinline__ void merge_and_store(const float *md, const int *mi, 
             h[s] = sel ? nh : h[s];
         }
     }
+    return filled;
 }
 
 template <int K, int S>
@@ -130,7 +134,19 @@ __global__ __launch_bounds__(64 * S) void knn_small_kernel(int c, int n, int k, 
         mrg_i[(w * K + s) * 64 + lane] = tk.top.i[s];
     }
     __syncthreads();
-    if (w == 0 && q_ok) merge_and_store<K, S>(mrg_d, mrg_i, lane, k, indices + ((size_t)smp * n + q) * k, n);
+    if (w == 0 && q_ok) {
+        int64_t *dst = indices + ((size_t)smp * n + q) * k;
+        const int filled = merge_and_store<K, S>(mrg_d, mrg_i, lane, k, dst, n);
+        // the lists hold finite distances only: a short row continues with its +inf distances (see fill_inf_tail)
+        if (filled < k)
+            fill_inf_tail(
+                filled, k, n,
+                [&](int j) {
+                    const float dx = xb[j] - qx, dy = (c > 1 ? xb[(size_t)n + j] : 0.f) - qy, dz = (c > 2 ? xb[(size_t)2 * n + j] : 0.f) - qz;
+                    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                },
+                [&](int slot, int j) { dst[slot] = (int64_t)j; });
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -332,7 +348,8 @@ __global__ __launch_bounds__(64 * kSW, (K == 16 ? 3 : K <= 25 ? 4 : 1)) void knn
                 bv = lt ? h[s] : bv;
                 best = lt ? s : best;
             }
-            // (the lists can run short only when distances are NaN: never emit an index outside the cloud)
+            // (the lists run short only when fewer than k distances are not NaN -- a +inf distance has a key below
+            // kKeyInf and enters like any other: never emit an index outside the cloud)
             dst[o] = (int64_t)min((int)(bv & 0xffffffffull), n - 1);
             int np = 0;
 #pragma unroll

@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256, CP >= 128 ? 2 : 1) void knn_mfma_kernel(int c,
         const float *d0 = mrg_d + ((w * 2 + 0) * K) * 32 + col, *d1 = mrg_d + ((w * 2 + 1) * K) * 32 + col;
         const int *i0 = mrg_i + ((w * 2 + 0) * K) * 32 + col, *i1 = mrg_i + ((w * 2 + 1) * K) * 32 + col;
         int p0 = 0, p1 = 0;
+        int filled = 0;  // slots that took a list entry (an empty slot of either list has index 0x7fffffff)
         int64_t *dst = indices + ((size_t)smp * n + q) * k;
         for (int o = 0; o < k; o++) {
             const float a = p0 < K ? d0[p0 * 32] : __builtin_inff();
@@ -185,10 +186,17 @@ __global__ __launch_bounds__(256, CP >= 128 ? 2 : 1) void knn_mfma_kernel(int c,
             const int ia = p0 < K ? i0[p0 * 32] : 0x7fffffff;
             const int ib = p1 < K ? i1[p1 * 32] : 0x7fffffff;
             const bool take0 = (a < bb) || (a == bb && ia < ib);
-            dst[o] = (int64_t)min(take0 ? ia : ib, n - 1);
+            const int id = take0 ? ia : ib;
+            dst[o] = (int64_t)min(id, n - 1);  // (n - 1: the padding of a list that stays short)
+            filled += id != 0x7fffffff ? 1 : 0;
             p0 += take0 ? 1 : 0;
             p1 += take0 ? 0 : 1;
         }
+        // the lists hold finite distances only: a short row continues with its +inf distances (see fill_inf_tail)
+        if (filled < k)
+            fill_inf_tail(
+                filled, k, n, [&](int j) { return expanded_dist(xb, sqb, c, n, q, sq_q, j); },
+                [&](int slot, int j) { dst[slot] = (int64_t)j; });
     }
 }
 
@@ -513,6 +521,12 @@ __global__ __launch_bounds__(512) void knn_mfma_split_kernel(int c, int n, int k
             out[pos * 256] = __float_as_int(e.y);
         }
     }
+    // `ties` slots are filled.  Fewer than k: the list holds finite distances only (nothing at +inf passes a strict
+    // compare, in the screen or in the rounds), so the row continues with its +inf distances (see fill_inf_tail)
+    if (ties < k)
+        fill_inf_tail(
+            ties, k, n, [&](int j) { return expanded_dist(xb, sqb, c, n, q, sq_q, j); },
+            [&](int slot, int j) { out[slot * 256] = j; });
     // a wave writes the rows of its 64 queries with consecutive lanes on consecutive words
     __builtin_amdgcn_wave_barrier();
     const int wq = (w - 4) * 64;  // first local query of this wave
@@ -523,7 +537,7 @@ __global__ __launch_bounds__(512) void knn_mfma_split_kernel(int c, int n, int k
     for (int e = lane; e < total; e += 64) {
         const int ql = e / k, o = e - ql * k;
         const int v = wout[o * 256 + ql];
-        dst[e] = (int64_t)((unsigned)v < (unsigned)n ? v : n - 1);  // (an empty slot only when distances are NaN)
+        dst[e] = (int64_t)((unsigned)v < (unsigned)n ? v : n - 1);  // (an empty slot: fewer than k distances that are not NaN)
     }
 }
 

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
         const int s = lane + 64 * h;
         if (s < k) {
             const unsigned j = (unsigned)list[h];
-            const bool real = j < (unsigned)n;  // (an empty slot only when distances are NaN)
+            const bool real = j < (unsigned)n;  // (an empty slot: fewer than k distances that are not NaN; +inf has a key and is listed)
             a.out[o + s] = (int64_t)(real ? (int)j : n - 1);
             if (a.dist) a.dist[o + s] = real ? wide_key_dist(list[h]) : __builtin_nanf("");
         }
