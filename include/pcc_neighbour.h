@@ -349,6 +349,50 @@ int pcc_devoxelize(int b, int c, int n, int res, float lo, float extent, const f
 int pcc_devoxelize_bwd(int b, int c, int n, int res, float lo, float extent, const float *xyz, const float *grad_out,
                        float *grad_grid, pcc_stream_t stream);
 
+/* Grid pooling (Point Transformer V2's partition-based pooling, KPConv's grid subsampling): the sparse form of pcc_voxelize,
+ * one output slot per OCCUPIED cell of the grid of pcc_voxel_index instead of a dense res^3 grid.  No counterpart in the
+ * reference; what a user writes in torch instead is a torch.unique over b * res^3 + cell (a global sort and a host
+ * synchronisation for the output size) and a scatter_reduce_ (float atomics).  The output is ragged -- every cloud has its
+ * own number U of occupied cells -- and is padded to a capacity m the caller chooses: a padded slot has an empty run.
+ *   layouts     cell[b, n], order[b, n] int32: those of pcc_voxel_index for the cloud; cluster[b, n], seg[b, m + 1], n_cells[b]
+ *               int32; x[b, c, n], grad_x[b, c, n], out[b, c, m], grad_out[b, c, m] float32 channels-major, arg[b, c, m] int32.
+ *               64-bit offsets throughout.
+ *   pcc_grid_cluster   U: the number of distinct cells >= 0 of the cloud, F: the number of its finite points (the first F
+ *               entries of order).  The occupied cells are ranked 0 .. U - 1 in ascending cell.  cluster[b, p]: the rank of
+ *               the cell of point p if that rank is < m; -1 for a dropped rank (>= m) and for cell = -1.  seg[b, r], r <
+ *               min(U, m): the first sorted position of rank r's run; every later entry up to seg[b, m]: the end of the last
+ *               kept run, F when U <= m and the first position of rank m otherwise.  So run r is order[seg[r] : seg[r + 1]],
+ *               in ascending point index, and a padded slot's run is empty.  n_cells[b] = U, the true count: U > m is how a
+ *               caller sees that cells were dropped.  The outputs at capacity m are those at capacity n restricted to their
+ *               first m (+ 1) entries, apart from the -1 of the dropped ranks.  Integers only: every word is fixed by the
+ *               cloud alone, not by b, the position in the batch or the run.  order is trusted to be pcc_voxel_index's (as in
+ *               pcc_voxelize: an entry outside [0, n) is skipped, never dereferenced).  n <= 16384 (pcc_voxel_index's limit:
+ *               one workgroup scans a cloud).
+ *   pcc_segment_pool   per slot r and channel over the run order[seg[r] : seg[r + 1]], in ascending position:
+ *               mode 0, mean  acc = +0.0f, then acc = acc + x[b, ch, order[pos]], then acc / (float)len, one IEEE division:
+ *                             word for word what pcc_voxelize writes into that cell;
+ *               mode 1, sum   the same without the division;
+ *               mode 2, max   torch.max over the run: the first NaN wins; otherwise the greatest value, the lowest point
+ *                             index among equal ones (-0 equals +0).  out is the word of x[b, ch, arg] (a NaN keeps its
+ *                             payload) and arg[b, ch, r] that point index; arg may be null, and is written in mode 2 only.
+ *               An empty run gives +0.0 and arg = -1.  A NaN from a mean or a sum is the word 0x7fc00000.  No float atomics:
+ *               every word of out and arg is written exactly once and is fixed by x, order and seg.  A run of more than 64
+ *               points is summed by one wave with a lane per channel, so a cell holding the whole cloud costs n wave steps.
+ *   pcc_segment_pool_bwd   a gather: with r = cluster[b, p], grad_x[b, ch, p] = grad_out[b, ch, r] / (float)(seg[r + 1] -
+ *               seg[r]) (mean, one division), grad_out[b, ch, r] (sum), grad_out[b, ch, r] where arg[b, ch, r] == p and +0.0
+ *               elsewhere (max); +0.0 for r = -1.  Every word is written and fixed.
+ * Requires c >= 1, n >= 1 (pcc_grid_cluster: n <= 16384), 1 <= m <= n, mode in {0, 1, 2}, b <= 65535, b * (n + 1) < 2^31 and
+ * non-null pointers (arg: in pcc_segment_pool_bwd with mode 2 only) -- PCC_EINVAL otherwise, under "grid_cluster:",
+ * "segment_pool:", "segment_pool_bwd:", before anything is enqueued.  b = 0 enqueues nothing and returns PCC_OK.  No c is
+ * refused (the kernels stride over the channel blocks beyond 65535 launch rows).  No workspace and no host synchronisation:
+ * the calls can be captured into a graph. */
+int pcc_grid_cluster(int b, int n, int m, const int32_t *cell, const int32_t *order, int32_t *cluster, int32_t *seg,
+                     int32_t *n_cells, pcc_stream_t stream);
+int pcc_segment_pool(int b, int c, int n, int m, int mode, const float *x, const int32_t *order, const int32_t *seg,
+                     float *out, int32_t *arg, pcc_stream_t stream);
+int pcc_segment_pool_bwd(int b, int c, int n, int m, int mode, const int32_t *cluster, const int32_t *seg,
+                         const int32_t *arg, const float *grad_out, float *grad_x, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

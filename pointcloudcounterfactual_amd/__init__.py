@@ -21,6 +21,8 @@ from pointcloudcounterfactual_amd.losses import (  # noqa: F401
     torch_sliced_wasserstein,
 )
 from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
+    GridIndex,
+    GridPooled,
     KernelPointConv,
     VoxelIndex,
     aggregate_points,
@@ -30,6 +32,10 @@ from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     estimate_normals,
     farthest_point_sample,
     feature_propagation,
+    grid_cluster,
+    grid_pool,
+    grid_subsample,
+    grid_unpool,
     group_points,
     interpolate_points,
     interpolation_weights,
@@ -42,6 +48,7 @@ from pointcloudcounterfactual_amd.neighbour_ops import (  # noqa: F401
     neighbour_softmax,
     point_voxel,
     sample_and_group,
+    segment_pool,
     vector_attention,
     voxel_index,
     voxelize,
@@ -55,4 +62,5 @@ __all__ = ['match_cost', 'nn_distance', 'chamfer', 'chamfer_emd', 'torch_chamfer
            'random_directions', 'sinkhorn_divergence', 'sinkhorn_schedule', 'torch_sinkhorn', 'VoxelIndex', 'voxel_index',
            'voxelize', 'devoxelize', 'point_voxel', 'neighbour_softmax', 'aggregate_points', 'attention_aggregate',
            'vector_attention', 'kernel_point_layout', 'kernel_point_influence', 'kpconv_aggregate', 'kernel_point_conv',
-           'KernelPointConv']
+           'KernelPointConv', 'GridIndex', 'GridPooled', 'grid_cluster', 'segment_pool', 'grid_pool', 'grid_subsample',
+           'grid_unpool']

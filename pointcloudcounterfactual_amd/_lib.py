@@ -77,6 +77,9 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_voxelize_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_devoxelize': (_int, [_int, _int, _int, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
     'pcc_devoxelize_bwd': (_int, [_int, _int, _int, _int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    'pcc_grid_cluster': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_segment_pool': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_segment_pool_bwd': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_graph_features': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
