@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from typing import Any, Iterator
+from typing import Any, Callable, Iterator
 
 # torch FIRST: libpcc_structural.so needs libamdhip64.so.7, and the process must end up with ONE HIP runtime.  With
 # torch imported before the library is loaded, the loader resolves that name to the runtime torch already brought in
@@ -176,3 +176,22 @@ def tuning(name: str, value: int) -> Iterator[None]:
         yield
     finally:
         set_tuning(name, 0)
+
+
+@contextlib.contextmanager
+def profile(mode: int = 1) -> Iterator[Callable[[str | bytes], tuple[float, int]]]:
+    """The library's launch profile for the body of a ``with``: cleared and enabled on entry (``mode`` 1: one event pair
+    around each launch), disabled and cleared behind it, whether or not the body raised.  Yields ``read(name)`` ->
+    (microseconds per launch, launches) over the profile names that begin with ``name``; synchronise before reading."""
+    def read(name: str | bytes) -> tuple[float, int]:
+        us, count = ctypes.c_double(), ctypes.c_int()
+        lib.pcc_profile_read(name.encode() if isinstance(name, str) else name, ctypes.byref(us), ctypes.byref(count))
+        return us.value, count.value
+
+    lib.pcc_profile_reset()
+    lib.pcc_profile_enable(mode)
+    try:
+        yield read
+    finally:
+        lib.pcc_profile_enable(0)
+        lib.pcc_profile_reset()

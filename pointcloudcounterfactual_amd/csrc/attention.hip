@@ -6,11 +6,11 @@
 // The [b,c,m,k] streams (rel in, grad_rel out) are the dominant traffic, so in every kernel that touches them consecutive
 // lanes take consecutive SLOTS of the list: whole cache lines per wave instruction.  What has to walk the k slots of a row
 // in order (the forward's sum, the softmax's sum and d) does so out of LDS, where a tile of rows lies at the odd row stride
-// k | 1: the lanes of a wave, each on its own row, hit distinct banks (the staging of local_geometry.hip).
+// k | 1: the lanes of a wave, each on its own row, hit distinct banks (pcc::padded_at, chan_block.hpp).
 //   * aggregation forward and grad_x: a workgroup owns CB channels of one sample (chan_block.hpp) with their rows of x or
 //     their gradient bins in LDS, or the direct path (global gathers, global float atomics) where they do not fit; a slot's
 //     index is loaded once for the CB channels, a weight word once per group among them;
-//   * grad_x sums the runs of equal consecutive indices inside a wave before one atomic per run (grouping.hip): the lanes
+//   * grad_x sums the runs of equal consecutive indices inside a wave before one atomic per run (pcc::wave_runs): the lanes
 //     of a wave are consecutive slots of a row here, and a ball_query(pad='first') row repeats one index;
 //   * grad_rel rides in the grad_x kernel (the same products) unless that launch is too narrow to stream it;
 //   * grad_w: a thread per (group, slot) walking the group's channels in ascending order, no atomics.
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kT) void agg_fwd_kernel(int c, int s, int n, int m,
                 const long long raw = ib[e];
                 const bool ok = in_range(raw, n);
                 const int t = ok ? (int)raw : 0;
-                const unsigned row = sl / uk, at = row * ks + (sl - row * uk);
+                const unsigned at = pcc::padded_at(sl, uk);
                 int gi = -1;
                 float wv = 0.f;
 #pragma unroll
@@ -125,16 +125,12 @@ __global__ __launch_bounds__(kT) void agg_bwd_kernel(int c, int s, int n, int m,
                                                      const float *__restrict__ go, float *__restrict__ grad_x,
                                                      float *__restrict__ grad_rel) {
     extern __shared__ __attribute__((aligned(16))) float bins[];  // [CB][n] (LDS path)
-    const int tid = threadIdx.x, nt = (int)blockDim.x, lane = tid & 63, lr = lane & 15;
+    const int tid = threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
     const unsigned um = (unsigned)m, uk = (unsigned)k, mk = um * uk;
     const int g = c / s;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
         const pcc::ListUnit w = pcc::list_unit<CB>(u, c, mk, nsplit, chunk);
-        if (!DIRECT) {
-            __syncthreads();  // (the previous unit's bins are written out)
-            for (int i = tid; i < w.cb * n; i += nt) bins[i] = 0.f;
-            __syncthreads();
-        }
+        if (!DIRECT) pcc::bins_clear(bins, w.cb * n, tid, nt);
         int grp[CB];
 #pragma unroll
         for (int cc = 0; cc < CB; cc++) grp[cc] = (w.c0 + min(cc, w.cb - 1)) / s;
@@ -166,16 +162,10 @@ __global__ __launch_bounds__(kT) void agg_bwd_kernel(int c, int s, int n, int m,
                 }
             }
             if (!gx) continue;  // (the same in every lane)
-            const int tp = __shfl_up(t, 1, 64);
-            const unsigned long long heads = __ballot(lane == 0 || tp != t);
-            const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
-            const pcc::SegMasks runs = {-(int)(lr >= 1 && lane - 1 >= head), -(int)(lr >= 2 && lane - 2 >= head),
-                                        -(int)(lr >= 4 && lane - 4 >= head), -(int)(lr >= 8 && lane - 8 >= head),
-                                        -(int)((lane & 16) != 0 && lane - lr - 1 >= head), -(int)(lane >= 32 && 31 >= head)};
-            const bool tail = t >= 0 && (lane == 63 || ((heads >> ((lane + 1) & 63)) & 1ull) != 0);
+            const pcc::WaveRuns runs = pcc::wave_runs(t, lane);
 #pragma unroll
-            for (int cc = 0; cc < CB; cc++) v[cc] = pcc::seg_prefix_sum(v[cc], runs);
-            if (tail) {
+            for (int cc = 0; cc < CB; cc++) v[cc] = pcc::seg_prefix_sum(v[cc], runs.masks);
+            if (runs.tail) {
 #pragma unroll
                 for (int cc = 0; cc < CB; cc++) {
                     if (cc < w.cb) {
@@ -188,10 +178,7 @@ __global__ __launch_bounds__(kT) void agg_bwd_kernel(int c, int s, int n, int m,
                 }
             }
         }
-        if (!DIRECT) {
-            __syncthreads();
-            for (int i = tid; i < w.cb * n; i += nt) gx[i] = bins[i];
-        }
+        if (!DIRECT) pcc::bins_store(gx, bins, w.cb * n, tid, nt);
     }
 }
 
@@ -230,7 +217,7 @@ __global__ __launch_bounds__(256) void agg_bwd_w_kernel(int c, int s, int n, int
 // ---- the softmax over the valid slots of a row ---------------------------------------------------------------------------
 
 // A tile: the rows r0 .. r0 + nr - 1 of the [b * g * m] rows of k slots, contiguous in memory.  Slot q of the tile is word
-// r0 * k + q of logits / attn, belongs to row r0 + q / k, and lies in LDS at (q / k) * (k | 1) + q % k.
+// r0 * k + q of logits / attn, belongs to row r0 + q / k, and lies in LDS at pcc::padded_at(q, k).
 struct SmTile {
     long long r0;
     unsigned nr, ns;
@@ -262,7 +249,7 @@ __global__ __launch_bounds__(kSmThreads) void softmax_fwd_kernel(int g, int n, i
         const size_t w0 = (size_t)t.r0 * uk;
         __syncthreads();  // (the previous tile is written out)
         for (unsigned q = tid; q < t.ns; q += kSmThreads) {
-            const unsigned row = q / uk, at = row * ks + (q - row * uk);
+            const unsigned row = q / uk, at = row * ks + (q - row * uk);  // (pcc::padded_at written out: 1 % slower through it)
             val[at] = logits[w0 + q];
             okf[at] = sm_valid(idx, t, q, row, g, n, m, uk);
         }
@@ -304,7 +291,7 @@ __global__ __launch_bounds__(kSmThreads) void softmax_bwd_kernel(int g, int n, i
         const size_t w0 = (size_t)t.r0 * uk;
         __syncthreads();
         for (unsigned q = tid; q < t.ns; q += kSmThreads) {
-            const unsigned row = q / uk, at = row * ks + (q - row * uk);
+            const unsigned row = q / uk, at = pcc::padded_at(q, uk, row);
             av[at] = attn[w0 + q];
             gv[at] = ga[w0 + q];
             okf[at] = sm_valid(idx, t, q, row, g, n, m, uk);
@@ -328,8 +315,7 @@ __global__ __launch_bounds__(kSmThreads) void softmax_bwd_kernel(int g, int n, i
         }
         __syncthreads();
         for (unsigned q = tid; q < t.ns; q += kSmThreads) {
-            const unsigned row = q / uk;
-            gl[w0 + q] = gv[row * ks + (q - row * uk)];
+            gl[w0 + q] = gv[pcc::padded_at(q, uk)];
         }
     }
 }
@@ -354,17 +340,9 @@ pcc::ListPlan make_plan(int b, int c, int n, unsigned len, bool split_lds, unsig
     return p;
 }
 
-// Threads of a workgroup: one per slot of a pass, or one per 8 words of the rows or bins if that is more; whole waves.
-unsigned threads_for(const pcc::ListPlan &p, unsigned long long slots) {
-    const unsigned long long by_tile = p.lds_bytes / 32, want = slots > by_tile ? slots : by_tile;
-    const unsigned t = (unsigned)((want > (unsigned)kT ? (unsigned)kT : want) + 63) / 64 * 64;
-    return t < 64 ? 64 : t;
-}
-
 void launch_bwd(const pcc::ListPlan &p, hipStream_t st, int c, int s, int n, int m, int k, const int64_t *idx, const float *w,
                 const float *grad_out, float *grad_x, float *grad_rel) {
-    const unsigned long long mk = (unsigned long long)m * k;
-    const dim3 block(threads_for(p, p.chunk < mk ? p.chunk : mk));
+    const dim3 block(p.threads((unsigned)m * (unsigned)k, 1));  // a lane per slot
     if (p.lds) {
         pcc::ProfScope prof("agg_bwd_kernel<lds>", st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
@@ -418,7 +396,7 @@ int pcc_aggregate_points(int b, int c, int g, int n, int m, int k, const float *
     const int s = c / g;
     const pcc::ListPlan p = make_plan(b, c, n, (unsigned)m, true, kMinChunkPts, kTileWords);
     const unsigned pts = p.chunk < (unsigned)m ? p.chunk : (unsigned)m, per_pass = (unsigned)(kTileSlots / k);
-    const dim3 block(threads_for(p, (unsigned long long)(pts < per_pass ? pts : per_pass) * k));
+    const dim3 block(p.threads_for((unsigned long long)(pts < per_pass ? pts : per_pass) * k));  // a lane per slot of a pass
     if (p.lds) {
         pcc::ProfScope prof("agg_fwd_kernel<lds>", st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
@@ -451,13 +429,7 @@ int pcc_aggregate_points_bwd(int b, int c, int g, int n, int m, int k, const flo
     const auto direct_plan = [&] { return pcc::make_list_plan(b, c, n, mk, true, kMinChunkSlots, 2); };
     if (grad_x) {
         pcc::ListPlan p = make_plan(b, c, n, mk, false, kMinChunkSlots, 0);
-        // LDS bins tie a channel block to one workgroup, and that workgroup's time is its ds_add_f32 count: while there are
-        // fewer workgroups than compute units, halve the block (the index list is read once more per halving)
-        while (p.lds && p.cb > 1 && p.units < pcc::device_cus_or(256)) {
-            p.cb /= 2;
-            p.lds_bytes /= 2;
-            p.units = (long long)b * pcc::ceil_div(c, p.cb);
-        }
+        p.spread_bins(b, c);
         if (!p.lds)
             if (int rc = pcc::zero_async(grad_x, gx_bytes, st, cannot_zero)) return rc;
         // grad_rel rides along unless the bins tie this launch to fewer workgroups than there are compute units

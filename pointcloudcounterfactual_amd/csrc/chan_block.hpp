@@ -1,7 +1,8 @@
-// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip, interpolate.hip, attention.hip): a
-// workgroup owns CB channels of one sample and keeps their rows of x, or their gradient bins, in LDS.  How the ids are
-// dealt, how much LDS a workgroup may take, how CB is chosen, how the kernel template is picked for it, and how the list of
-// a sample is split over several such workgroups.
+// Channel-block workgroups of the index-driven copies (graph_ops.hip, grouping.hip, interpolate.hip, attention.hip,
+// kpconv.hip): a workgroup owns CB channels of one sample and keeps their rows of x, or their gradient bins, in LDS.  How
+// the ids are dealt, how much LDS a workgroup may take, how CB is chosen, how the kernel template is picked for it, how the
+// list of a sample is split over several such workgroups and how many threads each gets, the protocol of the bins, and the
+// padded tile of list rows that attention.hip and kpconv.hip stage.
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -44,7 +45,7 @@ void dispatch_cb(int cb, F &&f) {
 }
 
 // ---- CB channels of a sample x a split of a per-sample list (grouping.hip: the m * k slots; interpolate.hip: the m dense
-// points; attention.hip: the dense points forward, the slots backward) ----
+// points; attention.hip: the dense points forward, the slots backward; kpconv.hip: the slots backward) ----
 constexpr int kWgThreads = 1024;         // threads of such a workgroup at the most
 constexpr int kCbDirect = 8;             // channels per workgroup of the direct path (nothing to fit)
 constexpr long long kMaxGrid = 1 << 20;  // workgroups per launch; the kernels stride over the units beyond
@@ -66,6 +67,24 @@ __device__ __forceinline__ ListUnit list_unit(long long u, int c, unsigned len, 
     return {smp, c0, min(CB, c - c0), lo, min(len, lo + chunk)};
 }
 
+// The gradient bins of a unit in LDS, `words` = cb * n of them, shared by the nt threads of the workgroup: zeroed once the
+// previous unit's bins are written out; added into (ds_add_f32); then written out whole once every add is done, so every
+// element of the unit's slice of the gradient is written and the host zero-fills nothing.
+__device__ __forceinline__ void bins_clear(float *bins, int words, int tid, int nt) {
+    __syncthreads();
+    for (int i = tid; i < words; i += nt) bins[i] = 0.f;
+    __syncthreads();
+}
+__device__ __forceinline__ void bins_store(float *dst, const float *bins, int words, int tid, int nt) {
+    __syncthreads();
+    for (int i = tid; i < words; i += nt) dst[i] = bins[i];
+}
+
+// Where slot q of a tile of rows of k slots lies in LDS: row q / k (`row`, where the caller has it for more) at the odd
+// stride k | 1, so that the lanes of a wave, each walking its own row, hit distinct banks.
+__device__ __forceinline__ unsigned padded_at(unsigned q, unsigned k, unsigned row) { return row * (k | 1u) + (q - row * k); }
+__device__ __forceinline__ unsigned padded_at(unsigned q, unsigned k) { return padded_at(q, k, q / k); }
+
 // How a call is cut into such workgroups: the path, CB, and into how many pieces the list of a sample is split.
 struct ListPlan {
     bool lds;
@@ -74,14 +93,27 @@ struct ListPlan {
     size_t lds_bytes;
     long long units;
     unsigned grid() const { return grid_for(units); }
-    // Threads per workgroup where they are not simply kWgThreads: one per `per` entries of a unit, or one per 8 words of
-    // its LDS tile (staged, or zeroed and written out) if that is more; whole waves.  A unit shorter than a full
-    // workgroup's reach (len = 512: 128 lanes with four entries each) would otherwise hold a CU's wave slots with waves
-    // that have nothing to do.
-    unsigned threads(unsigned len, unsigned per) const {
-        const unsigned ents = chunk < len ? chunk : len, by_entries = (ents + per - 1) / per, by_tile = (unsigned)(lds_bytes / 32);
-        const unsigned t = ((by_entries > by_tile ? by_entries : by_tile) + 63) / 64 * 64;
-        return t < 64 ? 64 : t > (unsigned)kWgThreads ? (unsigned)kWgThreads : t;
+    // Threads per workgroup where they are not simply kWgThreads: one per item of a pass over a unit, or one per 8 words
+    // of its LDS tile (staged, or zeroed and written out) if that is more; whole waves, 64 .. kWgThreads.  A unit shorter
+    // than a full workgroup's reach (len = 512: 128 lanes with four entries each) would otherwise hold a CU's wave slots
+    // with waves that have nothing to do.
+    unsigned threads_for(unsigned long long items) const {
+        const unsigned long long by_tile = lds_bytes / 32, want = items > by_tile ? items : by_tile;
+        const unsigned t = (unsigned)((want > (unsigned)kWgThreads ? (unsigned)kWgThreads : want) + 63) / 64 * 64;
+        return t < 64 ? 64 : t;
+    }
+    // ... where a lane takes `per` entries of a unit of a list of `len`
+    unsigned threads(unsigned len, unsigned per) const { return threads_for(((chunk < len ? chunk : len) + per - 1) / per); }
+    // LDS bins tie a channel block to one workgroup, and that workgroup walks the whole list of its sample, one LDS atomic
+    // per run and channel: while a backward has fewer workgroups than there are compute units, halve the block.  Each
+    // halving costs what a workgroup does once per entry whatever its CB: one more read of the index list (attention.hip),
+    // one more evaluation of the influences (kpconv.hip).
+    void spread_bins(int b, int c) {
+        while (lds && cb > 1 && units < device_cus_or(256)) {
+            cb /= 2;
+            lds_bytes /= 2;
+            units = (long long)b * ceil_div(c, cb);
+        }
     }
 };
 

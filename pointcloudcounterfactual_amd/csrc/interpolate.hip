@@ -143,11 +143,7 @@ __global__ __launch_bounds__(kT) void interp_bwd_x_kernel(int c, int n, int m, i
     const unsigned um = (unsigned)m;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
         const pcc::ListUnit w = pcc::list_unit<CB>(u, c, um, nsplit, chunk);
-        if (!DIRECT) {
-            __syncthreads();  // (the previous unit's bins are written out)
-            for (int i = tid; i < w.cb * n; i += nt) bins[i] = 0.f;
-            __syncthreads();
-        }
+        if (!DIRECT) pcc::bins_clear(bins, w.cb * n, tid, nt);
         const int64_t *ib = idx + (size_t)w.smp * um * k;
         const float *wb = wgt + (size_t)w.smp * um * k;
         const float *gb = g + ((size_t)w.smp * out_c + out_c0 + w.c0) * um;
@@ -174,10 +170,7 @@ __global__ __launch_bounds__(kT) void interp_bwd_x_kernel(int c, int n, int m, i
                 }
             }
         }
-        if (!DIRECT) {
-            __syncthreads();
-            for (int i = tid; i < w.cb * n; i += nt) gx[i] = bins[i];
-        }
+        if (!DIRECT) pcc::bins_store(gx, bins, w.cb * n, tid, nt);
     }
 }
 

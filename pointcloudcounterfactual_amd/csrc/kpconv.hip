@@ -5,16 +5,17 @@
 // The influences are a function of the coordinates alone, about 25 instructions with a square root per (slot, kernel
 // point), and with the usual extents most of them are exactly zero.
 //   * forward: a workgroup owns a tile of centres of one sample -- kTileSlots slots of the list at the odd row stride k | 1
-//     (the staging of attention.hip) -- and ALL channels, so an influence is computed once.  Pass 1, a lane per slot: the
+//     (pcc::padded_at, chan_block.hpp) -- and ALL channels, so an influence is computed once.  Pass 1, a lane per slot: the
 //     slot's influences on a block of kKpBlock kernel points go to LDS.  Pass 2, a lane per (kernel point, centre): the
 //     row's positive influences are packed to its front in slot order with their slot numbers.  Pass 3, a lane per (kernel
 //     point, kChanLane channels, centre): the sum over the packed pairs alone, the feature words gathered from x through L2 -- as
 //     many gathers as there are positive pairs.  The lanes of a wave are consecutive centres, so the stores are contiguous
 //     along m (whole cache lines for k <= 32).  An accumulator is one register of its lane: there is no array indexed by
 //     the kernel point, for any kp.
-//   * backward: agg_bwd_kernel's shape, a block of CB channels of a sample per workgroup (chan_block.hpp) with the bins of
-//     grad_x in LDS, or global atomics where they do not fit.  A lane per slot walks the kernel points in ascending order;
-//     the runs of equal consecutive targets are summed inside the wave, then one atomic per run.
+//   * backward: a block of CB channels of a sample per workgroup with the bins of grad_x in LDS (chan_block.hpp: the plan,
+//     bins_clear / bins_store), or global atomics where they do not fit.  A lane per slot walks the kernel points in
+//     ascending order; the runs of equal consecutive targets are summed inside the wave, then one atomic per run
+//     (pcc::scatter_runs, wave_ops.hpp).
 #include "chan_block.hpp"
 #include "pcc_common.hpp"
 #include "wave_ops.hpp"
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(kFwdThreads) void kp_fwd_kernel(int c, int n, int m
                 const long long raw = ib[sl];
                 const bool ok = in_range(raw, n);
                 const int t = ok ? (int)raw : 0;
-                const unsigned row = sl / uk, at = row * ks + (sl - row * uk);
+                const unsigned row = sl / uk, at = pcc::padded_at(sl, uk, row);
                 sidx[at] = t;
                 const float *pt = pb + (size_t)t * 3, *ct = qb + (size_t)row * 3;
                 const float rx = pt[0] - ct[0], ry = pt[1] - ct[1], rz = pt[2] - ct[2];
@@ -152,15 +153,11 @@ __global__ __launch_bounds__(kT) void kp_bwd_kernel(int c, int n, int m, int k, 
                                                     const float *__restrict__ kpts, const float *__restrict__ go,
                                                     float *__restrict__ grad_x) {
     extern __shared__ __attribute__((aligned(16))) float bins[];  // [CB][n] (LDS path)
-    const int tid = threadIdx.x, nt = (int)blockDim.x, lane = tid & 63, lr = lane & 15;
+    const int tid = threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
     const unsigned um = (unsigned)m, uk = (unsigned)k, mk = um * uk;
     for (long long u = pcc::xcd_contiguous((int)blockIdx.x, (int)gridDim.x); u < units; u += gridDim.x) {
         const pcc::ListUnit w = pcc::list_unit<CB>(u, c, mk, nsplit, chunk);
-        if (!DIRECT) {
-            __syncthreads();  // (the previous unit's bins are written out)
-            for (int i = tid; i < w.cb * n; i += nt) bins[i] = 0.f;
-            __syncthreads();
-        }
+        if (!DIRECT) pcc::bins_clear(bins, w.cb * n, tid, nt);
         const int64_t *ib = idx + (size_t)w.smp * mk;
         const float *pb = xyz + (size_t)w.smp * n * 3, *qb = centres + (size_t)w.smp * um * 3;
         const float *gb = go + ((size_t)w.smp * kp * c + w.c0) * um;  // kernel point t, channel c0 + cc: gb + (t * c + cc) * m
@@ -191,32 +188,15 @@ __global__ __launch_bounds__(kT) void kp_bwd_kernel(int c, int n, int m, int k, 
                     }
                 }
             }
-            const int tp = __shfl_up(t, 1, 64);
-            const unsigned long long heads = __ballot(lane == 0 || tp != t);
-            const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
-            const pcc::SegMasks runs = {-(int)(lr >= 1 && lane - 1 >= head), -(int)(lr >= 2 && lane - 2 >= head),
-                                        -(int)(lr >= 4 && lane - 4 >= head), -(int)(lr >= 8 && lane - 8 >= head),
-                                        -(int)((lane & 16) != 0 && lane - lr - 1 >= head), -(int)(lane >= 32 && 31 >= head)};
-            const bool tail = t >= 0 && (lane == 63 || ((heads >> ((lane + 1) & 63)) & 1ull) != 0);
-#pragma unroll
-            for (int cc = 0; cc < CB; cc++) v[cc] = pcc::seg_prefix_sum(v[cc], runs);
-            if (tail) {
-#pragma unroll
-                for (int cc = 0; cc < CB; cc++) {
-                    if (cc < w.cb) {
-                        if constexpr (DIRECT) {
-                            atomicAdd(gx + (size_t)cc * n + t, v[cc]);
-                        } else {
-                            atomicAdd(&bins[cc * n + t], v[cc]);
-                        }
-                    }
+            pcc::scatter_runs(v, w.cb, t, lane, [&](int cc, float sum) {
+                if constexpr (DIRECT) {
+                    atomicAdd(gx + (size_t)cc * n + t, sum);
+                } else {
+                    atomicAdd(&bins[cc * n + t], sum);
                 }
-            }
+            });
         }
-        if (!DIRECT) {
-            __syncthreads();
-            for (int i = tid; i < w.cb * n; i += nt) gx[i] = bins[i];
-        }
+        if (!DIRECT) pcc::bins_store(gx, bins, w.cb * n, tid, nt);
     }
 }
 
@@ -230,13 +210,6 @@ int check_sizes(const char *name, int b, int c, int n, int m, int k, int kp, flo
     if (k > kMaxK) return pcc::invalidf("%s: k > %d", name, kMaxK);
     if (!(sigma > 0.f) || !std::isfinite(sigma)) return pcc::invalidf("%s: sigma must be finite and > 0", name);
     return PCC_OK;
-}
-
-// Threads of a workgroup of the backward: one per slot of a pass, or one per 8 words of the bins if that is more; whole waves.
-unsigned threads_for(const pcc::ListPlan &p, unsigned long long items) {
-    const unsigned long long by_tile = p.lds_bytes / 32, want = items > by_tile ? items : by_tile;
-    const unsigned t = (unsigned)((want > (unsigned)kT ? (unsigned)kT : want) + 63) / 64 * 64;
-    return t < 64 ? 64 : t;
 }
 
 }  // namespace
@@ -273,16 +246,10 @@ int pcc_kpconv_aggregate_bwd(int b, int c, int n, int m, int k, int kp, const fl
     const float inv = 1.0f / sigma;
     const unsigned mk = (unsigned)m * (unsigned)k;
     pcc::ListPlan p = pcc::make_list_plan(b, c, n, mk, false, kMinChunkSlots, pcc::tuning(PCC_TUNE_INTERP_PATH));
-    // LDS bins tie a channel block to one workgroup, and that workgroup walks the whole list of its sample: while there are
-    // fewer workgroups than compute units, halve the block (the influences are computed once more per halving)
-    while (p.lds && p.cb > 1 && p.units < pcc::device_cus_or(256)) {
-        p.cb /= 2;
-        p.lds_bytes /= 2;
-        p.units = (long long)b * pcc::ceil_div(c, p.cb);
-    }
+    p.spread_bins(b, c);
     if (!p.lds)
         if (int rc = pcc::zero_async(grad_x, gx_bytes, st, cannot_zero)) return rc;
-    const dim3 block(threads_for(p, p.chunk < mk ? p.chunk : mk));
+    const dim3 block(p.threads(mk, 1));  // a lane per slot
     if (p.lds) {
         // (the profile's name says which channel block ran: the tests read it to know what they covered)
         static const char *const kNames[] = {"kp_bwd_kernel<lds> cb=1", "kp_bwd_kernel<lds> cb=2", "kp_bwd_kernel<lds> cb=4",

@@ -1,5 +1,5 @@
 // Cross-lane idioms of the kernels, gfx950 wave64: DPP moves under their names, reductions over a row of 16 lanes and
-// over the wave.  A DPP operand is a cross-lane VALU read: no trip through the LDS crossbar (ds_bpermute, what __shfl_*
+// over the wave, the segmented prefix sum and the run scatter of the backwards along an index list.  A DPP operand is a cross-lane VALU read: no trip through the LDS crossbar (ds_bpermute, what __shfl_*
 // compiles to).  A row is 16 consecutive lanes, a quad 4.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +95,41 @@ __device__ __forceinline__ float seg_prefix_sum(float v, const SegMasks &m) {
     v += keep_bits(dpp<kRowShr + 8>(v), m.shr8);
     v += keep_bits(dpp<kRowBcast15, 0xa>(v), m.bcast15);
     return v + keep_bits(dpp<kRowBcast31, 0xc>(v), m.bcast31);
+}
+
+// The runs of equal consecutive targets t among the 64 lanes of a wave (consecutive entries of an index list), as the
+// segments of seg_prefix_sum.  Bit l of `heads` = lane l opens a run, `head` is the lane that opens this lane's run; a
+// lane adds its partner at a step of the prefix sum iff the partner is not before the head of the lane's run.  `tail`:
+// the lane is the last of its run and the run's target is a point (t >= 0; the entries without one form runs of -1,
+// summed like any other but never added anywhere).  Every lane of the wave must be here (shuffle, ballot, and the DPP
+// moves that follow): the caller walks its list in whole waves under a wave-uniform bound.
+struct WaveRuns {
+    SegMasks masks;
+    bool tail;
+};
+__device__ __forceinline__ WaveRuns wave_runs(int t, int lane) {
+    const int lr = lane & 15;
+    const int tp = __shfl_up(t, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || tp != t);
+    const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+    return {{-(int)(lr >= 1 && lane - 1 >= head), -(int)(lr >= 2 && lane - 2 >= head), -(int)(lr >= 4 && lane - 4 >= head),
+             -(int)(lr >= 8 && lane - 8 >= head), -(int)((lane & 16) != 0 && lane - lr - 1 >= head),
+             -(int)(lane >= 32 && 31 >= head)},
+            t >= 0 && (lane == 63 || ((heads >> ((lane + 1) & 63)) & 1ull) != 0)};
+}
+// The scatter of a backward along such a list: v[cc], this lane's term for channel cc < cb, is summed over the lane's run
+// (channel by channel, the six steps of seg_prefix_sum: fixed bits), and the tail lane of every run calls add(cc, sum) for
+// the channels in ascending order -- one atomic per run and channel where 64 lanes on one address would serialise.
+template <int CB, class Add>
+__device__ __forceinline__ void scatter_runs(float (&v)[CB], int cb, int t, int lane, Add add) {
+    const WaveRuns runs = wave_runs(t, lane);
+#pragma unroll
+    for (int cc = 0; cc < CB; cc++) v[cc] = seg_prefix_sum(v[cc], runs.masks);
+    if (runs.tail) {
+#pragma unroll
+        for (int cc = 0; cc < CB; cc++)
+            if (cc < cb) add(cc, v[cc]);
+    }
 }
 
 // Maximum of a 64-bit key: over the 16 lanes of a row in every lane of the row (the tree of row_reduce16, both halves of

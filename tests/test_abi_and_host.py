@@ -329,6 +329,39 @@ def test_tuning_scope_sets_the_switch_and_always_sets_it_back(monkeypatch):
     assert calls == [('group_path', 2), ('group_path', 0)]
 
 
+def test_profile_scope_brackets_the_body_and_always_closes(monkeypatch):
+    """``_lib.profile(mode)`` is reset, enable(mode) on entry and enable(0), reset on exit, also when the body raises;
+    ``read`` takes ``str`` or ``bytes`` and returns (microseconds per launch, launches) as the library wrote them."""
+    from pointcloudcounterfactual_amd import _lib
+
+    calls = []
+
+    class Recorder:
+        def pcc_profile_reset(self):
+            calls.append('reset')
+
+        def pcc_profile_enable(self, mode):
+            calls.append(('enable', mode))
+
+        def pcc_profile_read(self, name, us, count):
+            calls.append(('read', name))
+            us._obj.value, count._obj.value = 12.5, 3
+            return 0
+
+    monkeypatch.setattr(_lib, 'lib', Recorder())
+    with _lib.profile(mode=2) as read:
+        assert calls == ['reset', ('enable', 2)]
+        got = [read('kp_bwd_kernel<direct>'), read(b'kp_bwd_kernel<lds> cb=4')]
+    assert got == [(12.5, 3), (12.5, 3)] and [type(v) for v in got[0]] == [float, int]
+    assert calls == ['reset', ('enable', 2), ('read', b'kp_bwd_kernel<direct>'), ('read', b'kp_bwd_kernel<lds> cb=4'),
+                     ('enable', 0), 'reset']
+    del calls[:]
+    with pytest.raises(ZeroDivisionError):
+        with _lib.profile():
+            1 / 0
+    assert calls == ['reset', ('enable', 1), ('enable', 0), 'reset']
+
+
 def test_sampling_and_grouping_dtype_and_device_errors_word_for_word():
     """The two raises ``farthest_point_sample``, ``ball_query``, ``group_points`` and ``sample_and_group`` share
     (``_float32``, ``_same_device``) carry the tensor's name in the words of ``_lib.ptr``; where two apply, the first in the

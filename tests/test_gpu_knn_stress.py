@@ -7,7 +7,6 @@ ascending by (distance, index), a +inf distance listed like any other, only NaN 
 Which kernel ran is read from the library's launch profile."""
 
 import contextlib
-import ctypes
 import functools
 
 import numpy as np
@@ -58,24 +57,16 @@ def _launches():
     """Counts of the launches inside the body, by kernel-name prefix: ``counts(name)`` after the body."""
     from pointcloudcounterfactual_amd import _lib
 
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
     got = {}
 
     def counts(name):
         return got[name]
 
-    try:
+    with _lib.profile() as read:
         yield counts
         torch.cuda.synchronize()
         for name in ('knn_mfma_kernel', 'knn_mfma_split_kernel', 'knn_wide_select_kernel', 'knn_sorted_kernel', 'knn_small_kernel'):
-            us, cnt = ctypes.c_double(), ctypes.c_int()
-            L.pcc_profile_read(name.encode(), ctypes.byref(us), ctypes.byref(cnt))
-            got[name] = cnt.value
-    finally:
-        L.pcc_profile_enable(0)
-        L.pcc_profile_reset()
+            got[name] = read(name)[1]
 
 
 def _knn(xd, k, switch):

@@ -67,8 +67,8 @@ def _bwd(xyz, centres, idx, kpts, sigma, go, c):
 
 
 def _expected_cb(b, c, n, cus):
-    """The channel block of the backward's LDS path by the rule of its plan (``make_list_plan`` of chan_block.hpp and the
-    halving in kpconv.hip): the largest of 8, 4, 2, 1 whose bins of n floats fit 64 KB (1 if none does), halved while there
+    """The channel block of the backward's LDS path by the rule of its plan (``make_list_plan`` and
+    ``ListPlan::spread_bins`` of chan_block.hpp): the largest of 8, 4, 2, 1 whose bins of n floats fit 64 KB (1 if none does), halved while there
     are fewer workgroups, ``b * ceil(c / cb)``, than compute units; None where one channel's bins exceed 160 KB (direct)."""
     cb = 8
     while cb > 1 and cb * n * 4 > 64 * 1024:
@@ -82,23 +82,13 @@ def _expected_cb(b, c, n, cus):
 
 def _bwd_variant(*args):
     """``_bwd(*args)`` and the variant that ran, from the library's launch profile: 'cb=1' ... 'cb=8' or 'direct'."""
-    import ctypes
-
     from pointcloudcounterfactual_amd import _lib
 
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    try:
+    with _lib.profile() as read:
         gx = _bwd(*args)
         ran = []
         for tag, name in [(f'cb={cb}', f'kp_bwd_kernel<lds> cb={cb}') for cb in (1, 2, 4, 8)] + [('direct', 'kp_bwd_kernel<direct>')]:
-            us, cnt = ctypes.c_double(), ctypes.c_int()
-            L.pcc_profile_read(name.encode(), ctypes.byref(us), ctypes.byref(cnt))
-            ran += [tag] * cnt.value
-    finally:
-        L.pcc_profile_enable(0)
-        L.pcc_profile_reset()
+            ran += [tag] * read(name)[1]
     assert len(ran) == 1, ran
     return gx, ran[0]
 

@@ -62,7 +62,8 @@ def parse(directory):
                 if t and not (t.startswith('.') and not t.endswith(':')):  # directives go, labels stay
                     body.append(t.replace(sym, '<kernel>'))
                 k += 1
-            while k < len(lines) and not lines[k].startswith('\t.section') and not lines[k].startswith('\t.text'):
+            # (the table follows a `.section .AMDGPU.csdata` line of its own; the next kernel begins with .text or its section)
+            while k < len(lines) and not lines[k].startswith('\t.text') and not (lines[k].startswith('\t.section') and 'csdata' not in lines[k]):
                 m = INFO.match(lines[k])
                 if m:
                     res[m.group(1)] = m.group(2).strip()

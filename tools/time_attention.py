@@ -14,7 +14,6 @@ stream.  `kernels` are the library's own per-launch averages (pcc_profile_enable
 and behind the grad_x / grad_rel kernel the rate at which it writes grad_rel, each as a share of the 8 TB/s HBM peak.
 Output: profiles/attention_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -56,23 +55,18 @@ def group_attention(x, idx, logits, rel=None):
 
 
 def kernel_times(run, stream_bytes):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name, label in KERNELS:
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {label} {us.value:.1f}'
-            if stream_bytes and label in ('fwd', 'grad_x(+rel)', 'grad_rel alone'):
-                rate = stream_bytes / (us.value * 1e-6)
-                text += f' ({rate / 1e12:.2f} TB/s of rel = {100 * rate / HBM_PEAK:.0f}% of peak)'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name, label in KERNELS:
+            us, cnt = read(name)
+            if cnt:
+                text += f' {label} {us:.1f}'
+                if stream_bytes and label in ('fwd', 'grad_x(+rel)', 'grad_rel alone'):
+                    rate = stream_bytes / (us * 1e-6)
+                    text += f' ({rate / 1e12:.2f} TB/s of rel = {100 * rate / HBM_PEAK:.0f}% of peak)'
     return text
 
 

@@ -16,7 +16,6 @@ def ev(fn, iters=10, warm=3):
     return s.elapsed_time(e) / iters * 1e3
 B, N = 32, 2048
 st = torch.cuda.current_stream().cuda_stream
-import ctypes
 for c, k in ((64, 25), (3, 25), (128, 25), (64, 20), (3, 4)):
     x = torch.randn(B, c, N, device=dev)
     idx = ops.hip_knn(x, k)
@@ -28,13 +27,11 @@ for c, k in ((64, 25), (3, 25), (128, 25), (64, 20), (3, 4)):
     gb = g2.numel() * 4 / 1e9
     print(f'c={c:3d} k={k:2d}: graph_features_bwd {t_f:7.1f} us ({gb / (t_f * 1e-6) / 1e3:.2f} TB/s of gradient read)  '
           f'gather_bwd {t_g:7.1f} us ({gb / 2 / (t_g * 1e-6) / 1e3:.2f} TB/s)')
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        L.pcc_graph_features_bwd(B, c, N, k, idx.data_ptr(), g2.data_ptr(), gx.data_ptr(), st)
-        L.pcc_gather_neighbours_bwd(B, c, N, k, idx.data_ptr(), g1.data_ptr(), gx.data_ptr(), st)
-    torch.cuda.synchronize()
-    for name in (b'edge_chunk_sort_kernel', b'edge_self_sum_kernel', b'edge_stream_bwd_kernel<features>', b'edge_stream_bwd_kernel<gather>'):
-        us = ctypes.c_double(); cnt = ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value: print(f'      {name.decode():36s} {us.value:7.1f} us x{cnt.value}')
-    L.pcc_profile_enable(0); L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            L.pcc_graph_features_bwd(B, c, N, k, idx.data_ptr(), g2.data_ptr(), gx.data_ptr(), st)
+            L.pcc_gather_neighbours_bwd(B, c, N, k, idx.data_ptr(), g1.data_ptr(), gx.data_ptr(), st)
+        torch.cuda.synchronize()
+        for name in ('edge_chunk_sort_kernel', 'edge_self_sum_kernel', 'edge_stream_bwd_kernel<features>', 'edge_stream_bwd_kernel<gather>'):
+            us, cnt = read(name)
+            if cnt: print(f'      {name:36s} {us:7.1f} us x{cnt}')

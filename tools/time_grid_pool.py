@@ -15,7 +15,6 @@ segment_pool('max') and segment_pool('mean'), with the achieved bytes per second
 m) * 4 bytes -- x read once, out written once, or the reverse -- over the kernel's time.
 Output: profiles/grid_pool_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -52,22 +51,17 @@ def packed(padded, count):
 
 
 def kernel_times(run, moved_bytes):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name in KERNELS:
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name.encode(), ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {name} {us.value:.1f}'
-            if name in MOVERS:
-                text += f' ({moved_bytes / (us.value * 1e-6) / 1e12:.2f} TB/s)'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name in KERNELS:
+            us, cnt = read(name)
+            if cnt:
+                text += f' {name} {us:.1f}'
+                if name in MOVERS:
+                    text += f' ({moved_bytes / (us * 1e-6) / 1e12:.2f} TB/s)'
     return text
 
 

@@ -14,7 +14,6 @@ B * (C * N + M * k * 12 + C * M) * 4-byte words (the list's indices are 8 bytes)
 launch) over 5 further forward + backward calls: the kernels without the calls' fixed cost, and the forward kernel's share
 of the peak.  Output: profiles/interpolate_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -43,22 +42,17 @@ def group_interp(x, idx, w):
 
 
 def kernel_times(run, fwd_bytes):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name, label in ((b'interp_fwd_kernel<lds>', 'fwd'), (b'interp_bwd_x_kernel<lds>', 'grad_x'), (b'interp_bwd_w_kernel', 'grad_w')):
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {label} {us.value:.1f}'
-            if label == 'fwd':
-                text += f' ({100 * fwd_bytes / (us.value * 1e-6) / HBM_PEAK:.0f}% of peak)'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name, label in (('interp_fwd_kernel<lds>', 'fwd'), ('interp_bwd_x_kernel<lds>', 'grad_x'), ('interp_bwd_w_kernel', 'grad_w')):
+            us, cnt = read(name)
+            if cnt:
+                text += f' {label} {us:.1f}'
+                if label == 'fwd':
+                    text += f' ({100 * fwd_bytes / (us * 1e-6) / HBM_PEAK:.0f}% of peak)'
     return text
 
 

@@ -17,7 +17,6 @@ bytes) as a share of the 8 TB/s HBM peak, and the backward kernel with its bins 
 `pairs` is the share of the (valid slot, kernel point) pairs with h > 0: the others are skipped.
 Output: profiles/kpconv_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -67,20 +66,15 @@ def ours_kpconv(x, xyz, centres, idx, kpts, sigma, weight=None):
 
 def profiled(run, names):
     """{name: microseconds per launch} of the library's kernels over 5 calls of ``run``."""
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     out = {}
-    for name in names:
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            out[name] = us.value
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name in names:
+            us, cnt = read(name)
+            if cnt:
+                out[name] = us
     return out
 
 

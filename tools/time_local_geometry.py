@@ -14,7 +14,6 @@ outputs = B * M * (8 k + 100) bytes, over its time, and its share of the 8 TB/s 
 per-launch averages (pcc_profile_enable(1): one event pair around each launch) over 5 further calls: the kernels without
 the calls' fixed cost, and the forward kernel's share of the peak.  Output: profiles/local_geometry_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 import time
@@ -43,23 +42,18 @@ def torch_geometry(xyz, idx):
 
 
 def kernel_times(run, fwd_bytes):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name, label in ((b'local_geometry_kernel', 'fwd'), (b'local_covariance_bwd_kernel<lds>', 'bwd lds'),
-                        (b'local_covariance_bwd_kernel<direct>', 'bwd direct')):
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {label} {us.value:.1f}'
-            if label == 'fwd':
-                text += f' ({100 * fwd_bytes / (us.value * 1e-6) / HBM_PEAK:.1f}% of peak)'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name, label in (('local_geometry_kernel', 'fwd'), ('local_covariance_bwd_kernel<lds>', 'bwd lds'),
+                            ('local_covariance_bwd_kernel<direct>', 'bwd direct')):
+            us, cnt = read(name)
+            if cnt:
+                text += f' {label} {us:.1f}'
+                if label == 'fwd':
+                    text += f' ({100 * fwd_bytes / (us * 1e-6) / HBM_PEAK:.1f}% of peak)'
     return text
 
 

@@ -15,7 +15,6 @@ debiased forward + backward calls.  The last row puts match_cost, sliced_wassers
 table for scale.
 Output: profiles/sinkhorn_times.txt (or --out)."""
 import argparse
-import ctypes
 import math
 import os
 import sys
@@ -56,21 +55,16 @@ def torch_sinkhorn_dense(x, y, eps, debias):
 
 
 def kernel_times(run):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name, label in ((b'sk_scan_kernel', 'round'), (b'sk_merge_kernel', 'merge'), (b'sk_scan_final_kernel', 'final round'),
-                        (b'sk_combine_kernel', 'combine'), (b'sk_cost_kernel', 'cost')):
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {label} {us.value:.1f}'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name, label in (('sk_scan_kernel', 'round'), ('sk_merge_kernel', 'merge'), ('sk_scan_final_kernel', 'final round'),
+                            ('sk_combine_kernel', 'combine'), ('sk_cost_kernel', 'cost')):
+            us, cnt = read(name)
+            if cnt:
+                text += f' {label} {us:.1f}'
     return text
 
 

@@ -11,7 +11,6 @@ are the library's own per-launch averages (pcc_profile_enable(1): one event pair
 forward + backward calls.  The last row puts match_cost and chamfer at (32, 2048) in the same table for scale.
 Output: profiles/sliced_wasserstein_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -35,20 +34,15 @@ def torch_sw(x, y, theta):
 
 
 def kernel_times(run):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name, label in ((b'sw_slice_kernel', 'slices'), (b'sw_finish_kernel', 'finish')):
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name, ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {label} {us.value:.1f}'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name, label in (('sw_slice_kernel', 'slices'), ('sw_finish_kernel', 'finish')):
+            us, cnt = read(name)
+            if cnt:
+                text += f' {label} {us:.1f}'
     return text
 
 

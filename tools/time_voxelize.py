@@ -14,7 +14,6 @@ averages (pcc_profile_enable(1)) over 5 further forward + backward calls of the 
 dense grid the achieved bytes per second of that write, B * C * R^3 * 4 bytes over the kernel's time.
 Output: profiles/voxelize_times.txt (or --out)."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -59,22 +58,17 @@ def torch_devoxelize(grid, xyz):
 
 
 def kernel_times(run, grid_bytes):
-    L = _lib.lib
-    L.pcc_profile_reset()
-    L.pcc_profile_enable(1)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize()
     text = ''
-    for name in KERNELS:
-        us, cnt = ctypes.c_double(), ctypes.c_int()
-        L.pcc_profile_read(name.encode(), ctypes.byref(us), ctypes.byref(cnt))
-        if cnt.value:
-            text += f' {name} {us.value:.1f}'
-            if name in GRID_WRITERS:
-                text += f' ({grid_bytes / (us.value * 1e-6) / 1e12:.2f} TB/s of grid written)'
-    L.pcc_profile_enable(0)
-    L.pcc_profile_reset()
+    with _lib.profile() as read:
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        for name in KERNELS:
+            us, cnt = read(name)
+            if cnt:
+                text += f' {name} {us:.1f}'
+                if name in GRID_WRITERS:
+                    text += f' ({grid_bytes / (us * 1e-6) / 1e12:.2f} TB/s of grid written)'
     return text
 
 
