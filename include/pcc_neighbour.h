@@ -393,6 +393,47 @@ int pcc_segment_pool(int b, int c, int n, int m, int mode, const float *x, const
 int pcc_segment_pool_bwd(int b, int c, int n, int m, int mode, const int32_t *cluster, const int32_t *seg,
                          const int32_t *arg, const float *grad_out, float *grad_x, pcc_stream_t stream);
 
+/* Submanifold sparse convolution (MinkUNet, SparseUNet, the conditional position encoding of Point Transformer V3) on the
+ * slots of pcc_grid_cluster: every occupied cell sums, over the ksize^3 offsets of a kernel, a weight matrix applied to the
+ * features of the occupied cell at that offset; the set of occupied cells does not grow.  No counterpart in the reference;
+ * what a user writes in torch instead is a dense [b, c, res, res, res] grid under torch.nn.Conv3d, or a ksize^3-wide list, a
+ * pcc_group_points along it (ksize^3 times the features) and one matmul.
+ *   layouts     cell[b, n], order[b, n], seg[b, m + 1], n_cells[b] int32: those of pcc_voxel_index and pcc_grid_cluster for the
+ *               same clouds, the same res and the same capacity m; nbr[b, m, t] int64, -1 where there is no neighbour, like
+ *               every other list here (pcc_group_points, pcc_aggregate_points and pcc_local_geometry take it unchanged);
+ *               x[b, c, n], out[b, o, m] float32 channels-major; weight[t, c, o], bias[o] float32.  64-bit offsets throughout.
+ *   pcc_cell_neighbours   the kernel map.  Slot r < min(U, m) has the flat cell cell[order[seg[r]]] = (i * res + j) * res + k.
+ *               With h = (ksize - 1) / 2 and offsets di, dj, dk in [-h, h], tap t = ((di + h) * ksize + (dj + h)) * ksize + (dk +
+ *               h).  nbr[b, r, t]: the rank of the cell (i + dilation * di, j + dilation * dj, k + dilation * dk) if that cell
+ *               lies inside [0, res)^3 (the triple is decomposed BEFORE the offset is added: nothing wraps around), is occupied
+ *               and has a rank < m; -1 otherwise, and in every tap of a padded slot (r >= min(U, m)).  So the centre tap of a
+ *               real slot is r itself, and the map is symmetric: nbr[r, t] = s >= 0 exactly when nbr[s, ksize^3 - 1 - t] = r.  The
+ *               map at capacity m is the map at capacity n cut to its first m rows, with the ranks >= m turned into -1.
+ *               Integers only: every word is written once and fixed by the cloud alone, not by b, the position in the batch or
+ *               the run.  The four index arrays are trusted to be the library's (an entry outside its range is skipped, never
+ *               dereferenced).  ksize is 3 or 5, dilation >= 1, 2 <= res <= 128, 1 <= m <= n <= 16384, b * m * ksize^3 < 2^31.
+ *   pcc_sparse_conv   out[b, oc, r] = bias[oc] + sum over t and ch of weight[t, ch, oc] * x[b, ch, nbr[b, r, t]], over the taps
+ *               with 0 <= nbr < n (n: the points of x; with a map of pcc_cell_neighbours n = m).  A row with no such tap is +0.0,
+ *               without the bias: with a map of pcc_cell_neighbours that row is exactly a padded slot.  Every word of out is
+ *               written exactly once; no float atomics; the [b, c, m, t] tensor of gathered features is never written.  The
+ *               contract is a bound, not fixed words: the result of a row depends on that row's list, on x and on weight
+ *               only -- so it is float-equal from run to run, at any batch position and for any b (the sign of a zero result
+ *               is not fixed) --, and against exact arithmetic, with D = (valid taps) * c + 1 and S = |bias| + sum of |w| * |x|
+ *               over the valid terms, |out - exact| <= D * 2^-24 / (1 - D * 2^-24) * S + D * 2^-126.  Non-finite features
+ *               propagate as IEEE.  A tap that is empty in one row and not in a neighbouring row may be computed with a +0.0
+ *               feature, so "an empty tap takes no part" holds for FINITE weights only: an infinite or NaN weight can turn rows
+ *               with an empty tap into NaN.  bias may be null.  t is any length >= 1 (ksize^3 for a map).
+ *               FORWARD ONLY for a general list: the gradient in x is the same entry point on the mirrored weights
+ *               (weight'[t, oc, ch] = weight[t' - 1 - t, ch, oc], no bias) only because the map of pcc_cell_neighbours is
+ *               symmetric, and the Python autograd node accepts such maps only.
+ * Requires c, o, n, m, t >= 1, b <= 65535, m * t < 2^31, t * c * o < 2^31 and non-null pointers but for bias -- PCC_EINVAL
+ * otherwise, under "cell_neighbours:", "sparse_conv:", before anything is enqueued.  b = 0 enqueues nothing and returns
+ * PCC_OK.  No workspace and no host synchronisation: the calls can be captured into a graph. */
+int pcc_cell_neighbours(int b, int n, int m, int res, int ksize, int dilation, const int32_t *cell, const int32_t *order,
+                        const int32_t *seg, const int32_t *n_cells, int64_t *nbr, pcc_stream_t stream);
+int pcc_sparse_conv(int b, int c, int o, int n, int m, int t, const float *x, const int64_t *nbr, const float *weight,
+                    const float *bias, float *out, pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);
