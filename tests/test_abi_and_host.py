@@ -241,6 +241,56 @@ def test_every_reference_import_from_neighbour_ops_resolves_here():
     assert idx.shape == (2, 5, 3) and (idx[:, :, 0] == range(5)).all()
 
 
+def test_neighbour_ops_package_keeps_the_public_surface():
+    """``pointcloudcounterfactual_amd.neighbour_ops`` is a package of one module per op family, and the one name every
+    caller imports from: each public name the single module had is an attribute of the package and of the same kind, and
+    what the top-level package imports from it is the very object the package holds."""
+    import ast
+
+    import pointcloudcounterfactual_amd as pkg
+    from pointcloudcounterfactual_amd import neighbour_ops as ours
+    from torch.autograd import Function
+
+    functions = {
+        'aggregate_points', 'attention_aggregate', 'ball_query', 'cell_neighbours', 'cross_square_distance', 'devoxelize',
+        'estimate_normals', 'farthest_point_sample', 'feature_propagation', 'get_graph_features', 'get_local_covariance',
+        'get_neighbours', 'global_max_mean_pool', 'global_max_pool', 'graph_filtering', 'graph_max_pooling', 'grid_cluster',
+        'grid_pool', 'grid_subsample', 'grid_unpool', 'group_points', 'hip_ball_query', 'hip_farthest_point_sample', 'hip_knn',
+        'hip_knn_cross', 'hip_kpconv_aggregate', 'index_k_neighbours', 'interpolate_points', 'interpolation_weights',
+        'kernel_point_conv', 'kernel_point_influence', 'kernel_point_layout', 'knn', 'knn_cross', 'kpconv_aggregate',
+        'local_covariance', 'local_geometry', 'neighbour_softmax', 'point_voxel', 'pykeops_knn', 'pykeops_square_distance',
+        'sample_and_group', 'segment_pool', 'self_square_distance', 'sparse_conv', 'square_distance', 'torch_aggregate_points',
+        'torch_aggregate_points_bwd', 'torch_ball_query', 'torch_cell_neighbours', 'torch_devoxelize',
+        'torch_farthest_point_sample', 'torch_grid_cluster', 'torch_group_points', 'torch_interpolate_points', 'torch_knn',
+        'torch_knn_cross', 'torch_kpconv_aggregate', 'torch_kpconv_aggregate_bwd', 'torch_local_covariance',
+        'torch_neighbour_softmax', 'torch_neighbour_softmax_bwd', 'torch_scatter_eigen', 'torch_segment_pool',
+        'torch_segment_pool_bwd', 'torch_sparse_conv', 'torch_square_distance', 'torch_voxel_index', 'torch_voxelize',
+        'vector_attention', 'voxel_index', 'voxelize'}
+    autograd = {'AggregatedPoints', 'Devoxelized', 'Grouped', 'Indexed', 'Interpolated', 'KernelPointAggregated', 'LocalCovariance',
+                'NeighbourSoftmax', 'SegmentPooled', 'SparseConvolved', 'Voxelized'}
+    tuples = {'FeaturePropagation', 'GridIndex', 'GridPooled', 'IndexedOp', 'LocalGeometry', 'SampleAndGroup', 'SparseConvMap',
+              'VoxelIndex'}
+    layers = {'KernelPointConv', 'SubmanifoldConv3d'}
+    constants = {'BALL_PAD': dict, 'F32': torch.dtype, 'I32': torch.dtype, 'I64': torch.dtype, 'KERNEL_SIZES': tuple,
+                 'MAX_KERNEL_POINTS': int, 'MAX_LIST_K': int, 'MAX_VOXEL_POINTS': int, 'GATHER': ours.IndexedOp,
+                 'GRAPH_FEATURES': ours.IndexedOp, 'GRAPH_MAX_POOL': ours.IndexedOp}
+    missing = [n for n in functions | autograd | tuples | layers | set(constants) if not hasattr(ours, n)]
+    assert missing == []
+    assert [n for n in functions if type(getattr(ours, n)).__name__ != 'function'] == []
+    assert [n for n in autograd if not issubclass(getattr(ours, n), Function)] == []
+    assert [n for n in tuples if not (issubclass(getattr(ours, n), tuple) and hasattr(getattr(ours, n), '_fields'))] == []
+    assert [n for n in layers if not issubclass(getattr(ours, n), torch.nn.Module)] == []
+    assert [n for n, kind in constants.items() if type(getattr(ours, n)) is not kind] == []
+    for n in autograd:  # the autograd node names seen in traces
+        assert getattr(ours, n).__name__ == n
+    # the top-level package re-exports the package's own objects
+    tree = ast.parse(open(pkg.__file__).read())
+    taken = [a.asname or a.name for node in tree.body if isinstance(node, ast.ImportFrom)
+             and node.module == 'pointcloudcounterfactual_amd.neighbour_ops' for a in node.names]
+    assert {'VoxelIndex', 'voxelize', 'sparse_conv', 'grid_pool'} <= set(taken), taken
+    assert [n for n in taken if getattr(pkg, n) is not getattr(ours, n)] == []
+
+
 def test_bench_starts_its_own_ranks(monkeypatch):
     """`bench.py --gpus N` without a launcher environment must start N ranks itself (reference: src/utils/parallel.py:37-53
     spawns its ranks): the parent builds a `torch.distributed.run` child command for N processes on 127.0.0.1 and relays
