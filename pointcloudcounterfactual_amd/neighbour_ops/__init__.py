@@ -38,6 +38,9 @@ from pointcloudcounterfactual_amd.neighbour_ops.pooling import (  # noqa: F401
 from pointcloudcounterfactual_amd.neighbour_ops.sparse import (  # noqa: F401
     KERNEL_SIZES, SparseConvMap, SparseConvolved, SubmanifoldConv3d, cell_neighbours, sparse_conv, torch_cell_neighbours,
     torch_sparse_conv)
+from pointcloudcounterfactual_amd.neighbour_ops.strided import (  # noqa: F401
+    MAX_WGRAD_ROWS, STRIDE_TAPS, SparseConv3d, SparseConvTranspose3d, StrideMap, coarsen_level, sparse_conv_transpose,
+    sparse_conv_wgrad, stride_map, strided_sparse_conv, torch_coarsen_cells, torch_sparse_conv_wgrad, torch_stride_map)
 from pointcloudcounterfactual_amd.neighbour_ops.geometry import (  # noqa: F401
     LocalCovariance, LocalGeometry, estimate_normals, local_covariance, local_geometry, torch_local_covariance, torch_scatter_eigen)
 from pointcloudcounterfactual_amd.neighbour_ops.graph import (  # noqa: F401
