@@ -11,6 +11,9 @@
  *   xyz1[b,n,3], xyz2[b,n,3] float32 in [0,1]^3 ; dist[b,n] float32 ; assignment[b,n] int32.
  * Deterministic where the reference races (GetMax / Assign, emd_cuda.cu:189,205): bidders of an iteration =
  * points unassigned when it starts; lowest bidder index wins a tie within the 1e-6 window.
+ *
+ * Alignment: as everywhere in the library (pcc_structural.h), every tensor argument may be any contiguous buffer aligned
+ * to its element size (4 bytes); no wider access is taken on a caller's pointer here.
  */
 #ifndef PCC_EMD_H
 #define PCC_EMD_H

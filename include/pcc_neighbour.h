@@ -8,6 +8,11 @@
  *   x[b, c, n] float32 (channels-major), indices[b, n, k] int64.
  * All entries enqueue on `stream` (hipStream_t as void*), never synchronise, and return 0 or an error code
  * (message via pcc_last_error(), include/pcc_structural.h).
+ *
+ * Alignment: every tensor argument, input or output, may be any contiguous buffer aligned to its element size -- 4 bytes,
+ * 8 for an int64 list (a chunk of a batch, a parameter inside a flat buffer, a slice of a gradient).  The kernels take
+ * wider accesses only where the sizes and the address allow it and fall back to element accesses otherwise
+ * (tests/test_gpu_unaligned_views.py runs every entry point on such buffers).
  */
 #ifndef PCC_NEIGHBOUR_H
 #define PCC_NEIGHBOUR_H
@@ -507,7 +512,7 @@ int pcc_pair_sqdist_sum_bwd(int b, int np, int nq, int d, const float *p, const 
  * variance (only a finite negative rounding residue is clamped to 0); relu(NaN) = NaN; the backward zeroes the gradient
  * where the pre-activation is <= 0 only, so a NaN pre-activation passes it (threshold_backward).
  * The 16-byte accesses are used only when n % 4 == 0 and z, y, res / z, grad_y, grad_z are 16-byte aligned; any
- * 4-byte-aligned contiguous tensor is accepted. */
+ * 4-byte-aligned contiguous tensor is accepted, and for n % 4 == 0 the backward's sums run in the same order either way. */
 int pcc_bn_stats(int b, int c, int n, const float *z, float *mean, float *var, pcc_stream_t stream);
 int pcc_bn_relu_res_fwd(int b, int c, int n, const float *z, const float *mean, const float *var, float eps,
                         const float *gamma, const float *beta, const float *res, int res_c, int r, float *y,

@@ -15,6 +15,11 @@
  * (0 = success, otherwise the hipError_t of the failed launch / a PCC_E* code) and records a message
  * retrievable with pcc_last_error(); the reference-named void launchers record the same message and
  * the host-side binding raises RuntimeError("HIP kernel failed : <code>") from it.
+ *
+ * Alignment: every tensor argument, input or output, may be any contiguous buffer aligned to its element size (4 bytes
+ * here: float32 and int32).  The kernels take wider accesses only where the sizes and the address allow it and fall
+ * back to element accesses otherwise (tests/test_gpu_unaligned_views.py runs every entry point on such buffers).  The one
+ * exception is the caller-provided workspace of pcc_approxmatch_ws, which must be 16-byte aligned (PCC_EINVAL otherwise).
  */
 #ifndef PCC_STRUCTURAL_H
 #define PCC_STRUCTURAL_H

@@ -140,11 +140,20 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_partial_kernel(int b, int c, 
     for (int smp = s0; smp < s1; smp++) {
         const float *zr = z + ((size_t)smp * c + ch) * n;
         const float *gr = gy + ((size_t)smp * c + ch) * n;
-        if (vec) {
+        if (n % 4 == 0) {
+            // groups of four whatever the bases: a misaligned z or grad_y changes the loads, not the order of the sums, so
+            // grad_gamma and grad_beta are the same words as for an aligned copy
             for (int i = tid; i < n / 4; i += 256) {
-                const float4 v = reinterpret_cast<const float4 *>(zr)[i];
-                const float4 g4 = reinterpret_cast<const float4 *>(gr)[i];
-                const float vv[4] = {v.x, v.y, v.z, v.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
+                float vv[4], gg[4];
+                if (vec) {
+                    const float4 v = reinterpret_cast<const float4 *>(zr)[i];
+                    const float4 g4 = reinterpret_cast<const float4 *>(gr)[i];
+                    vv[0] = v.x, vv[1] = v.y, vv[2] = v.z, vv[3] = v.w;
+                    gg[0] = g4.x, gg[1] = g4.y, gg[2] = g4.z, gg[3] = g4.w;
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) vv[q] = zr[4 * i + q], gg[q] = gr[4 * i + q];
+                }
                 float ps = 0.f, px = 0.f;  // four terms in float, the running sums in double
 #pragma unroll
                 for (int q = 0; q < 4; q++) {

@@ -148,7 +148,8 @@ void dispatch_ob(int o, F &&f) {
 // [ch = l >> 4] and B = X[ch = l >> 4][slot = l & 15] and holds D[oc = 4 * (l >> 4) + reg][slot = l & 15] in four registers.
 // A wave owns kMfmaNt tiles of 16 consecutive slots and NOT tiles of 16 output channels; row i of channel tile ot is the
 // output channel o0 + NOT * i + ot, so that the NOT weights a lane needs for one channel are consecutive words: one load of
-// NOT floats (VEC: o is a multiple of NOT, so the load is aligned and lies inside the row or outside it as a whole).  Per four
+// NOT floats (VEC: o is a multiple of NOT and weight itself starts on a 4 * NOT-byte boundary, which launch_mfma checks, so
+// the load is aligned and lies inside the row or outside it as a whole; any other weight takes the scalar loads).  Per four
 // channels a lane loads NOT weights and one gathered word of x per slot tile for NOT * kMfmaNt MFMAs: the operands a
 // VALU tile re-reads per output channel are loaded once per 16.  A tap that is empty for a whole tile of 16 slots is skipped
 // for that tile: a quarter of the VALU kernel's wave, so more taps are skipped and fewer lanes are zero-filled.
@@ -278,10 +279,16 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void sparse_conv_mfma_kernel(int c
 template <int NOT>
 void launch_mfma(int b, int c, int o, int n, int m, int t, const float *x, const int64_t *nbr, const float *weight, const float *bias,
                  float *out, hipStream_t st) {
-    static const char *const names[] = {"", "sparse_conv_mfma_kernel<16>", "sparse_conv_mfma_kernel<32>", "", "sparse_conv_mfma_kernel<64>"};
-    pcc::ProfScope prof(names[NOT], st);
+    // (the profile tells the variants apart behind one prefix per tile: the tests read either)
+    static const char *const names[][5] = {
+        {"", "sparse_conv_mfma_kernel<16>", "sparse_conv_mfma_kernel<32>", "", "sparse_conv_mfma_kernel<64>"},
+        {"", "sparse_conv_mfma_kernel<16> scalar weights", "sparse_conv_mfma_kernel<32> scalar weights", "",
+         "sparse_conv_mfma_kernel<64> scalar weights"}};
+    // (weight is the caller's pointer: any 4-byte-aligned address is legal, the wide load is taken only on a 4 * NOT-byte one)
+    const bool vec = o % NOT == 0 && (reinterpret_cast<uintptr_t>(weight) & (4 * NOT - 1)) == 0;
+    pcc::ProfScope prof(names[vec ? 0 : 1][NOT], st);
     const dim3 grid((unsigned)pcc::ceil_div(m, kMfmaRows), (unsigned)std::min(pcc::ceil_div(o, 16 * NOT), kMaxGridY), (unsigned)b);
-    if (o % NOT == 0)
+    if (vec)
         hipLaunchKernelGGL((sparse_conv_mfma_kernel<NOT, true>), grid, dim3(64 * kMfmaWaves), 0, st, c, o, n, m, t, x, nbr, weight, bias, out);
     else
         hipLaunchKernelGGL((sparse_conv_mfma_kernel<NOT, false>), grid, dim3(64 * kMfmaWaves), 0, st, c, o, n, m, t, x, nbr, weight, bias, out);

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from tests import bn_pair_reference as R
+from tests.unaligned_views import shifted
 
 pytestmark = pytest.mark.gpu
 
@@ -147,11 +148,7 @@ def test_bn_forward_at_every_branch(cuda, name, b, c, n, residual, mode):
 
 def _offset_view(t):
     """A contiguous copy of t that starts one float past a 16-byte boundary."""
-    flat = torch.empty(t.numel() + 1, device=t.device)
-    view = flat[1:].view(t.shape)
-    view.copy_(t)
-    assert view.is_contiguous() and view.data_ptr() % 16 == 4
-    return view
+    return shifted(t)
 
 
 @pytest.mark.parametrize('which', ['z', 'res', 'gy', 'y', 'grad_z'])

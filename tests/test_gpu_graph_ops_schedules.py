@@ -22,6 +22,8 @@ import ctypes
 import pytest
 import torch
 
+from tests.unaligned_views import shifted
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24  # unit roundoff of float32
@@ -273,9 +275,7 @@ def test_misaligned_index_view_takes_the_scalar_path(cuda):
     the per-edge scalar path; n * k % 4 == 0 here, so without the offset they would take the 16-byte path."""
     b, c, n, k = 2, 9, 2048, 25
     x, idx, ws = _inputs(b, c, n, k, 'exact', seed=5)
-    flat = torch.empty(b * n * k + 1, dtype=torch.int64, device=cuda)
-    view = flat[1:].view(b, n, k)
-    view.copy_(idx)
+    view = shifted(idx.to(cuda))
     assert view.is_contiguous() and view.data_ptr() % 16 == 8
     res = _run_ops(x, view, ws, cuda)
     _check_all('misaligned', res, _reference(x, _effective(idx, n), ws), True)
@@ -411,9 +411,7 @@ def test_global_max_pool_non_finite(cuda, n, layout):
     if layout == 'aligned':
         xd = x.to(cuda)
     else:
-        flat = torch.empty(b * c * n + 1, device=cuda)
-        xd = flat[1:].view(b, c, n)
-        xd.copy_(x)
+        xd = shifted(x.to(cuda))
         assert xd.is_contiguous() and xd.data_ptr() % 16 == 4
     ref, ref_arg = torch.max(x, dim=2)
 

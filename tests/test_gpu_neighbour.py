@@ -107,13 +107,7 @@ def test_inputs_that_are_views_with_a_storage_offset(cuda):
     notice and every result must equal the one for an aligned copy."""
     from pointcloudcounterfactual_amd import backend
     from pointcloudcounterfactual_amd import neighbour_ops as ops
-
-    def shifted(t):
-        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-        v = buf[1:].view(t.shape)
-        v.copy_(t)
-        assert v.is_contiguous() and v.data_ptr() % 16 != 0
-        return v
+    from tests.unaligned_views import shifted
 
     g = torch.Generator().manual_seed(5)
     x3 = torch.rand(3, 3, 1000, generator=g).to(cuda)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import structural_grad_reference as R
+from tests.unaligned_views import shifted
 
 pytestmark = pytest.mark.gpu
 
@@ -183,10 +184,7 @@ class Match:
         self.b, self.n, self.m = p1.shape[0], p1.shape[1], p2.shape[1]
         self.p1, self.p2 = _dev(p1, cuda), _dev(p2, cuda)
         if misaligned:  # a contiguous view 4 bytes past a 16-byte boundary: only the scalar kernels may run
-            buf = torch.zeros(match.size + 8, dtype=F32, device=cuda)
-            off = 1 + (-(buf.data_ptr() // 4) % 4)
-            self.match = buf[off:off + match.size].view(match.shape)
-            self.match.copy_(_dev(match, cuda))
+            self.match = shifted(_dev(match, cuda))
             assert self.match.data_ptr() % 16 == 4 and self.match.is_contiguous()
         else:
             self.match = _dev(match, cuda)

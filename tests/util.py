@@ -59,6 +59,33 @@ def c_status(lib, fn, *args) -> tuple[int, str]:
     return rc, lib.pcc_last_error().decode()
 
 
+MATCH_COST_RTOL = 1e-5  # the approximate EMD's cost against the float64 recurrence (tests/test_gpu_structural.py, smoke())
+
+
+def check_match_cost(oracle, a: np.ndarray, b: np.ndarray, cost: np.ndarray, grad1: np.ndarray | None = None,
+                     grad2: np.ndarray | None = None) -> None:
+    """``match_cost`` of the clouds ``a``, ``b`` inside the bars of tests/test_gpu_structural.py and ``smoke()``: the cost
+    MATCH_COST_RTOL relative to the float64 recurrence; the gradients within 3x the spread of the oracle's own legitimate
+    float32 evaluations (exp modes 0-3) around the float64 gradients, floor 5e-5 of the largest component."""
+    om64, _ = oracle.approxmatch_f64(a, b)
+    np.testing.assert_allclose(cost, oracle.matchcost_f64(a, b, om64), rtol=MATCH_COST_RTOL)
+    if grad1 is None:
+        return
+    h1, h2 = oracle.matchcostgrad_f64(a, b, om64)
+    scale = max(np.abs(h1).max(), np.abs(h2).max())
+    spread = 0.0
+    try:
+        for mode in (0, 1, 2, 3):
+            oracle.set_exp_mode(mode)
+            om, _ = oracle.approxmatch(a, b)
+            f1, f2 = oracle.matchcostgrad(a, b, om)
+            spread = max(spread, np.abs(f1 - h1).max(), np.abs(f2 - h2).max())
+    finally:
+        oracle.set_exp_mode(0)
+    bar = max(3 * spread, 5e-5 * scale)
+    assert np.abs(grad1 - h1).max() <= bar and np.abs(grad2 - h2).max() <= bar, (np.abs(grad1 - h1).max(), np.abs(grad2 - h2).max(), bar)
+
+
 class host_independent_math:
     """Context manager: ``torch.sqrt`` / ``torch.exp`` of float32 tensors rounded from float64 while it is active.  Torch
     hands float32 sqrt / exp on the CPU to a vector-math library whose code path, and last bit, depends on the CPU
