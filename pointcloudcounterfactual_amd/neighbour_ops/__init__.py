@@ -20,7 +20,7 @@ from pointcloudcounterfactual_amd.neighbour_ops.sampling import (  # noqa: F401
     BALL_PAD, ball_query, farthest_point_sample, hip_ball_query, hip_farthest_point_sample, torch_ball_query,
     torch_farthest_point_sample)
 from pointcloudcounterfactual_amd.neighbour_ops.grouping import (  # noqa: F401
-    Grouped, SampleAndGroup, group_points, sample_and_group, torch_group_points)
+    Grouped, QueryGrouped, SampleAndGroup, group_points, query_and_group, sample_and_group, torch_group_points)
 from pointcloudcounterfactual_amd.neighbour_ops.interpolate import (  # noqa: F401
     FeaturePropagation, Interpolated, feature_propagation, interpolate_points, interpolation_weights, torch_interpolate_points)
 from pointcloudcounterfactual_amd.neighbour_ops.attention import (  # noqa: F401

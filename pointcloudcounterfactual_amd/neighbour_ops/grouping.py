@@ -115,6 +115,50 @@ def group_points(x: torch.Tensor, idx: torch.Tensor, centres: torch.Tensor | Non
     return torch_group_points(x, idx.detach(), centres, point_major)
 
 
+class QueryGrouped(NamedTuple):
+    """What ``query_and_group`` returns."""
+
+    grouped: torch.Tensor     # [B,3+C,M,nsample] relative coordinates, then the gathered features
+    idx: torch.Tensor         # [B,M,nsample] int64 into the cloud (ball_query, or the list that was given)
+    cnt: torch.Tensor | None  # [B,M] int32 points inside each ball, capped at nsample; None for a given list
+
+
+def query_and_group(xyz: torch.Tensor, centres: torch.Tensor, features: torch.Tensor | None, radius: float, nsample: int,
+                    pad: str = 'first', idx: torch.Tensor | None = None) -> QueryGrouped:
+    """The grouping half of a set-abstraction layer around centres the caller has: ``ball_query(xyz, centres, radius,
+    nsample, pad)`` lists the neighbours of ``centres[B,M,3]`` in ``xyz[B,N,3]`` and one grouping op fills
+    ``grouped[B,3+C,M,nsample]``: channels 0-2 the neighbours' coordinates relative to their centre, the rest
+    ``features[B,C,N]`` gathered along the same list (absent for ``features=None``).  A list ``idx[B,M,nsample]`` int64 that
+    is given (a recorded one, or one of ``knn_cross``) is used in place of the ball query; ``cnt`` is then ``None``.
+    Gradients reach ``features``, ``xyz`` and ``centres``; ``idx`` and ``cnt`` are constants of the graph.  The arguments
+    are those of ``ball_query`` and ``group_points``, checked before anything runs."""
+    what = 'query_and_group'
+    _ball_args(xyz, centres, radius, nsample, pad)
+    b = xyz.shape[0]
+    if features is not None:
+        if features.dim() != 3 or features.shape[0] != b or features.shape[2] != xyz.shape[1] or features.shape[1] < 1:
+            raise ValueError(f'{what}: expected features[B = {b},C,N = {xyz.shape[1]}] with C >= 1, got {tuple(features.shape)}')
+        _float32('features', features)
+        _same_device('features', features, xyz.device)
+    cnt = None
+    if idx is None:
+        idx, cnt = ball_query(xyz, centres, radius, nsample, pad=pad, return_count=True)
+    else:
+        if tuple(idx.shape) != (b, centres.shape[1], nsample):
+            raise ValueError(f'{what}: expected idx[B,M,nsample] = {(b, centres.shape[1], nsample)}, got {tuple(idx.shape)}')
+        _list_arg(what, idx, b)
+        _list_on(idx, xyz.device)
+        idx = idx.detach()
+    if xyz.device.type == 'cuda':
+        parts = (xyz, centres, True) + (() if features is None else (features, None, False))
+        grouped = Grouped.apply(idx, *parts)
+    else:
+        grouped = torch_group_points(xyz, idx, centres, True)
+        if features is not None:
+            grouped = torch.cat((grouped, torch_group_points(features, idx)), 1)
+    return QueryGrouped(grouped, idx, cnt)
+
+
 class SampleAndGroup(NamedTuple):
     """What ``sample_and_group`` returns."""
 
@@ -144,12 +188,5 @@ def sample_and_group(xyz: torch.Tensor, features: torch.Tensor | None, m: int, r
     _ball_args(xyz, xyz.new_zeros((b, 0, 3)), radius, nsample, pad)  # (radius, nsample and pad, before the sampling runs)
     sel = farthest_point_sample(xyz, m, start)
     centres = torch.gather(xyz, 1, sel[:, :, None].expand(-1, -1, 3))
-    idx, cnt = ball_query(xyz, centres, radius, nsample, pad=pad, return_count=True)
-    if xyz.device.type == 'cuda':
-        parts = (xyz, centres, True) + (() if features is None else (features, None, False))
-        grouped = Grouped.apply(idx, *parts)
-    else:
-        grouped = torch_group_points(xyz, idx, centres, True)
-        if features is not None:
-            grouped = torch.cat((grouped, torch_group_points(features, idx)), 1)
+    grouped, idx, cnt = query_and_group(xyz, centres, features, radius, nsample, pad)
     return SampleAndGroup(centres, grouped, idx, cnt, sel)
