@@ -102,6 +102,46 @@ enum { PCC_BALL_PAD_FIRST = 0, PCC_BALL_PAD_NONE = 1 };
 int pcc_ball_query(int b, int n, int m, int nsample, float radius, int pad, const float *xyz, const float *centres,
                    int64_t *idx, int32_t *cnt, pcc_stream_t stream);
 
+/* Ragged batches: k-NN and ball query over packed clouds.  A packed batch is one xyz[n, 3] (point-major float32) that holds
+ * the clouds of the batch end to end, and offset[b] int32, their cumulative ends: cloud c is the rows
+ * [offset[c-1], offset[c]).  The queries (query[m, 3] with query_offset[b]; centres[m, 3] with centre_offset[b]) are packed
+ * the same way and may alias the points.  The layout of the published pointops package; no counterpart in the reference.
+ *   clouds      Every offset is clipped by the kernel and never trusted: lo_b = min(max(offset[b-1], 0), n) with
+ *               offset[-1] = 0, and hi_b = min(max(offset[b], lo_b), n).  The query side is clipped the same way against m.
+ *               Query row i belongs to the cloud whose clipped query range holds it.  A row behind the last range belongs
+ *               to no cloud.  A cloud may have no points or no queries.  Offsets stay on the device.  The entry points read
+ *               none of them on the host.  They need no host synchronisation and no workspace, so there is no pool
+ *               allocation.  The grid is a function of m alone.
+ *   indices     Indices are global: idx points into the packed xyz, so lo_b <= idx < hi_b for a real slot.  A row's words
+ *               depend only on its own cloud's points, the query, and k or (radius, nsample, pad), plus the base lo_b that
+ *               is added.  They do not depend on b, on where the cloud lies in the packed array, or on what else shares
+ *               the workgroup.
+ *   k-NN        The distance is pcc_knn's c <= 3 form with the query as in pcc_knn_cross: df = xyz[j] - query[i],
+ *               acc = df0 * df0, then two fmaf.  Each row is ascending by (distance, index).  -0 equals +0 and is reported
+ *               as +0.  A NaN distance is never listed.  +inf is listed like any other value.  A row that runs short is
+ *               completed with idx = -1, dist = +inf.  Short rows come from a cloud with fewer than k points, from NaN
+ *               distances, from a NaN query, or from a row of no cloud.  This deliberately differs from pcc_knn_cross's
+ *               n - 1 / NaN, because here k may exceed the cloud and -1 is what every list op skips.  The weight
+ *               1 / (+inf + eps) of such a slot is 0.  Requires 1 <= k <= 32 in this version.  k > 32 returns PCC_EINVAL
+ *               with a message that says so.  b <= 65535.  64-bit element offsets throughout.  b = 0 or m = 0 enqueues
+ *               nothing and returns PCC_OK.  n = 0 with m > 0 is allowed: every row is padding.  For a cloud with
+ *               hi_b - lo_b >= k and no NaN, idx - lo_b and dist are bit for bit what pcc_knn_cross(1, 3, m_b, n_b, k, ...)
+ *               returns for that cloud alone.  idx[m, k], and dist[m, k] when dist is non-null.
+ *   ball query  Per cloud this is exactly pcc_ball_query's rule: r2 = radius * radius in float32, a strict d < r2, the
+ *               first nsample inside points in ascending index, cnt, and pad FIRST / NONE.  With FIRST an empty ball is
+ *               filled with lo_b, the cloud's first point.  A row of no cloud or of an empty cloud gets cnt = 0 and -1
+ *               throughout, whatever pad is.  The argument checks are the same as pcc_ball_query's.  For every cloud,
+ *               idx - lo_b (real and FIRST-padded slots) and cnt are word for word pcc_ball_query(1, n_b, m_b, ...).
+ *               idx[m, nsample], and cnt[m] when cnt is non-null.
+ *   alignment   Every tensor argument may be any buffer aligned to its element size (the alignment paragraph above).
+ * Every query of a workgroup scans the union of the workgroup's clouds exhaustively: there is no culling and no split of
+ * the candidates for few queries over a huge cloud (it would need a workspace). */
+int pcc_knn_ragged(int b, int n, int m, int k, const float *xyz, const int32_t *offset, const float *query,
+                   const int32_t *query_offset, int64_t *idx, float *dist, pcc_stream_t stream);
+int pcc_ball_query_ragged(int b, int n, int m, int nsample, float radius, int pad, const float *xyz, const int32_t *offset,
+                          const float *centres, const int32_t *centre_offset, int64_t *idx, int32_t *cnt,
+                          pcc_stream_t stream);
+
 /* Grouping: the gather along an index list that belongs to another point set, idx[b, m, k] int64 into a cloud of n points
  * (m != n allowed): the lists of pcc_ball_query around the centres of pcc_fps, or of pcc_knn_cross.  No counterpart in the
  * reference; what a user writes in torch instead is an expanded index tensor, a gather per input, a subtraction and a cat.

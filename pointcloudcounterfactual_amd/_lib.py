@@ -60,6 +60,8 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_knn_cross': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_fps': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     'pcc_ball_query': (_int, [_int, _int, _int, _int, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_knn_ragged': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_ball_query_ragged': (_int, [_int, _int, _int, _int, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_group_points': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     'pcc_group_points_bwd': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     'pcc_interpolate': (_int, [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp]),

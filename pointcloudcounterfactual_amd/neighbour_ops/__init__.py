@@ -19,8 +19,12 @@ from pointcloudcounterfactual_amd.neighbour_ops.search import (  # noqa: F401
 from pointcloudcounterfactual_amd.neighbour_ops.sampling import (  # noqa: F401
     BALL_PAD, ball_query, farthest_point_sample, hip_ball_query, hip_farthest_point_sample, torch_ball_query,
     torch_farthest_point_sample)
+from pointcloudcounterfactual_amd.neighbour_ops.ragged import (  # noqa: F401
+    MAX_RAGGED_K, ball_query_ragged, batch2offset, farthest_point_sample_ragged, hip_ball_query_ragged, hip_knn_ragged, knn_ragged,
+    offset2batch, offset2bincount, torch_ball_query_ragged, torch_knn_ragged)
 from pointcloudcounterfactual_amd.neighbour_ops.grouping import (  # noqa: F401
-    Grouped, QueryGrouped, SampleAndGroup, group_points, query_and_group, sample_and_group, torch_group_points)
+    Grouped, QueryGrouped, SampleAndGroup, group_points, group_points_relative, query_and_group, sample_and_group,
+    torch_group_points)
 from pointcloudcounterfactual_amd.neighbour_ops.interpolate import (  # noqa: F401
     FeaturePropagation, Interpolated, feature_propagation, interpolate_points, interpolation_weights, torch_interpolate_points)
 from pointcloudcounterfactual_amd.neighbour_ops.attention import (  # noqa: F401

@@ -115,6 +115,36 @@ def group_points(x: torch.Tensor, idx: torch.Tensor, centres: torch.Tensor | Non
     return torch_group_points(x, idx.detach(), centres, point_major)
 
 
+def _group_relative(xyz: torch.Tensor, features: torch.Tensor | None, idx: torch.Tensor, centres: torch.Tensor,
+                    point_major: bool) -> torch.Tensor:
+    """``group_points_relative`` on checked arguments: one grouping op fills ``[B,3+C,M,k]`` on the accelerator (``out_c`` /
+    ``out_c0``: no ``cat``), the torch composition for CPU tensors."""
+    if xyz.device.type == 'cuda':
+        return Grouped.apply(idx, xyz, centres, True, *(() if features is None else (features, None, point_major)))
+    grouped = torch_group_points(xyz, idx, centres, True)
+    if features is not None:
+        grouped = torch.cat((grouped, torch_group_points(features, idx, None, point_major)), 1)
+    return grouped
+
+
+def group_points_relative(xyz: torch.Tensor, features: torch.Tensor | None, idx: torch.Tensor, centres: torch.Tensor,
+                          point_major: bool = False) -> torch.Tensor:
+    """``grouped[B,3+C,M,k]`` along one list ``idx[B,M,k]`` int64 into the N points: channels 0-2 the coordinates
+    ``xyz[B,N,3]`` of the listed points relative to their row's centre ``centres[B,M,3]``, behind them ``features`` gathered
+    along the same list -- ``[B,C,N]``, or ``[B,N,C]`` with ``point_major`` -- (absent for ``features=None``).  The grouping
+    half of ``query_and_group`` for a list the caller has, in either feature layout.  A slot outside ``[0, N)`` is +0 in
+    every channel and carries no gradient; differentiable in ``xyz``, ``centres`` and ``features``.  The arguments are those
+    of ``group_points``, checked before anything runs."""
+    what = 'group_points_relative'
+    _group_args(xyz, idx, centres, True, what)
+    if features is not None:
+        _group_args(features, idx, None, point_major, what)
+        if (features.shape[1] if point_major else features.shape[2]) != xyz.shape[1]:
+            raise ValueError(f'{what}: xyz and features name different numbers of points: {tuple(xyz.shape)} and {tuple(features.shape)}')
+        _same_device('features', features, xyz.device)
+    return _group_relative(xyz, features, idx.detach(), centres, point_major)
+
+
 class QueryGrouped(NamedTuple):
     """What ``query_and_group`` returns."""
 
@@ -149,14 +179,7 @@ def query_and_group(xyz: torch.Tensor, centres: torch.Tensor, features: torch.Te
         _list_arg(what, idx, b)
         _list_on(idx, xyz.device)
         idx = idx.detach()
-    if xyz.device.type == 'cuda':
-        parts = (xyz, centres, True) + (() if features is None else (features, None, False))
-        grouped = Grouped.apply(idx, *parts)
-    else:
-        grouped = torch_group_points(xyz, idx, centres, True)
-        if features is not None:
-            grouped = torch.cat((grouped, torch_group_points(features, idx)), 1)
-    return QueryGrouped(grouped, idx, cnt)
+    return QueryGrouped(_group_relative(xyz, features, idx, centres, False), idx, cnt)
 
 
 class SampleAndGroup(NamedTuple):
