@@ -438,6 +438,57 @@ int pcc_segment_pool(int b, int c, int n, int m, int mode, const float *x, const
 int pcc_segment_pool_bwd(int b, int c, int n, int m, int mode, const int32_t *cluster, const int32_t *seg,
                          const int32_t *arg, const float *grad_out, float *grad_x, pcc_stream_t stream);
 
+/* Ragged grid pooling: the index of pcc_grid_cluster for a whole packed batch (the layout of pcc_knn_ragged) with clouds of
+ * any size and up to 2^16 cells per axis -- the partition of Point Transformer V2 / V3's GridPool, of KPConv's grid
+ * subsampling and of the sparse-convolution front ends on scenes.  No counterpart in the reference; what a user writes in
+ * torch instead is a key, torch.unique(sorted, return_inverse, return_counts) and a scatter_reduce_.
+ *   layouts     xyz[n, 3] float32 packed, offset[b] int32 cumulative ends (on the device), start[b, 3] float32 (the origin of
+ *               every cloud's grid), size > 0 finite (the cell edge).  Outputs, all int32: cluster[n], order[n], seg[m + 1],
+ *               coord[m, 4], new_offset[b], n_cells[1].  64-bit address arithmetic throughout.
+ *   cloud       Exactly pcc_knn_ragged's rule.  Offsets are clipped and never trusted: lo_c = min(max(offset[c-1], 0), n)
+ *               with offset[-1] = 0, hi_c = min(max(offset[c], lo_c), n).  A row belongs to the cloud whose clipped range
+ *               holds it (bisection, <= 16 steps).  A row behind the last range belongs to none.  Nothing is read outside
+ *               xyz[0, n), offset[0, b), start[0, b), whatever the offsets hold.
+ *   cell        Per axis a, in float32 with every operation rounded (IEEE): t = (x[a] - start[c][a]) / size.  The point is
+ *               valid on that axis iff t >= 0 (false for NaN) and floorf(t) < 2^axis_bits; then q[a] = (int)floorf(t).  The
+ *               division is a correctly rounded division, not a reciprocal multiply.  A point is dropped if any axis is
+ *               invalid, if it is non-finite, or if it belongs to no cloud.  For coordinates at or above start this is
+ *               div(coord - start, size, rounding_mode='trunc').
+ *   key         cloud_bits is the bit width of b: the field holds 0 .. b, and the value b is the dropped key.
+ *               key = (c << 3 axis_bits) | (q0 << 2 axis_bits) | (q1 << axis_bits) | q2.  A dropped point keys as
+ *               b << 3 axis_bits, behind every valid key.  Requires 1 <= axis_bits <= 16 and
+ *               cloud_bits + 3 axis_bits <= 63.
+ *   outputs     With U the number of distinct valid keys and rank(key) the number of distinct valid keys below it:
+ *               order: all n points ascending by (key, point index); dropped points come last, in index order.
+ *               cluster[p] = rank if the point is valid and rank < m, else -1.
+ *               seg[r] for r < min(U, m) is the first sorted position of slot r's run; seg[min(U, m) .. m] is the end of
+ *               the last kept run.  This is pcc_grid_cluster's rule, so a padded slot's run is empty and
+ *               pcc_segment_pool(b = 1, ...) takes order / seg as they are.
+ *               coord[r] = (c, q0, q1, q2) for a kept slot, (-1, -1, -1, -1) for a padded one.
+ *               new_offset[c] = min(m, number of distinct valid keys of clouds <= c): the cumulative ends of the pooled
+ *               level, which is the offset of the next stage.
+ *               n_cells[0] = U, the true count; U > m is how a caller sees that cells were dropped.
+ *               The outputs at capacity m are those at capacity n restricted to their first m (+ 1) entries, apart from
+ *               the -1 of the dropped ranks.  Integers only.  Every word of all six outputs is written exactly once per
+ *               call.  Each word is fixed by the inputs: not by the run, not by what shares a workgroup.  A cloud's
+ *               coord[:, 1:], its runs and its slot numbers relative to new_offset[c-1] do not depend on the other clouds
+ *               or on the cloud's position in the batch.
+ *   refusals    PCC_EINVAL under "grid_cluster_ragged:" before anything is enqueued: n < 1, m < 1 or m > n, b < 1 or
+ *               b > 65535, n + 1 >= 2^31, axis_bits out of range or the key wider than 63 bits, size not finite or <= 0, a
+ *               null pointer.
+ *   launches    No host synchronisation: nothing is read on the host, and the grid of every launch is a function of
+ *               (b, n, m, axis_bits) alone.  The device-wide steps -- the key, ceil((cloud_bits + 3 axis_bits) / 8) passes
+ *               of a stable least-significant-digit radix sort over tiles of PCC_GRID_RAGGED_TILE keys, the run heads and
+ *               their scan, the outputs -- are separate launches on the caller's stream; no workgroup waits on another.
+ *               The sort's ping-pong buffers, histograms and scans come from the library's stream-ordered workspace
+ *               (PCC_ENOMEM when it cannot be had), about 28 bytes per point.
+ *   capture     Graph capture is neither claimed nor tested for this entry point.
+ *   alignment   Every tensor argument may be any buffer aligned to its element size (the alignment paragraph above). */
+#define PCC_GRID_RAGGED_TILE 2048
+int pcc_grid_cluster_ragged(int b, int n, int m, int axis_bits, const float *xyz, const int32_t *offset, const float *start,
+                            float size, int32_t *cluster, int32_t *order, int32_t *seg, int32_t *coord, int32_t *new_offset,
+                            int32_t *n_cells, pcc_stream_t stream);
+
 /* Submanifold sparse convolution (MinkUNet, SparseUNet, the conditional position encoding of Point Transformer V3) on the
  * slots of pcc_grid_cluster: every occupied cell sums, over the ksize^3 offsets of a kernel, a weight matrix applied to the
  * features of the occupied cell at that offset; the set of occupied cells does not grow.  No counterpart in the reference;

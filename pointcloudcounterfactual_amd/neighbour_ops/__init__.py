@@ -39,6 +39,9 @@ from pointcloudcounterfactual_amd.neighbour_ops.voxel import (  # noqa: F401
 from pointcloudcounterfactual_amd.neighbour_ops.pooling import (  # noqa: F401
     GridIndex, GridPooled, SegmentPooled, grid_cluster, grid_pool, grid_subsample, grid_unpool, segment_pool, torch_grid_cluster,
     torch_segment_pool, torch_segment_pool_bwd)
+from pointcloudcounterfactual_amd.neighbour_ops.ragged_grid import (  # noqa: F401
+    GRID_RAGGED_TILE, MAX_AXIS_BITS, RaggedGrid, RaggedGridPooled, default_axis_bits, grid_cluster_ragged, grid_pool_ragged,
+    grid_unpool_ragged, hip_grid_cluster_ragged, ragged_grid_start, torch_grid_cluster_ragged)
 from pointcloudcounterfactual_amd.neighbour_ops.sparse import (  # noqa: F401
     KERNEL_SIZES, SparseConvMap, SparseConvolved, SubmanifoldConv3d, cell_neighbours, sparse_conv, torch_cell_neighbours,
     torch_sparse_conv)
