@@ -53,10 +53,17 @@ int pcc_last_status(void);
  * trace reports.  pcc_profile_enable(0): off.  pcc_profile_read synchronises on the recorded events and returns the
  * average duration (microseconds) and the number of recorded scopes whose name starts with `kernel_prefix` since the
  * last enable / pcc_profile_reset().  Returns 0, or PCC_EINVAL if nothing matched.  Not thread-safe against
- * concurrent launches; meant for bench.py. */
+ * concurrent launches; meant for bench.py.
+ * pcc_profile_names is the exact launch record since the last enable / pcc_profile_reset(): one line
+ * "name<TAB>launches<LF>" per distinct scope name, whole names (no prefix matching: "am_materialise_kernel" and
+ * "am_materialise_kernel<cost>" are two lines), in the order of each name's first launch.  A name carries the template
+ * instantiation wherever a launcher picks one of several ("fps_reg_kernel<256,8>").  Waits for the recorded events,
+ * writes at most capacity - 1 bytes and a terminating 0 into buf (nothing if buf is NULL or capacity is 0) and returns
+ * the bytes the whole text needs, terminator included: call again with a larger buffer if that exceeds capacity. */
 void pcc_profile_enable(int on);
 void pcc_profile_reset(void);
 int pcc_profile_read(const char *kernel_prefix, double *avg_us, int *launches);
+size_t pcc_profile_names(char *buf, size_t capacity);
 
 /* ---- Chamfer nearest neighbour ---------------------------------------------------------------
  * Replaces `nndistance` (reference nndistance.cu:125-128; declared structural_loss.cpp:13).

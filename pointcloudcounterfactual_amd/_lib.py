@@ -32,6 +32,7 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_profile_enable': (None, [_int]),
     'pcc_profile_reset': (None, []),
     'pcc_profile_read': (_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
+    'pcc_profile_names': (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
     'nndistance': (None, [_int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_nndistance': (_int, [_int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nndistancegrad': (None, [_int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -187,12 +188,23 @@ def tuning(name: str, value: int) -> Iterator[None]:
 def profile(mode: int = 1) -> Iterator[Callable[[str | bytes], tuple[float, int]]]:
     """The library's launch profile for the body of a ``with``: cleared and enabled on entry (``mode`` 1: one event pair
     around each launch), disabled and cleared behind it, whether or not the body raised.  Yields ``read(name)`` ->
-    (microseconds per launch, launches) over the profile names that begin with ``name``; synchronise before reading."""
+    (microseconds per launch, launches) over the profile names that begin with ``name``; synchronise before reading.
+    ``read.exact()`` -> {exact profile name: launches} of everything recorded so far, no prefix matching (it synchronises
+    the device itself, so the record is complete)."""
     def read(name: str | bytes) -> tuple[float, int]:
         us, count = ctypes.c_double(), ctypes.c_int()
         lib.pcc_profile_read(name.encode() if isinstance(name, str) else name, ctypes.byref(us), ctypes.byref(count))
         return us.value, count.value
 
+    def exact() -> dict[str, int]:
+        torch.cuda.synchronize()
+        need = lib.pcc_profile_names(None, 0)
+        buf = ctypes.create_string_buffer(need)
+        if lib.pcc_profile_names(buf, need) != need:
+            raise RuntimeError('the launch record changed while it was read')
+        return {name: int(count) for name, count in (line.split('\t') for line in buf.value.decode().splitlines())}
+
+    read.exact = exact  # type: ignore[attr-defined]
     lib.pcc_profile_reset()
     lib.pcc_profile_enable(mode)
     try:

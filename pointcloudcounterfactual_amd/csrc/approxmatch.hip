@@ -1144,17 +1144,34 @@ static bool cull_enabled() {  // measurement switch (pcc_test_hooks.h): every wo
     return pcc::tuning(PCC_TUNE_AM_NOCULL) == 0;
 }
 
+// The launch profile's name of a pass: mode, level, and which kernel variant ran it -- [0] "plain" (no skip logic: what
+// am_nocull runs everywhere), [1] the level's work-skipping variant: "fine" (V_CULL, am_fine_kernel), "own" (V_COWN) or
+// "list" (V_CLIST).
 template <int MODE>
-const char *phase_name(int level) {
-    static const char *const names[4][kLevels] = {
-        {"am_phase_kernel<A> L0", "", "", "", "", "", "", "", ""},
-        {"am_phase_kernel<B> L0", "am_phase_kernel<B> L1", "am_phase_kernel<B> L2", "am_phase_kernel<B> L3",
-         "am_phase_kernel<B> L4", "am_phase_kernel<B> L5", "am_phase_kernel<B> L6", "am_phase_kernel<B> L7",
-         "am_phase_kernel<B> L8"},
-        {"am_phase_kernel<CA> L0", "am_phase_kernel<CA> L1", "am_phase_kernel<CA> L2", "am_phase_kernel<CA> L3",
-         "am_phase_kernel<CA> L4", "am_phase_kernel<CA> L5", "am_phase_kernel<CA> L6", "am_phase_kernel<CA> L7", ""},
-        {"", "", "", "", "", "", "", "", "am_phase_kernel<C> L8"}};
-    return names[MODE][level];
+const char *phase_name(int level, bool skipping) {
+    static const char *const names[4][kLevels][2] = {
+        {{"am_phase_kernel<A> L0 plain", "am_phase_kernel<A> L0 fine"}, {"", ""}, {"", ""}, {"", ""}, {"", ""},
+         {"", ""}, {"", ""}, {"", ""}, {"", ""}},
+        {{"am_phase_kernel<B> L0 plain", "am_phase_kernel<B> L0 fine"},
+         {"am_phase_kernel<B> L1 plain", "am_phase_kernel<B> L1 fine"},
+         {"am_phase_kernel<B> L2 plain", "am_phase_kernel<B> L2 fine"},
+         {"am_phase_kernel<B> L3 plain", "am_phase_kernel<B> L3 own"},
+         {"am_phase_kernel<B> L4 plain", "am_phase_kernel<B> L4 own"},
+         {"am_phase_kernel<B> L5 plain", "am_phase_kernel<B> L5 own"},
+         {"am_phase_kernel<B> L6 plain", "am_phase_kernel<B> L6 own"},
+         {"am_phase_kernel<B> L7 plain", "am_phase_kernel<B> L7 own"},
+         {"am_phase_kernel<B> L8 plain", "am_phase_kernel<B> L8 own"}},
+        {{"am_phase_kernel<CA> L0 plain", "am_phase_kernel<CA> L0 fine"},
+         {"am_phase_kernel<CA> L1 plain", "am_phase_kernel<CA> L1 fine"},
+         {"am_phase_kernel<CA> L2 plain", "am_phase_kernel<CA> L2 fine"},
+         {"am_phase_kernel<CA> L3 plain", "am_phase_kernel<CA> L3 list"},
+         {"am_phase_kernel<CA> L4 plain", "am_phase_kernel<CA> L4 list"},
+         {"am_phase_kernel<CA> L5 plain", "am_phase_kernel<CA> L5 list"},
+         {"am_phase_kernel<CA> L6 plain", "am_phase_kernel<CA> L6 list"},
+         {"am_phase_kernel<CA> L7 plain", "am_phase_kernel<CA> L7 list"}, {"", ""}},
+        {{"", ""}, {"", ""}, {"", ""}, {"", ""}, {"", ""}, {"", ""}, {"", ""}, {"", ""},
+         {"am_phase_kernel<C> L8 plain", "am_phase_kernel<C> L8 list"}}};
+    return names[MODE][level][skipping];
 }
 
 template <int MODE, int R, int S, int G = 1>
@@ -1164,7 +1181,8 @@ int launch_phase_rs(PhaseArgs a, int b, int var, hipStream_t st, const char *wha
     const long long grid = (long long)b * a.tiles;
     if (grid > 0x7fffffffLL) return pcc::invalid("approxmatch: grid too large");
     {
-        pcc::ProfScope prof(phase_name<MODE>(a.level), st);
+        const bool skipping = (var == V_CLIST && (MODE == PH_CA || MODE == PH_C)) || (var == V_COWN && MODE == PH_B);
+        pcc::ProfScope prof(phase_name<MODE>(a.level, skipping), st);
         const dim3 g((unsigned)grid), blk(64 * S);
         // only the combinations the schedule uses are instantiated
         if (var == V_CLIST && (MODE == PH_CA || MODE == PH_C))
@@ -1183,7 +1201,7 @@ int launch_fine(PhaseArgs a, int b, hipStream_t st, const char *what) {
     const long long grid = (long long)b * a.tiles;
     if (grid > 0x7fffffffLL) return pcc::invalid("approxmatch: grid too large");
     {
-        pcc::ProfScope prof(phase_name<MODE>(a.level), st);
+        pcc::ProfScope prof(phase_name<MODE>(a.level, true), st);
         hipLaunchKernelGGL((am_fine_kernel<(MODE == PH_C ? PH_CA : MODE), kPhCH>), dim3((unsigned)grid), dim3(64 * kFineS), 0, st, a);
     }
     return pcc::check_launch(what);

@@ -344,7 +344,9 @@ void launch_bwd(const pcc::ListPlan &p, hipStream_t st, int c, int s, int n, int
                 const float *grad_out, float *grad_x, float *grad_rel) {
     const dim3 block(p.threads((unsigned)m * (unsigned)k, 1));  // a lane per slot
     if (p.lds) {
-        pcc::ProfScope prof("agg_bwd_kernel<lds>", st);
+        static const char *const kNames[] = {"agg_bwd_kernel<lds> cb=1", "agg_bwd_kernel<lds> cb=2",
+                                             "agg_bwd_kernel<lds> cb=4", "agg_bwd_kernel<lds> cb=8"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
             (void)pcc::allow_lds<agg_bwd_kernel<CB, false>>(pcc::kLdsWg);
             hipLaunchKernelGGL((agg_bwd_kernel<CB, false>), dim3(p.grid()), block, p.lds_bytes, st, c, s, n, m, k, p.units, p.nsplit,
@@ -398,7 +400,9 @@ int pcc_aggregate_points(int b, int c, int g, int n, int m, int k, const float *
     const unsigned pts = p.chunk < (unsigned)m ? p.chunk : (unsigned)m, per_pass = (unsigned)(kTileSlots / k);
     const dim3 block(p.threads_for((unsigned long long)(pts < per_pass ? pts : per_pass) * k));  // a lane per slot of a pass
     if (p.lds) {
-        pcc::ProfScope prof("agg_fwd_kernel<lds>", st);
+        static const char *const kNames[] = {"agg_fwd_kernel<lds> cb=1", "agg_fwd_kernel<lds> cb=2",
+                                             "agg_fwd_kernel<lds> cb=4", "agg_fwd_kernel<lds> cb=8"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
             (void)pcc::allow_lds<agg_fwd_kernel<CB, false>>(pcc::kLdsWg);
             hipLaunchKernelGGL((agg_fwd_kernel<CB, false>), dim3(p.grid()), block, p.lds_bytes + (size_t)CB * kTileWords * sizeof(float),

@@ -127,25 +127,28 @@ __global__ __launch_bounds__(WAVES * 64) void ball_lds_kernel(int n, int m, int 
 }
 
 template <int WAVES>
-void launch_direct(int b, int n, int m, int nsample, float r2, int pad, const float *xyz, const float *centres, int64_t *idx,
+void launch_direct(const char *name, int b, int n, int m, int nsample, float r2, int pad, const float *xyz, const float *centres, int64_t *idx,
                    int32_t *cnt, hipStream_t st) {
-    pcc::ProfScope prof("ball_direct_kernel", st);
+    pcc::ProfScope prof(name, st);
     hipLaunchKernelGGL((ball_direct_kernel<WAVES>), dim3((m - 1) / WAVES + 1, b), dim3(WAVES * 64), 0, st, n, m, nsample, r2,
                        pad, xyz, centres, idx, cnt);
 }
 template <int WAVES, int TILE>
-void launch_lds(int b, int n, int m, int nsample, float r2, int pad, const float *xyz, const float *centres, int64_t *idx,
+void launch_lds(const char *name, int b, int n, int m, int nsample, float r2, int pad, const float *xyz, const float *centres, int64_t *idx,
                 int32_t *cnt, hipStream_t st) {
-    pcc::ProfScope prof("ball_lds_kernel", st);
+    pcc::ProfScope prof(name, st);
     hipLaunchKernelGGL((ball_lds_kernel<WAVES, TILE>), dim3((m - 1) / WAVES + 1, b), dim3(WAVES * 64), 0, st, n, m, nsample,
                        r2, pad, xyz, centres, idx, cnt);
 }
 
 // The variants: value v of the ball_path switch forces kPaths[v - 1]; kProduct is what a call takes without it
 // (DESIGN.md section 4f has the measurements behind the choice).
-typedef void (*Launch)(int, int, int, int, float, int, const float *, const float *, int64_t *, int32_t *, hipStream_t);
+typedef void (*Launch)(const char *, int, int, int, int, float, int, const float *, const float *, int64_t *, int32_t *, hipStream_t);
 const Launch kPaths[] = {launch_direct<4>, launch_direct<16>, launch_lds<4, 1024>, launch_lds<16, 4096>};
+// ... under these names in the launch profile: the instantiation, <WAVES> and <WAVES,TILE>
+const char *const kNames[] = {"ball_direct_kernel<4>", "ball_direct_kernel<16>", "ball_lds_kernel<4,1024>", "ball_lds_kernel<16,4096>"};
 constexpr int kNumPaths = (int)(sizeof kPaths / sizeof kPaths[0]);
+static_assert(sizeof kNames / sizeof kNames[0] == kNumPaths, "ball_query: one profile name per variant");
 constexpr int kProduct = 3;  // 16 queries per workgroup over LDS tiles of 4096 candidates: the fastest at every shape measured
 
 }  // namespace
@@ -163,6 +166,6 @@ extern "C" int pcc_ball_query(int b, int n, int m, int nsample, float radius, in
     const float r2 = radius * radius;  // one float32 multiplication (-ffp-contract=off)
     const int forced = pcc::tuning(PCC_TUNE_BALL_PATH);  // measurement switch: 1 .. 4 forces a variant
     const int path = forced >= 1 && forced <= kNumPaths ? forced - 1 : kProduct;
-    kPaths[path](b, n, m, nsample, r2, pad, xyz, centres, idx, cnt, static_cast<hipStream_t>(stream));
+    kPaths[path](kNames[path], b, n, m, nsample, r2, pad, xyz, centres, idx, cnt, static_cast<hipStream_t>(stream));
     return pcc::check_launch("ball_query");
 }

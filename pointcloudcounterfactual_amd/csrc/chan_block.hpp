@@ -35,6 +35,9 @@ inline int fit_cb(int cb_max, size_t row_bytes, size_t bytes = kLdsHalfCu) {
     return cb;
 }
 
+// position of cb in {1, 2, 4, 8, 16}: the row of a launcher's table of launch-profile names, which carry the instantiation
+inline int cb_index(int cb) { return cb >= 16 ? 4 : cb >= 8 ? 3 : cb >= 4 ? 2 : cb >= 2 ? 1 : 0; }
+
 // f(std::integral_constant<int, cb>) for cb a power of two <= CB_MAX
 template <int CB_MAX = 8, class F>
 void dispatch_cb(int cb, F &&f) {

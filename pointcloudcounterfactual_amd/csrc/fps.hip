@@ -201,8 +201,9 @@ __global__ __launch_bounds__(kMemBlock) void fps_mem_kernel(int n, int m, const 
 }
 
 template <int BLOCK, int P>
-void launch_reg(int b, int n, int m, const float *xyz, const int32_t *start, int64_t *idx, float *dist, hipStream_t st) {
-    pcc::ProfScope prof("fps_reg_kernel", st);
+void launch_reg(const char *name, int b, int n, int m, const float *xyz, const int32_t *start, int64_t *idx, float *dist,
+                hipStream_t st) {
+    pcc::ProfScope prof(name, st);
     hipLaunchKernelGGL((fps_reg_kernel<BLOCK, P>), dim3(b), dim3(BLOCK), 0, st, n, m, xyz, start, idx, dist);
 }
 
@@ -210,11 +211,16 @@ void launch_reg(int b, int n, int m, const float *xyz, const int32_t *start, int
 // product takes the first one that holds the cloud.
 struct Path {
     int capacity;
-    void (*launch)(int, int, int, const float *, const int32_t *, int64_t *, float *, hipStream_t);
+    void (*launch)(const char *, int, int, int, const float *, const int32_t *, int64_t *, float *, hipStream_t);
+    const char *name;  // the launch profile's: the instantiation, <BLOCK,P>
 };
-const Path kPaths[] = {{64 * 4, launch_reg<64, 4>},      {256 * 4, launch_reg<256, 4>},    {256 * 8, launch_reg<256, 8>},
-                       {512 * 8, launch_reg<512, 8>},    {1024 * 8, launch_reg<1024, 8>},  {1024 * 16, launch_reg<1024, 16>},
-                       {0, nullptr}};
+const Path kPaths[] = {{64 * 4, launch_reg<64, 4>, "fps_reg_kernel<64,4>"},
+                       {256 * 4, launch_reg<256, 4>, "fps_reg_kernel<256,4>"},
+                       {256 * 8, launch_reg<256, 8>, "fps_reg_kernel<256,8>"},
+                       {512 * 8, launch_reg<512, 8>, "fps_reg_kernel<512,8>"},
+                       {1024 * 8, launch_reg<1024, 8>, "fps_reg_kernel<1024,8>"},
+                       {1024 * 16, launch_reg<1024, 16>, "fps_reg_kernel<1024,16>"},
+                       {0, nullptr, nullptr}};
 constexpr int kNumPaths = (int)(sizeof kPaths / sizeof kPaths[0]);
 
 }  // namespace
@@ -233,7 +239,7 @@ extern "C" int pcc_fps(int b, int n, int m, const float *xyz, const int32_t *sta
     while (kPaths[path].capacity && kPaths[path].capacity < n) ++path;
     if (forced >= 1 && forced <= kNumPaths && (!kPaths[forced - 1].capacity || kPaths[forced - 1].capacity >= n)) path = forced - 1;
     if (kPaths[path].capacity) {
-        kPaths[path].launch(b, n, m, xyz, start, idx, dist, st);
+        kPaths[path].launch(kPaths[path].name, b, n, m, xyz, start, idx, dist, st);
         return pcc::check_launch("fps");
     }
     pcc::WsBlock ws(st);

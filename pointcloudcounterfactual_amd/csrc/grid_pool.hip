@@ -402,7 +402,9 @@ int pcc_segment_pool(int b, int c, int n, int m, int mode, const float *x, const
             const int cb = pcc::fit_cb(kCb, (size_t)n * sizeof(float));  // 8 channels up to n = 2048, 4 to 4096, 2 to 8192, 1 above
             const long long blocks = (long long)b * pcc::ceil_div(c, cb);
             const int threads = std::min(kLdsThreads, pcc::ceil_div(std::max(m, pcc::ceil_div(cb * n, 4)), 64) * 64);
-            pcc::ProfScope prof("seg_pool_lds_kernel", st);
+            static const char *const kNames[] = {"seg_pool_lds_kernel<1>", "seg_pool_lds_kernel<2>",
+                                                 "seg_pool_lds_kernel<4>", "seg_pool_lds_kernel<8>"};
+            pcc::ProfScope prof(kNames[pcc::cb_index(cb)], st);
             pcc::dispatch_cb<kCb>(cb, [&](auto CB) {
                 attr = pcc::allow_lds<seg_pool_lds_kernel<MODE, CB>>(pcc::kLdsWgDyn);
                 if (attr == hipSuccess)
@@ -439,7 +441,9 @@ int pcc_segment_pool_bwd(int b, int c, int n, int m, int mode, const int32_t *cl
             const int per = MODE == kMax ? 2 : 1;  // rows of m words per channel
             const int cb = pcc::fit_cb(kCb, (size_t)m * per * sizeof(float));
             const int threads = std::min(kLdsThreads, pcc::ceil_div(n, 64) * 64);
-            pcc::ProfScope prof("seg_pool_bwd_lds_kernel", st);
+            static const char *const kNames[] = {"seg_pool_bwd_lds_kernel<1>", "seg_pool_bwd_lds_kernel<2>",
+                                                 "seg_pool_bwd_lds_kernel<4>", "seg_pool_bwd_lds_kernel<8>"};
+            pcc::ProfScope prof(kNames[pcc::cb_index(cb)], st);
             pcc::dispatch_cb<kCb>(cb, [&](auto CB) {
                 attr = pcc::allow_lds<seg_pool_bwd_lds_kernel<MODE, CB>>(pcc::kLdsWgDyn);
                 if (attr == hipSuccess)

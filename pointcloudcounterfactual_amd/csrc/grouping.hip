@@ -250,7 +250,9 @@ int pcc_group_points(int b, int c, int n, int m, int k, int point_major, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     const pcc::ListPlan p = make_plan(b, c, n, m, k, true);
     if (p.lds) {
-        pcc::ProfScope prof("group_fwd_kernel<lds>", st);
+        static const char *const kNames[] = {"group_fwd_kernel<lds> cb=1", "group_fwd_kernel<lds> cb=2",
+                                             "group_fwd_kernel<lds> cb=4", "group_fwd_kernel<lds> cb=8"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
             (void)pcc::allow_lds<group_fwd_kernel<CB, false>>(pcc::kLdsWg);
             hipLaunchKernelGGL((group_fwd_kernel<CB, false>), dim3(p.grid()), dim3(kT), p.lds_bytes, st, c, n, m, k, point_major,
@@ -277,7 +279,9 @@ int pcc_group_points_bwd(int b, int c, int n, int m, int k, int point_major, con
     if (grad_x) {
         const pcc::ListPlan p = make_plan(b, c, n, m, k, false);
         if (p.lds) {
-            pcc::ProfScope prof("group_bwd_kernel<lds>", st);
+            static const char *const kNames[] = {"group_bwd_kernel<lds> cb=1", "group_bwd_kernel<lds> cb=2",
+                                                 "group_bwd_kernel<lds> cb=4", "group_bwd_kernel<lds> cb=8"};
+            pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
             pcc::dispatch_cb(p.cb, [&](auto CB) {
                 (void)pcc::allow_lds<group_bwd_kernel<CB, false>>(pcc::kLdsWg);
                 hipLaunchKernelGGL((group_bwd_kernel<CB, false>), dim3(p.grid()), dim3(kT), p.lds_bytes, st, c, n, m, k,

@@ -231,7 +231,9 @@ int pcc_interpolate(int b, int c, int n, int m, int k, const float *x, const int
     // slice is aligned when the base is and m % 4 == 0)
     const dim3 block(p.threads((unsigned)m, (m & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 4 : 1));
     if (p.lds) {
-        pcc::ProfScope prof("interp_fwd_kernel<lds>", st);
+        static const char *const kNames[] = {"interp_fwd_kernel<lds> cb=1", "interp_fwd_kernel<lds> cb=2",
+                                             "interp_fwd_kernel<lds> cb=4", "interp_fwd_kernel<lds> cb=8"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
         pcc::dispatch_cb(p.cb, [&](auto CB) {
             full_or_not(block, [&](auto FULL) {
                 (void)pcc::allow_lds<interp_fwd_kernel<CB, false, FULL>>(pcc::kLdsWg);
@@ -263,7 +265,9 @@ int pcc_interpolate_bwd(int b, int c, int n, int m, int k, const float *x, const
         const pcc::ListPlan p = make_plan(b, c, n, m, false);
         const dim3 block(p.threads((unsigned)m, 1));
         if (p.lds) {
-            pcc::ProfScope prof("interp_bwd_x_kernel<lds>", st);
+            static const char *const kNames[] = {"interp_bwd_x_kernel<lds> cb=1", "interp_bwd_x_kernel<lds> cb=2",
+                                                 "interp_bwd_x_kernel<lds> cb=4", "interp_bwd_x_kernel<lds> cb=8"};
+            pcc::ProfScope prof(kNames[pcc::cb_index(p.cb)], st);
             pcc::dispatch_cb(p.cb, [&](auto CB) {
                 full_or_not(block, [&](auto FULL) {
                     (void)pcc::allow_lds<interp_bwd_x_kernel<CB, false, FULL>>(pcc::kLdsWg);

@@ -53,6 +53,13 @@ int with_slots(int k, F &&f) {
     return f(std::integral_constant<int, kSlots[I]>{});
 }
 
+// position of the instantiation K in kSlots (the row of a launcher's table of profile names)
+constexpr int slot_index(int K) {
+    int i = 0;
+    for (int s : kSlots) i += s < K;
+    return i;
+}
+
 // the next smaller instantiation (0 below the first): the sorted kernel of K serves k in (prev_slots(K), K]
 constexpr int prev_slots(int K) {
     int p = 0;

@@ -367,14 +367,18 @@ __global__ __launch_bounds__(64 * kSW, (K == 16 ? 3 : K <= 25 ? 4 : 1)) void knn
 
 template <int K>
 int launch_small(int b, int c, int n, int k, const float *x, int64_t *indices, hipStream_t st) {
-    pcc::ProfScope prof("knn_small_kernel", st);
+    static const char *const kNames[] = {"knn_small_kernel<4,4>", "knn_small_kernel<8,4>", "knn_small_kernel<16,4>",
+                                         "knn_small_kernel<20,4>", "knn_small_kernel<25,4>", "knn_small_kernel<32,4>"};  // <K,S>
+    pcc::ProfScope prof(kNames[slot_index(K)], st);
     hipLaunchKernelGGL((knn_small_kernel<K, 4>), dim3(pcc::ceil_div(n, 64), b), dim3(256), 0, st, c, n, k, x, indices);
     return PCC_OK;
 }
 
 template <int K>
 int launch_sorted(const KnnSortedArgs &a, hipStream_t st) {
-    pcc::ProfScope prof("knn_sorted_kernel", st);
+    static const char *const kNames[] = {"knn_sorted_kernel<4>", "knn_sorted_kernel<8>", "knn_sorted_kernel<16>",
+                                         "knn_sorted_kernel<20>", "knn_sorted_kernel<25>", "knn_sorted_kernel<32>"};
+    pcc::ProfScope prof(kNames[slot_index(K)], st);
     const int waves = a.batch * a.nb;
     hipLaunchKernelGGL((knn_sorted_kernel<K, prev_slots(K)>), dim3(pcc::ceil_div(waves, kSW)), dim3(64 * kSW), 0, st, a);
     return PCC_OK;

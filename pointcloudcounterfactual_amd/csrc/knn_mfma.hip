@@ -557,6 +557,28 @@ int with_cp(int c, F &&f) {
     }
 }
 
+constexpr int cp_index(int CP) {
+    int i = 0;
+    for (int v : kCPs) i += v < CP;
+    return i;
+}
+// the launch profile's names of the instantiations, [slot_index(K)][cp_index(CP)]: <K,CP,tiles per stage> and <K,CP>
+static_assert(kTT128 == 1, "the profile names say one tile per stage at 128 channels");
+const char *const kMfmaNames[][5] = {
+    {"knn_mfma_kernel<4,8,1>", "knn_mfma_kernel<4,16,1>", "knn_mfma_kernel<4,32,1>", "knn_mfma_kernel<4,64,1>", "knn_mfma_kernel<4,128,1>"},
+    {"knn_mfma_kernel<8,8,1>", "knn_mfma_kernel<8,16,1>", "knn_mfma_kernel<8,32,1>", "knn_mfma_kernel<8,64,1>", "knn_mfma_kernel<8,128,1>"},
+    {"knn_mfma_kernel<16,8,1>", "knn_mfma_kernel<16,16,1>", "knn_mfma_kernel<16,32,1>", "knn_mfma_kernel<16,64,1>", "knn_mfma_kernel<16,128,1>"},
+    {"knn_mfma_kernel<20,8,1>", "knn_mfma_kernel<20,16,1>", "knn_mfma_kernel<20,32,1>", "knn_mfma_kernel<20,64,1>", "knn_mfma_kernel<20,128,1>"},
+    {"knn_mfma_kernel<25,8,1>", "knn_mfma_kernel<25,16,1>", "knn_mfma_kernel<25,32,1>", "knn_mfma_kernel<25,64,1>", "knn_mfma_kernel<25,128,1>"},
+    {"knn_mfma_kernel<32,8,1>", "knn_mfma_kernel<32,16,1>", "knn_mfma_kernel<32,32,1>", "knn_mfma_kernel<32,64,1>", "knn_mfma_kernel<32,128,1>"}};
+const char *const kSplitNames[][5] = {
+    {"", "knn_mfma_split_kernel<4,16>", "knn_mfma_split_kernel<4,32>", "knn_mfma_split_kernel<4,64>", "knn_mfma_split_kernel<4,128>"},
+    {"", "knn_mfma_split_kernel<8,16>", "knn_mfma_split_kernel<8,32>", "knn_mfma_split_kernel<8,64>", "knn_mfma_split_kernel<8,128>"},
+    {"", "knn_mfma_split_kernel<16,16>", "knn_mfma_split_kernel<16,32>", "knn_mfma_split_kernel<16,64>", "knn_mfma_split_kernel<16,128>"},
+    {"", "knn_mfma_split_kernel<20,16>", "knn_mfma_split_kernel<20,32>", "knn_mfma_split_kernel<20,64>", "knn_mfma_split_kernel<20,128>"},
+    {"", "knn_mfma_split_kernel<25,16>", "knn_mfma_split_kernel<25,32>", "knn_mfma_split_kernel<25,64>", "knn_mfma_split_kernel<25,128>"},
+    {"", "knn_mfma_split_kernel<32,16>", "knn_mfma_split_kernel<32,32>", "knn_mfma_split_kernel<32,64>", "knn_mfma_split_kernel<32,128>"}};
+
 template <int K, int CP>
 int launch_split(int b, int c, int n, int k, const float *x, const float *sq, int64_t *indices, hipStream_t st) {
     constexpr int lds = split_lds_bytes<K, CP>();
@@ -566,7 +588,7 @@ int launch_split(int b, int c, int n, int k, const float *x, const float *sq, in
     }
     pcc::WsBlock logs(st);  // the selection waves' records (stream-ordered: freed behind the kernel)
     if (int rc = logs.alloc(split_log_bytes(b, n), "knn: workspace allocation failed")) return rc;
-    pcc::ProfScope prof("knn_mfma_split_kernel", st);
+    pcc::ProfScope prof(kSplitNames[slot_index(K)][cp_index(CP)], st);
     hipLaunchKernelGGL((knn_mfma_split_kernel<K, CP>), dim3(pcc::ceil_div(n, kSplitQ), b), dim3(512), lds, st, c, n, k, x, sq,
                        reinterpret_cast<float2 *>(logs.p), indices);
     return PCC_OK;
@@ -581,11 +603,11 @@ int launch_mfma(int b, int c, int n, int k, const float *x, const float *sq, int
     if (sw == 2 || (sw == 0 && (long long)pcc::ceil_div(n, kSplitQ) * b * 4 >= 3LL * pcc::device_cus() && split_log_bytes(b, n) <= (1ull << 30))) {
         return with_cp<16>(c, [&](auto CP) { return launch_split<K, CP>(b, c, n, k, x, sq, indices, st); });
     }
-    pcc::ProfScope prof("knn_mfma_kernel", st);
     const dim3 grid(pcc::ceil_div(n, 128), b);
     // two 32-candidate tiles (two accumulator chains) per stage while the double-buffered tiles leave room for two
     // workgroups per CU; 128 channels keep one
     return with_cp<8>(c, [&](auto CP) {
+        pcc::ProfScope prof(kMfmaNames[slot_index(K)][cp_index(CP)], st);
         hipLaunchKernelGGL((knn_mfma_kernel<K, CP, (CP == 128 ? kTT128 : 1)>), grid, dim3(256), 0, st, c, n, k, x, sq, indices);
         return PCC_OK;
     });

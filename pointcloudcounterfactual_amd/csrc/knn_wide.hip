@@ -270,7 +270,16 @@ __global__ __launch_bounds__(64 * kSelW) void knn_wide_select_kernel(WideSelArgs
 
 template <int L, int SRC>
 void launch_select(const WideSelArgs &a, hipStream_t st) {
-    pcc::ProfScope prof("knn_wide_select_kernel", st);
+    // the launch profile's name: <list slots, source of the keys>, "sliced" where the candidate axis is cut (a.slices > 1:
+    // partial lists to workspace, merged by the <.,keys> launch that follows)
+    static const char *const kNames[2][3][2] = {
+        {{"knn_wide_select_kernel<64,diff>", "knn_wide_select_kernel<64,diff> sliced"},
+         {"knn_wide_select_kernel<64,rows>", "knn_wide_select_kernel<64,rows> sliced"},
+         {"knn_wide_select_kernel<64,keys>", "knn_wide_select_kernel<64,keys>"}},
+        {{"knn_wide_select_kernel<128,diff>", "knn_wide_select_kernel<128,diff> sliced"},
+         {"knn_wide_select_kernel<128,rows>", "knn_wide_select_kernel<128,rows> sliced"},
+         {"knn_wide_select_kernel<128,keys>", "knn_wide_select_kernel<128,keys>"}}};
+    pcc::ProfScope prof(kNames[L == 128][SRC == kSrcDiff ? 0 : SRC == kSrcRows ? 1 : 2][a.slices > 1], st);
     hipLaunchKernelGGL((knn_wide_select_kernel<L, SRC>), dim3(pcc::ceil_div(a.rows, kSelW), SRC == kSrcKeys ? 1 : a.slices),
                        dim3(64 * kSelW), 0, st, a);
 }

@@ -191,6 +191,25 @@ int pcc_profile_read(const char *kernel_prefix, double *avg_us, int *launches) {
     if (launches) *launches = n;
     return n ? PCC_OK : PCC_EINVAL;
 }
+size_t pcc_profile_names(char *buf, size_t capacity) {
+    std::lock_guard<std::mutex> lk(pcc::g_prof_mu);
+    std::vector<std::pair<std::string, int>> counts;  // in the order of each name's first launch
+    for (auto &r : pcc::g_prof) {
+        (void)hipEventSynchronize(r.b);
+        auto it = counts.begin();
+        while (it != counts.end() && it->first != r.name) ++it;
+        if (it == counts.end()) counts.emplace_back(r.name, 1);
+        else it->second++;
+    }
+    std::string text;
+    for (auto &c : counts) text += c.first + '\t' + std::to_string(c.second) + '\n';
+    if (buf && capacity) {
+        const size_t len = text.size() < capacity - 1 ? text.size() : capacity - 1;
+        std::memcpy(buf, text.data(), len);
+        buf[len] = '\0';
+    }
+    return text.size() + 1;
+}
 
 const char *pcc_version(void) { return "pcc_structural 0.1 (gfx950)"; }
 const char *pcc_last_error(void) { return t_msg; }

@@ -351,7 +351,13 @@ extern "C" int pcc_sinkhorn(int b, int n, int m, const float *x, const float *y,
         r.hout = gen[cur];
         r.average = t >= 0;
         {
-            pcc::ProfScope prof("sk_scan_kernel", st);
+            static const char *const kScanNames[] = {
+                "sk_scan_kernel S=1", "sk_scan_kernel S=2", "sk_scan_kernel S=3", "sk_scan_kernel S=4",
+                "sk_scan_kernel S=5", "sk_scan_kernel S=6", "sk_scan_kernel S=7", "sk_scan_kernel S=8",
+                "sk_scan_kernel S=9", "sk_scan_kernel S=10", "sk_scan_kernel S=11", "sk_scan_kernel S=12",
+                "sk_scan_kernel S=13", "sk_scan_kernel S=14", "sk_scan_kernel S=15", "sk_scan_kernel S=16"};  // (the slices the scans take)
+            static_assert(sizeof kScanNames / sizeof kScanNames[0] == kMaxSplit, "one profile name per slice count");
+            pcc::ProfScope prof(kScanNames[r.S - 1], st);
             hipLaunchKernelGGL(sk_scan_kernel<false>, grid, dim3(kRows), 0, st, r);
         }
         if (int rc = pcc::check_launch("sinkhorn(scan)")) return rc;

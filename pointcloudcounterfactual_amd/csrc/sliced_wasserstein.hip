@@ -241,8 +241,8 @@ __global__ __launch_bounds__(256) void sw_finish_kernel(int n, int p, int nchunk
 }
 
 template <int T, int E, bool REGS>
-void launch_slices(int b, bool grad, const Args &a, hipStream_t st) {
-    pcc::ProfScope prof("sw_slice_kernel", st);
+void launch_slices(const char *name, int b, bool grad, const Args &a, hipStream_t st) {
+    pcc::ProfScope prof(name, st);
     const dim3 grid((unsigned)a.nchunks, (unsigned)b), block(T);
     if (grad) hipLaunchKernelGGL((sw_slice_kernel<T, E, true, REGS>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((sw_slice_kernel<T, E, false, REGS>), grid, block, 0, st, a);
@@ -252,12 +252,19 @@ void launch_slices(int b, bool grad, const Args &a, hipStream_t st) {
 // product takes the first one that holds the cloud.  All of them return the same words.
 struct Variant {
     int capacity;
-    void (*launch)(int, bool, const Args &, hipStream_t);
+    void (*launch)(const char *, int, bool, const Args &, hipStream_t);
+    const char *name;  // the launch profile's: the instantiation, <threads,elements per thread>
 };
-const Variant kVariants[] = {{64, launch_slices<64, 1, true>},     {128, launch_slices<64, 2, true>},    {256, launch_slices<64, 4, true>},
-                             {512, launch_slices<128, 4, true>},   {1024, launch_slices<256, 4, true>},  {2048, launch_slices<512, 4, true>},
-                             {4096, launch_slices<1024, 4, true>}, {8192, launch_slices<1024, 8, false>}, {2048, launch_slices<256, 8, true>},
-                             {4096, launch_slices<512, 8, true>}};
+const Variant kVariants[] = {{64, launch_slices<64, 1, true>, "sw_slice_kernel<64,1>"},
+                             {128, launch_slices<64, 2, true>, "sw_slice_kernel<64,2>"},
+                             {256, launch_slices<64, 4, true>, "sw_slice_kernel<64,4>"},
+                             {512, launch_slices<128, 4, true>, "sw_slice_kernel<128,4>"},
+                             {1024, launch_slices<256, 4, true>, "sw_slice_kernel<256,4>"},
+                             {2048, launch_slices<512, 4, true>, "sw_slice_kernel<512,4>"},
+                             {4096, launch_slices<1024, 4, true>, "sw_slice_kernel<1024,4>"},
+                             {8192, launch_slices<1024, 8, false>, "sw_slice_kernel<1024,8>"},
+                             {2048, launch_slices<256, 8, true>, "sw_slice_kernel<256,8>"},
+                             {4096, launch_slices<512, 8, true>, "sw_slice_kernel<512,8>"}};
 constexpr int kNumVariants = (int)(sizeof kVariants / sizeof kVariants[0]);
 static_assert(PCC_SW_MAX_N == 8192, "the largest variant holds PCC_SW_MAX_N elements");
 
@@ -296,7 +303,7 @@ extern "C" int pcc_sliced_wasserstein(int b, int n, int p, const float *x, const
     int path = 0;
     while (kVariants[path].capacity < n) ++path;
     if (forced >= 1 && forced <= kNumVariants && kVariants[forced - 1].capacity >= n) path = forced - 1;
-    kVariants[path].launch(b, grad, a, st);
+    kVariants[path].launch(kVariants[path].name, b, grad, a, st);
     if (int rc = pcc::check_launch("sliced_wasserstein")) return rc;
     if (finish) {
         pcc::ProfScope prof("sw_finish_kernel", st);

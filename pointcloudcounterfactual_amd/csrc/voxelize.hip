@@ -479,7 +479,9 @@ int pcc_voxel_index(int b, int n, const float *xyz, int res, float lo, float ext
         while (npad < n) npad <<= 1;
         const int slots = npad / kSortThreads < 2 ? 2 : npad / kSortThreads;  // keys per thread: 2 up to 2048 keys, then 4, 8, 16
         hipError_t attr = hipSuccess;
-        pcc::ProfScope prof("vox_index_lds_kernel", st);
+        static const char *const kNames[] = {"vox_index_lds_kernel<2>", "vox_index_lds_kernel<4>",
+                                             "vox_index_lds_kernel<8>", "vox_index_lds_kernel<16>"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(slots) - 1], st);
         pcc::dispatch_cb<16>(slots, [&](auto E) {
             if constexpr (E >= 2) {
                 attr = pcc::allow_lds<vox_index_lds_kernel<E>>((size_t)padded(kMaxPoints) * sizeof(u64));
@@ -514,7 +516,7 @@ int pcc_voxelize(int b, int c, int n, int res, const float *x, const int32_t *ce
     const unsigned cblocks = grid_y(c, kCb);
     const bool wide = (bins & 3) == 0 && ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(grid)) & 15) == 0;
     {
-        pcc::ProfScope prof("vox_fwd_kernel", st);
+        pcc::ProfScope prof(wide ? "vox_fwd_kernel<4>" : "vox_fwd_kernel<1>", st);
         if (wide)
             hipLaunchKernelGGL(vox_fwd_kernel<4>, dim3((unsigned)pcc::ceil_div(bins / 4, kT), cblocks, (unsigned)b), dim3(kT), 0, st, c, n,
                                bins, x, order, counts, start, grid);
@@ -567,7 +569,9 @@ int pcc_devoxelize_bwd(int b, int c, int n, int res, float lo, float extent, con
     if (row <= kLdsRow) {
         const int cb = pcc::fit_cb(kCb, row, kLdsRow);  // 8 channels up to res = 16, 4 to 20, 2 to 25, 1 to 32
         hipError_t attr = hipSuccess;
-        pcc::ProfScope prof("devox_bwd_lds_kernel", st);
+        static const char *const kNames[] = {"devox_bwd_lds_kernel<1>", "devox_bwd_lds_kernel<2>",
+                                             "devox_bwd_lds_kernel<4>", "devox_bwd_lds_kernel<8>"};
+        pcc::ProfScope prof(kNames[pcc::cb_index(cb)], st);
         pcc::dispatch_cb<kCb>(cb, [&](auto CB) {
             attr = pcc::allow_lds<devox_bwd_lds_kernel<CB>>(kLdsRow);
             if (attr == hipSuccess)

@@ -196,3 +196,33 @@ class GroupedGradX:
 
     def check_bound(self, gx):
         assert self.ratio(gx) <= 1.0
+
+
+# ---- which kernels a call runs (include/pcc_test_hooks.h, interp_path), as exact launch-profile names ----
+TILE_WORDS = 1024 + 512  # words of LDS per channel the forward stages its tile of list rows in, beside the rows of x
+
+
+def fwd_kernel(b, c, n, forced=0):
+    from tests.list_plan_reference import kernel_of
+
+    return kernel_of('agg_fwd_kernel', b, c, n, forced, tile_words=TILE_WORDS)
+
+
+def bwd_kernels(b, c, n, want, cus, forced=0):
+    """The kernels of ``pcc_aggregate_points_bwd`` for ``want = (grad_x, grad_w, grad_rel)`` on a device of ``cus`` compute
+    units.  grad_x: the plan of the list ops, its channel block halved while the LDS bins leave compute units idle; grad_rel
+    rides along unless those bins tie the launch to fewer workgroups than compute units -- it then, and where grad_x is not
+    asked for, takes a launch of the direct kernel of its own."""
+    from tests.list_plan_reference import kernel_of, plan
+
+    names = set()
+    if want[0]:
+        path, cb = plan(b, c, n, forced, spread_cus=cus)
+        names.add(kernel_of('agg_bwd_kernel', b, c, n, forced, spread_cus=cus))
+        if want[2] and path == 'lds' and b * -(-c // cb) < cus:
+            names.add('agg_bwd_kernel<direct>')
+    elif want[2]:
+        names.add('agg_bwd_kernel<direct>')
+    if want[1]:
+        names.add('agg_bwd_w_kernel')
+    return names

@@ -115,3 +115,14 @@ class BallReference:
             fill = (got[0] if c else 0) if pad == 'first' else -1
             assert (idx[bi, qi, c:] == fill).all(), (bi, qi, 'padding')
         return int(amb_rows.sum())
+
+
+# The kernel variants of pcc_ball_query (include/pcc_test_hooks.h, ball_path): value -> exact
+# launch-profile name.  1, 2: candidates from global memory, 4 / 16 queries (one wave each) per workgroup; 3, 4: candidates
+# staged through LDS, 4 queries x tiles of 1024 / 16 queries x tiles of 4096.  Every size takes PRODUCT.
+VARIANTS = {1: 'ball_direct_kernel<4>', 2: 'ball_direct_kernel<16>', 3: 'ball_lds_kernel<4,1024>', 4: 'ball_lds_kernel<16,4096>'}
+PRODUCT = 4
+
+
+def kernel_of(forced=0):
+    return VARIANTS[forced or PRODUCT]

@@ -101,3 +101,19 @@ def generic_cloud(seed, b, n, kind):
 
 
 GENERIC_KINDS = ('uniform', 'gauss', 'uniform_x100', 'gauss_x100', 'uniform_x1e-3', 'gauss_x1e-3', 'uniform_+50', 'gauss_+50')
+
+
+# The kernel variants of pcc_fps (include/pcc_test_hooks.h, fps_path): value -> (exact launch-profile
+# name, points the variant holds).  Six register variants (block, P) of capacity block * P, smallest first, then the
+# memory path for any n.
+VARIANTS = {1: ('fps_reg_kernel<64,4>', 256), 2: ('fps_reg_kernel<256,4>', 1024), 3: ('fps_reg_kernel<256,8>', 2048),
+            4: ('fps_reg_kernel<512,8>', 4096), 5: ('fps_reg_kernel<1024,8>', 8192), 6: ('fps_reg_kernel<1024,16>', 16384),
+            7: ('fps_mem_kernel', None)}
+
+
+def kernel_of(n, forced=0):
+    """The kernel a cloud of ``n`` points runs: the product takes the first variant that holds the cloud; a forced
+    variant that cannot hold it is ignored."""
+    if forced and (VARIANTS[forced][1] is None or VARIANTS[forced][1] >= n):
+        return VARIANTS[forced][0]
+    return next(name for name, cap in VARIANTS.values() if cap is None or cap >= n)

@@ -19,6 +19,24 @@ CB, LONG_RUN, SCAN_THREADS, LDS_MAX_N, LDS_MAX_BWD_M = 8, 64, 1024, 40000, 20000
 LDS_ROWS_N = {8: 2048, 4: 4096, 2: 8192}
 
 
+def _rows(words):
+    """Rows of ``words`` floats a workgroup stages: 8, 4 or 2 while they fit 64 KB (LDS_ROWS_N), one above."""
+    return next((cb for cb in (8, 4, 2) if words <= LDS_ROWS_N[cb]), 1)
+
+
+def pool_kernels(n):
+    """The exact launch-profile names of ``pcc_segment_pool`` on clouds of n points: the LDS kernel in its rows-per-workgroup
+    instantiation up to LDS_MAX_N, the gathering kernel above; the long-run kernel is launched wherever a run can be longer
+    than LONG_RUN (n > LONG_RUN)."""
+    names = {f'seg_pool_lds_kernel<{_rows(n)}>' if n <= LDS_MAX_N else 'seg_pool_kernel'}
+    return names | ({'seg_long_kernel'} if n > LONG_RUN else set())
+
+
+def pool_bwd_kernel(m, mode):
+    """... of ``pcc_segment_pool_bwd`` with m slots: rows of m gradients (and m indices, for max)."""
+    return f'seg_pool_bwd_lds_kernel<{_rows(m * (2 if mode == MAX else 1))}>' if m <= LDS_MAX_BWD_M else 'seg_pool_bwd_kernel'
+
+
 def grid_cluster(cell, order, m):
     """``(cluster[b,n], seg[b,m+1], count[b])`` int32 from ``pcc_voxel_index``'s ``cell`` and ``order``."""
     b, n = cell.shape

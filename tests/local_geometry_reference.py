@@ -21,6 +21,12 @@ N_GRID = (1, 3, 64, 1025)
 B_MAX = 3
 # n on both sides of the one boundary the dispatch has in n: the backward's LDS bins hold 8192 points
 BOUNDARIES = (8192, 8193)
+LDS_MAX_N = 8192  # 12 n bytes of bins in the backward's 96 KB of LDS
+
+
+def bwd_kernel(n):
+    """The exact launch-profile name of pcc_local_covariance_bwd's kernel: LDS bins while a sample's fit, global atomics above."""
+    return 'local_covariance_bwd_kernel<lds>' if n <= LDS_MAX_N else 'local_covariance_bwd_kernel<direct>'
 
 
 def cloud(seed, n, b=B_MAX, scale=1.0, shift=0.0):

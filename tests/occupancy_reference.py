@@ -150,3 +150,18 @@ def generic_case(kind, seed, clouds, n, res, in_sphere):
     for a in (points, expected):
         a.setflags(write=False)
     return points, expected, 1.0 - keep / n
+
+
+# ---- which kernels a call runs (include/pcc_structural.h; include/pcc_test_hooks.h, occupancy_path), exact profile names ----
+LDS_MAX_RES = 32  # res^3 int32 counters fit the LDS histogram's 128 KB up to here
+
+
+def kernels_of(res, in_sphere, per_cloud, forced=0):
+    """The LDS-histogram kernel (per cloud / whole set) wherever res^3 counters fit a workgroup's LDS, the global-atomic
+    kernel otherwise; occupancy_path = 1 forces the global path, 2 the LDS path -- ignored where the counters do not fit
+    (res > 32).  With in_sphere the deferred points take one more pass, the fallback kernel."""
+    if res <= LDS_MAX_RES and forced != 1:
+        names = {'occ_lds_kernel(per cloud)' if per_cloud else 'occ_lds_kernel(set)'}
+    else:
+        names = {'occ_global_kernel'}
+    return names | ({'occ_fallback_kernel'} if in_sphere else set())

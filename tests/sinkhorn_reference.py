@@ -119,3 +119,27 @@ class Result:
         for key, bar in (('pot', BAR_POT), ('cost', BAR_COST), ('grad', BAR_GRAD)):
             assert mult.get(key, 0.0) <= bar, (what, key, mult)
         return mult
+
+
+# ---- how many column slices a call's scans take (include/pcc_test_hooks.h, sinkhorn_split) ----
+MAX_SPLIT, TILE, GROUP = 16, 256, 8
+
+
+def slices(n, m, debias=True, forced=0):
+    """The slices S the launch-profile name of the scans carries ("sk_scan_kernel S=..."): the allowance is the forced value
+    (16 at the most), or by the row count (n + m, twice that with debias) the power of two that brings rows x slices to
+    4096 waves' worth (262144), 16 at the most; a scan over c columns then takes ceil(c / chunk) slices of chunk = the
+    columns over the allowance rounded up to whole groups of 8, none shorter than a 256-column tile; S is the most any scan
+    takes (the scans run over n and over m columns)."""
+    if forced >= 1:
+        allow = min(forced, MAX_SPLIT)
+    else:
+        rows, allow = (n + m) * (2 if debias else 1), 1
+        while allow < MAX_SPLIT and rows * allow < 4096 * 64:
+            allow *= 2
+    taken = [-(-cols // max(TILE, -(-(-(-cols // allow)) // GROUP) * GROUP)) for cols in (n, m)]
+    return max(taken)
+
+
+def scan_kernel(n, m, debias=True, forced=0):
+    return f'sk_scan_kernel S={slices(n, m, debias, forced)}'

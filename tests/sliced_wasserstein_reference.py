@@ -13,6 +13,17 @@ U = 2.0 ** -24  # unit roundoff of float32
 CHUNK = 8       # PCC_SW_CHUNK: projections per workgroup
 # how many points variant v = 1 .. 10 of the sw_path switch holds (include/pcc_test_hooks.h)
 VARIANT_CAPACITY = (64, 128, 256, 512, 1024, 2048, 4096, 8192, 2048, 4096)
+# ... and its (threads, elements per thread), which its exact launch-profile name carries
+VARIANT_SHAPE = ((64, 1), (64, 2), (64, 4), (128, 4), (256, 4), (512, 4), (1024, 4), (1024, 8), (256, 8), (512, 8))
+assert all(t * e == cap for (t, e), cap in zip(VARIANT_SHAPE, VARIANT_CAPACITY))
+
+
+def kernel_of(n, forced=0):
+    """The slice kernel a cloud of ``n`` points runs: the product takes the first variant that holds
+    the cloud; a forced variant that cannot hold it is ignored."""
+    v = forced - 1 if forced and VARIANT_CAPACITY[forced - 1] >= n else next(i for i, cap in enumerate(VARIANT_CAPACITY) if cap >= n)
+    return 'sw_slice_kernel<%d,%d>' % VARIANT_SHAPE[v]
+
 
 # The grid of the forward tests.  n: the sizes the issue names -- they hold both sides of every power of two from 64 to
 # 2048, where the kernel changes its thread count or its elements per thread -- and 4097, 8191 for the last two changes

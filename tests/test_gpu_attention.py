@@ -12,17 +12,32 @@ import pytest
 import torch
 
 from tests import attention_reference as ref
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ('random', 'knn_cross', 'ball_none', 'ball_first')
 
 
+_PATH = [0]  # the interp_path value in force: every aggregate call below asserts the kernels the plan predicts under it
+
+
 def _forced(path, fn):
+    """``fn()`` under interp_path = ``path``.  ``_fwd`` and ``_bwd`` assert from their launch records that the forced
+    variant ran and its sibling did not; a forced LDS path that cannot hold a row (and, forward, its tile) is ignored
+    (include/pcc_test_hooks.h): the plan then predicts the direct kernel, the product's choice."""
     from pointcloudcounterfactual_amd import _lib
 
     with _lib.tuning('interp_path', path):
-        return fn()
+        _PATH[0] = path
+        try:
+            return fn()
+        finally:
+            _PATH[0] = 0
 
 
 def _p(t):
@@ -62,7 +77,9 @@ def _fwd(x, idx, w, rel=None):
     b, c, n = x.shape
     g, m, k = w.shape[1:]
     out = _nan((b, c, m), x.device)
-    _lib.call(_lib.lib.pcc_aggregate_points, 'aggregate_points', x.device, b, c, g, n, m, k, _p(x), _p(idx), _p(w), _p(rel), _p(out))
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_aggregate_points, 'aggregate_points', x.device, b, c, g, n, m, k, _p(x), _p(idx),
+                                     _p(w), _p(rel), _p(out)))
+    assert names == ({ref.fwd_kernel(b, c, n, _PATH[0]): 1} if b and m else {}), (n, _PATH[0], names)
     return out.cpu().numpy()
 
 
@@ -77,8 +94,11 @@ def _bwd(x, idx, w, rel, go, n, want=(True, True, True)):
     gx = _nan((b, c, n), dev) if want[0] else None
     gw = _nan((b, g, m, k), dev) if want[1] else None
     gr = _nan((b, c, m, k), dev) if want[2] else None
-    _lib.call(_lib.lib.pcc_aggregate_points_bwd, 'aggregate_points_bwd', dev, b, c, g, n, m, k, _p(x), _p(idx), _p(w), _p(rel), _p(go),
-              _p(gx), _p(gw), _p(gr))
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_aggregate_points_bwd, 'aggregate_points_bwd', dev, b, c, g, n, m, k, _p(x), _p(idx),
+                                     _p(w), _p(rel), _p(go), _p(gx), _p(gw), _p(gr)))
+    if b and m:
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        assert set(names) == ref.bwd_kernels(b, c, n, want, cus, _PATH[0]), (n, want, _PATH[0], names)
     return tuple(None if t is None else t.cpu().numpy() for t in (gx, gw, gr))
 
 

@@ -8,8 +8,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests.ball_query_reference import GENERIC_KINDS, GENERIC_SHAPES, BallReference, between_lattice, generic_cloud
+from tests.ball_query_reference import GENERIC_KINDS, GENERIC_SHAPES, BallReference, between_lattice, generic_cloud, kernel_of
 from tests.fps_reference import lattice_cloud
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +40,14 @@ def _ball(x, c, radius, nsample, pad, count=True):
 
 
 def _forced(path, fn):
+    """``fn()`` under ball_path = ``path`` (0: the product's choice), once its launch record holds the kernel of that
+    variant and nothing else."""
     from pointcloudcounterfactual_amd import _lib
 
     with _lib.tuning('ball_path', path):
-        return fn()
+        got, names = ran(fn)
+    assert set(names) == {kernel_of(path)}, (path, names)
+    return got
 
 
 def _lattice_centres(seed, x, m, between):
@@ -100,7 +109,7 @@ def test_every_variant_gives_the_same_words(cuda, n):
             xs, cs = torch.from_numpy(x).to(cuda), torch.from_numpy(c).to(cuda)
             for radius in (0.125, 0.2, 10.0):
                 for nsample, pad in ((1, 'none'), (31, 'first'), (200, 'first'), (200, 'none')):
-                    base = _ball(xs, cs, radius, nsample, pad)
+                    base = _forced(0, lambda: _ball(xs, cs, radius, nsample, pad))
                     ref.check_exact(radius, nsample, pad, *base)
                     for path in PATHS:
                         got = _forced(path, lambda: _ball(xs, cs, radius, nsample, pad))

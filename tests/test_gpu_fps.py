@@ -7,12 +7,26 @@ import numpy as np
 import pytest
 import torch
 
-from tests.fps_reference import GENERIC_KINDS, check_validity, fps_reference, generic_cloud, lattice_cloud
+from tests.fps_reference import GENERIC_KINDS, VARIANTS, check_validity, fps_reference, generic_cloud, kernel_of, lattice_cloud
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 # fps_path values (include/pcc_test_hooks.h) -> points the variant holds (7: the memory path, any n)
 CAPACITY = {1: 256, 2: 1024, 3: 2048, 4: 4096, 5: 8192, 6: 16384, 7: None}
+assert CAPACITY == {path: cap for path, (_, cap) in VARIANTS.items()}
+
+
+def _fps_on(kernel, x, m, cuda, start=None):
+    """``_fps`` once its launch record is ``kernel`` twice (the call with and the call without the distance output) and
+    nothing else: the variant named ran, and no sibling."""
+    got, names = ran(lambda: _fps(x, m, cuda, start))
+    assert names == {kernel: 2}, (kernel, names)
+    return got
 
 
 def _fps(x, m, cuda, start=None):
@@ -59,22 +73,24 @@ BOUNDARIES = sorted({65, 1025, 2049} | {c + d for c in CAPACITY.values() if c fo
 @pytest.mark.parametrize('n', BOUNDARIES)
 def test_every_path_gives_the_same_bits(cuda, n):
     """Every (block, P) variant that holds n and the memory path against the product's choice, at the sizes just below, at
-    and above every capacity of the table; the product's choice itself against the reference."""
+    and above every capacity of the table; the product's choice itself against the reference.  Each call's launch record
+    proves the variant: the first that holds n for the product, the forced one where it holds n, and -- a forced variant
+    that cannot hold n is ignored (include/pcc_test_hooks.h) -- the product's choice again where it does not."""
     from pointcloudcounterfactual_amd import _lib
 
     for levels in (4, 16):
         x = lattice_cloud(77 * levels + n, 2, n, levels)
         start = np.array([n - 1, n // 2])
         for m in sorted({min(2, n), min(n, 200), n // 3}):
-            base = _fps(x, m, cuda, start)
+            base = _fps_on(kernel_of(n), x, m, cuda, start)
             if m <= 200:
                 ref_idx, ref_dist = fps_reference(x, m, start)
                 assert np.array_equal(base[0], ref_idx) and _same_bits(base[1], ref_dist)
             for path, cap in CAPACITY.items():
-                if cap is not None and cap < n:
-                    continue
+                ignored = cap is not None and cap < n
+                assert kernel_of(n, path) == (kernel_of(n) if ignored else VARIANTS[path][0])
                 with _lib.tuning('fps_path', path):
-                    got = _fps(x, m, cuda, start)
+                    got = _fps_on(kernel_of(n, path), x, m, cuda, start)
                 assert np.array_equal(got[0], base[0]) and _same_bits(got[1], base[1]), (levels, m, path)
 
 
@@ -132,9 +148,9 @@ def test_non_finite_points_are_excluded(cuda):
     # every variant keeps them out
     from pointcloudcounterfactual_amd import _lib
 
-    for path in CAPACITY:
+    for path in CAPACITY:  # (n = 257: variant 1 cannot hold it and is ignored)
         with _lib.tuning('fps_path', path):
-            got = _fps(x, m, cuda, start)
+            got = _fps_on(kernel_of(n, path), x, m, cuda, start)
         assert np.array_equal(got[0], ref_idx) and _same_bits(got[1], ref_dist), path
 
 

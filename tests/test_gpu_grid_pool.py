@@ -9,6 +9,11 @@ import torch
 
 from tests import grid_pool_reference as ref
 from tests import voxel_reference as vref
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -77,7 +82,9 @@ def _pool(x, order, seg, mode, with_arg=True):
     b, c, n = x.shape
     m = seg.shape[1] - 1
     out, arg = _Out((b, c, m), torch.float32, x.device), _Out((b, c, m), torch.int32, x.device)
-    _call('segment_pool', x.device, b, c, n, m, mode, x.data_ptr(), order.data_ptr(), seg.data_ptr(), out.ptr(), arg.ptr() if with_arg else None)
+    _, names = ran(lambda: _call('segment_pool', x.device, b, c, n, m, mode, x.data_ptr(), order.data_ptr(), seg.data_ptr(), out.ptr(),
+                                 arg.ptr() if with_arg else None))
+    assert set(names) == (ref.pool_kernels(n) if b else set()), (n, names)  # (the variant the size predicts, no sibling)
     written = mode == ref.MAX and with_arg
     return out.numpy(), arg.numpy(untouched=not written)
 
@@ -85,8 +92,9 @@ def _pool(x, order, seg, mode, with_arg=True):
 def _pool_bwd(g, cluster, seg, arg, mode, n):
     b, c, m = g.shape
     gx = _Out((b, c, n), torch.float32, g.device)
-    _call('segment_pool_bwd', g.device, b, c, n, m, mode, cluster.data_ptr(), seg.data_ptr(), None if arg is None else arg.data_ptr(),
-          g.data_ptr(), gx.ptr())
+    _, names = ran(lambda: _call('segment_pool_bwd', g.device, b, c, n, m, mode, cluster.data_ptr(), seg.data_ptr(),
+                                 None if arg is None else arg.data_ptr(), g.data_ptr(), gx.ptr()))
+    assert set(names) == ({ref.pool_bwd_kernel(m, mode)} if b else set()), (m, mode, names)
     return gx.numpy()
 
 

@@ -19,6 +19,10 @@ from tests import grid_ragged_reference as G
 from tests import ragged_reference as R
 from tests import unaligned_views as U
 from tests import unaligned_views_grid_ragged  # noqa: F401  (registers the entry point's case before the registry suites read it)
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -183,7 +187,13 @@ def _pool_case(kind):
 @pytest.mark.parametrize('kind', ['one_cell', (40000, 20000), (40001, 20001)], ids=['one_cell', 'lds', 'global'])
 def test_grid_pool_ragged_device_against_cpu(cuda, kind):
     """Index words, pooled mean / sum / max and the gradients of the features and of ``xyz``, word for word: the sums run in
-    ascending point index on both sides, and ``pcc_segment_pool_bwd`` is a gather."""
+    ascending point index on both sides, and ``pcc_segment_pool_bwd`` is a gather.  The launch record of the device side
+    proves the side of ``segment_pool``'s LDS limits the case names: rows of n points staged in LDS up to 40000 and gathered
+    above, rows of m slots for the backward up to 20000 (tests/grid_pool_reference.py)."""
+    from pointcloudcounterfactual_amd import _lib
+    from tests import grid_pool_reference as pref
+    from tests.which_ran import family
+
     ops = _ops()
     i, m = _pool_case(kind)
     n, c = len(i['xyz']), 3
@@ -194,12 +204,16 @@ def test_grid_pool_ragged_device_against_cpu(cuda, kind):
         for dev in ('cpu', cuda):
             to = (lambda a: torch.from_numpy(a)) if dev == 'cpu' else (lambda a: _dev(a, cuda))
             xyz, f = to(i['xyz']).requires_grad_(True), to(feats).requires_grad_(True)
-            out = ops.grid_pool_ragged(xyz, f, to(i['offset']), i['size'], reduce, start=to(i['start']), m=m, axis_bits=i['axis_bits'])
-            u = int(out.grid.count)
-            assert kind == 'one_cell' or u >= m
-            keep = min(u, m)
-            ((out.features * to(w)).sum() + (out.xyz[:keep] * to(v)[:keep]).sum()).backward()
+            with _lib.profile() as read:  # (the CPU side records nothing)
+                out = ops.grid_pool_ragged(xyz, f, to(i['offset']), i['size'], reduce, start=to(i['start']), m=m, axis_bits=i['axis_bits'])
+                u = int(out.grid.count)
+                assert kind == 'one_cell' or u >= m
+                keep = min(u, m)
+                ((out.features * to(w)).sum() + (out.xyz[:keep] * to(v)[:keep]).sum()).backward()
+                pools = set(family(read.exact(), 'seg_')) if dev == cuda else None
             res.append([*out.grid.index, out.grid.coord, out.offset, out.xyz.detach(), out.features.detach(), f.grad, xyz.grad,
                         ops.grid_unpool_ragged(out.features.detach(), out.grid)])
+        mode = pref.MODES[reduce]
+        assert pools == pref.pool_kernels(n) | {pref.pool_bwd_kernel(m, pref.MEAN), pref.pool_bwd_kernel(m, mode)}, (kind, reduce, pools)
         for a, b in zip(*res):
             assert b.device == cuda and U.same_words(a, b), reduce

@@ -9,17 +9,33 @@ import pytest
 import torch
 
 from tests import grouping_reference as ref
+from tests.list_plan_reference import kernel_of
+from tests.which_ran import assert_only, ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -1234.5  # what the channels outside a call's slice must keep
 
 
+_PATH = [0]  # the group_path value in force: every call below asserts the kernel the plan predicts under it
+
+
 def _forced(path, fn):
+    """``fn()`` under group_path = ``path``.  ``_fwd`` and ``_bwd`` assert from their launch records that the forced
+    variant ran and its sibling did not; a forced LDS path that cannot hold a row is ignored (include/pcc_test_hooks.h):
+    the plan then predicts the direct kernel, the product's choice."""
     from pointcloudcounterfactual_amd import _lib
 
     with _lib.tuning('group_path', path):
-        return fn()
+        _PATH[0] = path
+        try:
+            return fn()
+        finally:
+            _PATH[0] = 0
 
 
 def _p(t):
@@ -36,8 +52,9 @@ def _fwd(x, idx, centre, point_major, out_c=None, out_c0=0):
     m, k = idx.shape[1:]
     out_c = c if out_c is None else out_c
     out = torch.full((b, out_c, m, k), SENTINEL, dtype=torch.float32, device=x.device)
-    _lib.call(_lib.lib.pcc_group_points, 'group_points', x.device, b, c, n, m, k, int(point_major), _p(x), _p(idx), _p(centre),
-              _p(out), out_c, out_c0)
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_group_points, 'group_points', x.device, b, c, n, m, k, int(point_major), _p(x),
+                                     _p(idx), _p(centre), _p(out), out_c, out_c0))
+    assert names == ({kernel_of('group_fwd_kernel', b, c, n, _PATH[0]): 1} if b and m else {}), (n, _PATH[0], names)
     out = out.cpu().numpy()
     rest = np.delete(out, np.s_[out_c0:out_c0 + c], axis=1)
     assert (rest == np.float32(SENTINEL)).all()
@@ -52,8 +69,11 @@ def _bwd(idx, g, n, c, point_major, out_c0=0, want_x=True, want_c=True):
     b, out_c, m, k = g.shape
     gx = torch.full((b, n, c) if point_major else (b, c, n), float('nan'), device=g.device) if want_x else None
     gc = torch.full((b, m, c) if point_major else (b, c, m), float('nan'), device=g.device) if want_c else None
-    _lib.call(_lib.lib.pcc_group_points_bwd, 'group_points_bwd', g.device, b, c, n, m, k, int(point_major), _p(idx), _p(g), out_c,
-              out_c0, _p(gx), _p(gc))
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_group_points_bwd, 'group_points_bwd', g.device, b, c, n, m, k, int(point_major),
+                                     _p(idx), _p(g), out_c, out_c0, _p(gx), _p(gc)))
+    if b and m:
+        assert_only(names, [kernel_of('group_bwd_kernel', b, c, n, _PATH[0])] if want_x else [], 'group_bwd_kernel')
+        assert ('group_centre_bwd_kernel' in names) == want_c, names
     back = lambda t: None if t is None else ref.to_layout(t.cpu().numpy(), point_major)  # noqa: E731
     return back(gx), back(gc)
 

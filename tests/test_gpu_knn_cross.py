@@ -8,6 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -165,21 +170,34 @@ def test_knn_cross_non_finite_values(cuda, oracle_mod):
 @pytest.mark.parametrize('b,nq,n', [(1, 5, 20000), (2, 64, 3000)])
 @pytest.mark.parametrize('c', [3, 64])
 def test_knn_cross_split_is_invisible(cuda, b, nq, n, c):
+    """... and the launch record shows that the switch acts: the selection kernel of (k, c) alone where the slices the rule
+    of tests/knn_reference.py predicts are 1, its "sliced" launch and the merge launch where they are more.  (The record
+    tells one slice from several, not how many: the count is an argument of the kernel, not an instantiation.)"""
     from pointcloudcounterfactual_amd import _lib
     from pointcloudcounterfactual_amd import neighbour_ops as ops
+    from tests import knn_reference as kr
+    from tests.which_ran import assert_only, ran
+
+    def selection(k, forced):
+        cus = torch.cuda.get_device_properties(cuda).multi_processor_count
+        sliced = kr.cross_slices(b * nq, n, cus, forced) > 1  # (both shapes: one launch over all b * nq rows)
+        return {kr.wide_select(c, k, sliced)} | ({kr.wide_merge(k)} if sliced else set())
 
     q, x = _cloud(nq + c, b, c, nq).to(cuda), _cloud(n + c, b, c, n).to(cuda)
     for k in (16, 128):
-        auto = ops.hip_knn_cross(q, x, k, return_distance=True)
+        auto, names = ran(lambda: ops.hip_knn_cross(q, x, k, return_distance=True))
+        assert_only(names, selection(k, 0), 'knn_wide_select_kernel')
         for s in (1, 2, 7, 16):
             with _lib.tuning('knn_cross_split', s):
-                idx, dist = ops.hip_knn_cross(q, x, k, return_distance=True)
+                (idx, dist), names = ran(lambda: ops.hip_knn_cross(q, x, k, return_distance=True))
+            assert_only(names, selection(k, s), 'knn_wide_select_kernel')
             assert torch.equal(idx, auto[0]), (k, s)
             assert torch.equal(dist, auto[1]), (k, s)
         assert idx.min() >= 0 and idx.max() < n
 
 
-@pytest.mark.parametrize('nq,n,c,k', [(64, 200000, 3, 20), (640, 120000, 8, 64), (128, 50000, 64, 128)])
+@pytest.mark.parametrize('nq,n,c,k', [(64, 200000, 3, 20), (640, 120000, 8, 64), (128, 50000, 64, 128),
+                                       (5, 20000, 3, 128)])  # (the last: the 128-slot selection on difference-form distances, sliced)
 def test_knn_cross_large_shapes_against_float64(cuda, nq, n, c, k):
     """Too large for the oracle: float64 distances on the device.  An entry may differ from the float64 list only as a
     certified near tie, |d64[got] - d64[expected]| <= 4 (c + 2) eps32 (|q|^2 + |x|^2), and at most 0.1 % of the entries."""

@@ -13,7 +13,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import knn_reference as kr
 from tests import knn_stress_clouds as sc
+from tests.which_ran import assert_only
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +60,8 @@ def _case(kind, c, n, seed=11):
 
 @contextlib.contextmanager
 def _launches():
-    """Counts of the launches inside the body, by kernel-name prefix: ``counts(name)`` after the body."""
+    """Counts of the launches inside the body, by kernel-name prefix: ``counts(name)`` after the body; ``counts.exact``:
+    the exact launch record."""
     from pointcloudcounterfactual_amd import _lib
 
     got = {}
@@ -67,6 +74,7 @@ def _launches():
         torch.cuda.synchronize()
         for name in ('knn_mfma_kernel', 'knn_mfma_split_kernel', 'knn_wide_select_kernel', 'knn_sorted_kernel', 'knn_small_kernel'):
             got[name] = read(name)[1]
+        counts.exact = read.exact()
 
 
 def _knn(xd, k, switch):
@@ -80,6 +88,14 @@ def _knn(xd, k, switch):
             idx = ops.knn(xd, k)
     assert counts(ran) >= 1, (switch, ran)
     assert all(counts(name) == 0 for name in idle), (switch, idle)
+    # ... and the instantiation: the list width and the padded channel count of this call
+    b, c, n = xd.shape
+    forced = {tune[0]: tune[1]} if tune else {}
+    exact = kr.kernel_of(b, c, n, k, torch.cuda.get_device_properties(xd.device).multi_processor_count,
+                         nosplit=forced.get('knn_nosplit', 0), wide=forced.get('knn_wide', 0))
+    assert exact.startswith(ran), (exact, ran)
+    assert_only(counts.exact, exact, 'knn_sorted_kernel', 'knn_small_kernel', 'knn_mfma_kernel', 'knn_mfma_split_kernel',
+                'knn_wide_select_kernel')  # (the self search never slices: no merge launch either)
     return idx
 
 
@@ -113,6 +129,20 @@ def test_knn_stress_every_kernel_matches_the_oracle(cuda, oracle_mod, kind, c):
         xd = _t(x).to(cuda)
         for switch in SWITCHES:
             for k in KS + EXTRA_KS.get(kind, ()):
+                _assert_lists(_knn(xd, k, switch), exp[:, :, :k], f'{kind} c={c} n={n} k={k} {switch}')
+
+
+@pytest.mark.parametrize('c', (4, 9, 17, 33, 65))
+def test_knn_every_instantiation_matches_the_oracle(cuda, oracle_mod, c):
+    """Every (list width, padded channel count) instantiation of the two MFMA kernels -- k at the top of every slot class
+    and one above the class below, c one above every padded count -- forced through knn_nosplit, proven by the launch
+    record (``_knn``) and held to the oracle's lists."""
+    for kind, n in (('gauss', 300), ('twins', 130)):
+        x, dm = _case(kind, c, n)
+        exp = sc.expected_lists(dm, 32)
+        xd = _t(x).to(cuda)
+        for k in (1, 4, 5, 8, 9, 16, 17, 20, 21, 25, 26, 32):
+            for switch in ('mfma', 'split'):
                 _assert_lists(_knn(xd, k, switch), exp[:, :, :k], f'{kind} c={c} n={n} k={k} {switch}')
 
 
@@ -190,8 +220,11 @@ def test_knn_stress_cross_of_two_clouds(cuda, oracle_mod, kind, c):
             want = _expected_dist(dm, exp)
             ok = ~np.isnan(want)
             for split in (0, 1, 2, 7) if kind in ('twins', 'overflow') else (0,):
-                with _lib.tuning('knn_cross_split', split):
+                with _lib.tuning('knn_cross_split', split), _launches() as counts:
                     idx, dist = ops.hip_knn_cross(qd, xd, k, return_distance=True)
+                # one launch over the 2 x 45 queries; unforced, n <= 300 < 2048 candidates never slices
+                sliced = kr.cross_slices(2 * nq, n, torch.cuda.get_device_properties(cuda).multi_processor_count, split) > 1
+                assert_only(counts.exact, {kr.wide_select(c, k, sliced)} | ({kr.wide_merge(k)} if sliced else set()), 'knn_wide_select_kernel')
                 _assert_lists(idx, exp, f'cross {kind} c={c} n={n} k={k} split={split}')
                 dist = dist.cpu().numpy()
                 assert np.array_equal(np.isnan(dist), ~ok), (kind, c, n, k, split)
@@ -260,10 +293,13 @@ def test_knn_stress_difference_form_overflow(cuda, oracle_mod, c, n, stride, ker
         with _launches() as counts:
             idx = ops.knn(xd, k)
         assert counts(kernel) >= 1 and counts('knn_wide_select_kernel') == 0
+        assert kr.kernel_of(b, c, n, k).startswith(kernel + '<')
+        assert_only(counts.exact, kr.kernel_of(b, c, n, k), *kr.FAMILIES)
         _assert_lists(idx[:, ::stride], exp[:, ::stride, :k], f'diff overflow c={c} n={n} k={k} {kernel}')
         with _launches() as counts, _lib.tuning('knn_wide', 1):
             idx = ops.knn(xd, k)
         assert counts('knn_wide_select_kernel') >= 1 and counts(kernel) == 0
+        assert_only(counts.exact, kr.wide_select(c, k), *kr.FAMILIES)  # (c <= 3: no distance kernel)
         _assert_lists(idx[:, ::stride], exp[:, ::stride, :k], f'diff overflow c={c} n={n} k={k} wide')
         if n <= 3000:
             idx, dist = ops.hip_knn_cross(xd, xd, k, return_distance=True)

@@ -5,6 +5,11 @@ import numpy as np
 import pytest
 import torch
 
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 
@@ -84,9 +89,16 @@ def test_knn_wide_degenerate_clouds(cuda, oracle_mod):
         same = torch.full((2, c, 100), 0.25)
         assert (_knn(same, 40, cuda) == np.arange(40)[None, None, :]).all(), c
     one = torch.rand(3, 3, 1)
-    with _lib.tuning('knn_wide', 1):
-        assert (_knn(one, 1, cuda) == 0).all()
-        assert (_knn(torch.rand(2, 9, 1), 1, cuda) == 0).all()
+    from tests import knn_reference as kr
+    from tests.which_ran import assert_only, ran
+
+    with _lib.tuning('knn_wide', 1):  # (n = 1 launches too: the selection kernel, and the distance kernel where c > 3)
+        got, names = ran(lambda: _knn(one, 1, cuda))
+        assert_only(names, kr.wide_select(3, 1), *kr.FAMILIES)
+        assert (got == 0).all()
+        got, names = ran(lambda: _knn(torch.rand(2, 9, 1), 1, cuda))
+        assert_only(names, {kr.wide_select(9, 1), 'knn_wide_dist_kernel'}, *kr.FAMILIES)
+        assert (got == 0).all()
     for c, oracle in ((3, oracle_mod.knn_diff), (200, oracle_mod.knn_expanded)):
         x = _cloud(5 + c, 2, c, 200)
         x[0, 1, 17] = float('nan')
@@ -108,10 +120,16 @@ def test_knn_wide_switch_matches_the_existing_kernels(cuda, b, c, n, k):
     """The test switch sends calls the existing kernels handle through the wide path: the same bits."""
     from pointcloudcounterfactual_amd import _lib
 
+    from tests import knn_reference as kr
+    from tests.which_ran import assert_only, ran
+
+    cus = torch.cuda.get_device_properties(cuda).multi_processor_count
     x = _cloud(b * 13 + c + n + k, b, c, n)
-    ref = _knn(x, k, cuda)
+    ref, names = ran(lambda: _knn(x, k, cuda))
+    assert_only(names, kr.kernel_of(b, c, n, k, cus), *kr.FAMILIES)  # (the kernel of the size, none of the wide path)
     with _lib.tuning('knn_wide', 1):
-        got = _knn(x, k, cuda)
+        got, names = ran(lambda: _knn(x, k, cuda))
+    assert_only(names, {kr.wide_select(c, k)} | ({'knn_wide_dist_kernel'} if c > 3 else set()), *kr.FAMILIES)
     assert np.array_equal(got, ref)
 
 

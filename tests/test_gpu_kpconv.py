@@ -15,6 +15,10 @@ import pytest
 import torch
 
 from tests import kpconv_reference as ref
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -10,6 +10,11 @@ import pytest
 import torch
 
 from tests import local_geometry_reference as ref
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -58,8 +63,10 @@ def _backward(xyz, idx, mean, grad_cov, grad_mean):
     b, n, _ = xyz.shape
     m, k = idx.shape[1:]
     gx = _guarded((b, n, 3), float('nan'), xyz.device)
-    _lib.call(_lib.lib.pcc_local_covariance_bwd, 'local_covariance_bwd', xyz.device, b, n, m, k, xyz.data_ptr(), idx.data_ptr(),
-              mean.data_ptr(), grad_cov.data_ptr(), None if grad_mean is None else grad_mean.data_ptr(), gx.data_ptr())
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_local_covariance_bwd, 'local_covariance_bwd', xyz.device, b, n, m, k, xyz.data_ptr(),
+                                     idx.data_ptr(), mean.data_ptr(), grad_cov.data_ptr(),
+                                     None if grad_mean is None else grad_mean.data_ptr(), gx.data_ptr()))
+    assert names == ({ref.bwd_kernel(n): 1} if b and m else {}), (n, names)  # (the side of the LDS boundary the rule predicts)
     return _open(gx, (b, n, 3))
 
 

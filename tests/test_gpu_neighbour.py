@@ -7,6 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import knn_reference as kr
+from tests.which_ran import assert_only, ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'ref_neighbour_ops.npz'), allow_pickle=False)
@@ -141,6 +148,20 @@ def test_knn_ties_ascending_index(cuda, oracle_mod):
     assert (idx[0, :, 0] == np.arange(300) % 50).all()  # lowest copy first
 
 
+def _knn_forced(x, k, kernel, cuda):
+    """``knn(x, k)`` under knn_nosplit = ``kernel`` (0: the product's dispatch) as numpy, once the launch record shows the
+    instantiation tests/knn_reference.py predicts -- the 128-query kernel (1) or the role-split kernel (2) at the list
+    width of k and the padded channel count of c -- and no other search kernel."""
+    from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
+
+    b, c, n = x.shape
+    with _lib.tuning('knn_nosplit', kernel):
+        idx, names = ran(lambda: ops.knn(x.to(cuda), k).cpu().numpy())
+    cus = torch.cuda.get_device_properties(cuda).multi_processor_count
+    assert_only(names, kr.kernel_of(b, c, n, k, cus, nosplit=kernel), *kr.FAMILIES)
+    return idx
+
+
 @pytest.mark.parametrize('b,c,n,k', [(2, 4, 64, 4), (2, 6, 200, 16), (2, 64, 257, 25), (1, 64, 2048, 25), (2, 128, 300, 20),
                                        (1, 128, 2048, 25), (2, 17, 131, 8), (2, 64, 2050, 25), (2, 32, 500, 30)])
 @pytest.mark.parametrize('kernel', [1, 2])
@@ -151,8 +172,7 @@ def test_knn_mfma_vs_oracle(cuda, oracle_mod, b, c, n, k, kernel):
     from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
 
     x = _x(c * 7 + n, b, c, n)
-    with _lib.tuning('knn_nosplit', kernel):
-        idx = ops.knn(x.to(cuda), k).cpu().numpy()
+    idx = _knn_forced(x, k, kernel, cuda)
     exp = oracle_mod.knn_expanded(x.numpy(), k)
     assert np.array_equal(idx, exp)
 
@@ -168,8 +188,7 @@ def test_knn_mfma_instantiation_choice(cuda, oracle_mod, c, k, kernel):
     from pointcloudcounterfactual_amd import _lib, neighbour_ops as ops
 
     x = _x(c * 131 + k, 2, c, 130)
-    with _lib.tuning('knn_nosplit', kernel):
-        idx = ops.knn(x.to(cuda), k).cpu().numpy()
+    idx = _knn_forced(x, k, kernel, cuda)
     assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), k))
 
 
@@ -179,7 +198,8 @@ def test_knn_mfma_many_small_clouds_take_the_role_split_kernel(cuda, oracle_mod)
     from pointcloudcounterfactual_amd import neighbour_ops as ops
 
     x = _x(99, 200, 8, 40)
-    idx = ops.knn(x.to(cuda), 5).cpu().numpy()
+    idx = _knn_forced(x, 5, 0, cuda)
+    assert kr.kernel_of(200, 8, 40, 5, torch.cuda.get_device_properties(cuda).multi_processor_count) == 'knn_mfma_split_kernel<8,16>'
     assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), 5))
 
 
@@ -197,8 +217,7 @@ def test_knn_mfma_adversarial_orders(cuda, oracle_mod, kernel):
     ties = torch.cat([_x(11, 1, c, 70)] * 10, dim=2)                                 # every point ten times
     for x, k in ((line, 25), (rev, 25), (ties, 16), (torch.cat([line, rev, ties], 0), 20)):
         x = x.contiguous()
-        with _lib.tuning('knn_nosplit', kernel):
-            idx = ops.knn(x.to(cuda), k).cpu().numpy()
+        idx = _knn_forced(x, k, kernel, cuda)
         assert np.array_equal(idx, oracle_mod.knn_expanded(x.numpy(), k))
 
 

@@ -12,7 +12,12 @@ import pytest
 import torch
 
 from tests.occupancy_reference import (AMBIGUOUS_CAP, GENERIC_KINDS, LATTICE_RES, cell_rule, counts_of, generic_case,
-                                       generic_points, lattice_points)
+                                       generic_points, kernels_of, lattice_points)
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,8 +37,13 @@ def _gpu(x, cuda, *args, path=0, **kwargs):
     from pointcloudcounterfactual_amd import _lib
 
     x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x, dtype=np.float32))
+    xd = x.to(cuda)
     with _lib.tuning('occupancy_path', path):
-        out = _sm().occupancy_grid(x.to(cuda), *args, **kwargs)
+        out, names = ran(lambda: _sm().occupancy_grid(xd, *args, **kwargs))
+    # the forced path's kernel ran and no sibling (path 2 is ignored where res > 32: the global kernel, the product's choice)
+    res, in_sphere, per_cloud = (lambda resolution=28, in_sphere=False, per_cloud=False, *_, **__: (resolution, in_sphere, per_cloud))(*args, **kwargs)
+    if xd.numel():
+        assert set(names) == kernels_of(res, in_sphere, per_cloud, path), (res, in_sphere, per_cloud, path, names)
     assert out.dtype == torch.int64 and out.device.type == 'cuda'
     return out.cpu()
 
@@ -142,8 +152,10 @@ def test_a_dirty_counts_buffer_is_overwritten(cuda):
                     counts = torch.full((s if per_cloud else 1, res ** 3), 12345, dtype=torch.int32, device=cuda)
                     with _lib.tuning('occupancy_path', path):
                         for _ in range(2):  # (the second call finds the first one's counts)
-                            call(_lib.lib.pcc_occupancy_grid, 'occupancy_grid', cuda, s, n, ptr(xd, 'xyz', torch.float32, cuda), res, -0.5,
-                                 1.0, in_sphere, per_cloud, ptr(counts, 'counts', torch.int32, cuda))
+                            _, names = ran(lambda: call(_lib.lib.pcc_occupancy_grid, 'occupancy_grid', cuda, s, n,
+                                                        ptr(xd, 'xyz', torch.float32, cuda), res, -0.5, 1.0, in_sphere, per_cloud,
+                                                        ptr(counts, 'counts', torch.int32, cuda)))
+                            assert set(names) == kernels_of(res, in_sphere, per_cloud, path), (res, in_sphere, per_cloud, path, names)
                     want = cpu if per_cloud else cpu.sum(0, keepdim=True)
                     assert torch.equal(counts.cpu().to(torch.int64), want.reshape(-1, res ** 3)), (s, n, res, in_sphere, per_cloud, path)
 

@@ -18,6 +18,10 @@ from tests import ragged_reference as R
 from tests import unaligned_views as U
 from tests import unaligned_views_ragged  # noqa: F401  (registers the two entry points' cases before the registry suites read it)
 from tests.ball_query_reference import GENERIC_KINDS, GENERIC_SHAPES, between_lattice, generic_cloud
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

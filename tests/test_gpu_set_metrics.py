@@ -11,6 +11,10 @@ import pytest
 import torch
 
 from tests.util import pair
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -46,11 +50,17 @@ def _rtol(n, m):
     return (max(n, m) + 2) * 2.0 ** -24
 
 
-def _check_directional(a, b, kind_tag):
+def _check_directional(a, b, kind_tag, oracle_mod=None):
     sm = _sm()
     n, m = a.size(1), b.size(1)
     for mean in (True, False):
         e_ab, e_ba = _pinned(a, b, mean)
+        if oracle_mod is not None and mean:  # the minima under the pinned sums are the oracle's, bit for bit (pair (0, 0))
+            from pointcloudcounterfactual_amd import backend
+
+            od1, _, od2, _ = oracle_mod.nndistance(a[:1].cpu().numpy(), b[:1].cpu().numpy())
+            d1, _, d2, _ = backend.NNDistance(a[:1].contiguous(), b[:1].contiguous())
+            assert np.array_equal(d1.cpu().numpy(), od1) and np.array_equal(d2.cpu().numpy(), od2)
         d_ab, d_ba = sm._chamfer_matrix(a, b, mean)
         err_ab = np.abs(d_ab.cpu().numpy() - e_ab) / e_ab.clip(min=np.finfo(np.float64).tiny)
         err_ba = np.abs(d_ba.cpu().numpy() - e_ba) / e_ba.clip(min=np.finfo(np.float64).tiny)
@@ -73,10 +83,10 @@ def _check_directional(a, b, kind_tag):
 @pytest.mark.parametrize('s,r', [(1, 1), (5, 7), (33, 2)])
 @pytest.mark.parametrize('n', POINTS)
 @pytest.mark.parametrize('m', POINTS)
-def test_directional_entries_against_the_pinned_search(cuda, s, r, n, m):
+def test_directional_entries_against_the_pinned_search(cuda, oracle_mod, s, r, n, m):
     for kind in ('recon', 'uniform'):
         a, b = _banks(n * 7 + m + s, s, n, r, m, kind, cuda)
-        _check_directional(a, b, kind)
+        _check_directional(a, b, kind, oracle_mod)
 
 
 @pytest.mark.parametrize('s,r,n,m', [(3, 2, 2049, 100), (2, 3, 100, 4100), (2, 2, 2500, 2300), (1, 2, 4096, 4097)])

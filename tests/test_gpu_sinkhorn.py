@@ -4,6 +4,7 @@ and bars stated there: the grid of sizes around every tile, group and slice boun
 determinism and independence of the batch, aliasing, a temperature far below the cloud's scale, every subset of the
 outputs, non-finite input, the refusals, every column split forced through the test hook, and autograd."""
 
+import contextlib
 import ctypes
 import itertools
 
@@ -13,6 +14,11 @@ import torch
 
 from pointcloudcounterfactual_amd.losses import sinkhorn_divergence, torch_sinkhorn  # noqa: F401  (no feature, no test)
 from tests import sinkhorn_reference as ref
+from tests.which_ran import assert_only, ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,9 +49,25 @@ def _shapes(b, n, m):
     return {'cost': (b,), 'pot_x': (b, n), 'pot_y': (b, m), 'grad_x': (b, n, 3), 'grad_y': (b, m, 3)}
 
 
+_SPLIT = [0]  # the sinkhorn_split value in force: ``_call`` asserts the slice count the rule predicts under it
+
+
+@contextlib.contextmanager
+def _split(value):
+    from pointcloudcounterfactual_amd import _lib
+
+    with _lib.tuning('sinkhorn_split', value):
+        _SPLIT[0] = value
+        try:
+            yield
+        finally:
+            _SPLIT[0] = 0
+
+
 def _call(x, y, eps, debias=True, want=ALL):
     """``pcc_sinkhorn`` on device tensors for the outputs named in ``want`` (null pointers for the others): ``{name: numpy}``.
-    The outputs start as NaN with sentinels behind them: every element must be written, nothing else."""
+    The outputs start as NaN with sentinels behind them: every element must be written, nothing else.  The launch record
+    must name the scans by the slice count ``ref.slices`` predicts, with the merge kernel exactly where that is above 1."""
     from pointcloudcounterfactual_amd import _lib
 
     b, n, m = x.shape[0], x.shape[1], y.shape[1]
@@ -56,8 +78,12 @@ def _call(x, y, eps, debias=True, want=ALL):
         bufs[name] = torch.full((size + GUARD,), SENTINEL, dtype=torch.float32, device=x.device)
         bufs[name][:size] = float('nan')
     sched = (ctypes.c_float * len(eps))(*eps)
-    _lib.call(_lib.lib.pcc_sinkhorn, 'sinkhorn', x.device, b, n, m, x.data_ptr(), y.data_ptr(), len(eps), ctypes.cast(sched, ctypes.c_void_p),
-              int(debias), *[bufs[name].data_ptr() if name in bufs else None for name in ALL])
+    _, names = ran(lambda: _lib.call(_lib.lib.pcc_sinkhorn, 'sinkhorn', x.device, b, n, m, x.data_ptr(), y.data_ptr(), len(eps),
+                                     ctypes.cast(sched, ctypes.c_void_p), int(debias),
+                                     *[bufs[name].data_ptr() if name in bufs else None for name in ALL]))
+    if b and want:
+        assert_only(names, ref.scan_kernel(n, m, debias, _SPLIT[0]), 'sk_scan_kernel')
+        assert ('sk_merge_kernel' in names) == (ref.slices(n, m, debias, _SPLIT[0]) > 1), names
     out = {}
     for name in want:
         host, size = bufs[name].cpu().numpy(), int(np.prod(shapes[name]))
@@ -115,8 +141,7 @@ SPLIT_BOUNDARIES = ((32766, 1, 16), (32767, 1, 8), (65534, 1, 8), (65535, 1, 4),
 def test_product_split_boundaries(cuda, n, m, slices):
     """The product's own choice of slices either side of the sizes where it changes, inside the bars; forcing the number
     of slices this test expects must return the product's words (which pins the choice itself)."""
-    from pointcloudcounterfactual_amd import _lib
-
+    assert ref.slices(n, m, False) == slices  # (what ``_call`` holds the launch record to)
     for k, steps in enumerate((8, 2)):
         scale, centre = ref.SCALES[(n + k) % 3]
         x, y = ref.clouds(n + k, 1, n, m, scale, centre)
@@ -125,7 +150,7 @@ def test_product_split_boundaries(cuda, n, m, slices):
         got = _call(xd, yd, eps, False)
         mult = ref.Result(x, y, eps, False).check(got, (n, m, steps))
         print(f'sinkhorn {n} x {m} T={steps} scale={scale} (product: {slices} slices): {mult}')
-        with _lib.tuning('sinkhorn_split', slices):
+        with _split(slices):
             forced = _call(xd, yd, eps, False)
         for name in ALL:
             assert _same_words(forced[name], got[name]), (name, n, m, steps)
@@ -255,16 +280,16 @@ def test_every_split_inside_the_bars(cuda):
     (1, 2, 4, 8, 16), an odd one and one above the most the kernel takes -- against the reference, and against the
     product's choice (the switch at 0).  The orders of summation differ, so the words may: every variant is held to
     the reference's bars and its potentials to ``ref.BAR_SPLIT`` U of the product's."""
-    from pointcloudcounterfactual_amd import _lib
-
     for (n, m), debias in (((700, 1300), True), ((257, 4100), False)):
         x, y = ref.clouds(n * m, 2, n, m)
         eps = ref.schedule(8, ref.diameter(x, y))
         want = ref.Result(x, y, eps, debias)
         xd, yd = _dev(x, cuda), _dev(y, cuda)
         product = _call(xd, yd, eps, debias)
-        for split in (1, 2, 3, 4, 8, 16, 99):
-            with _lib.tuning('sinkhorn_split', split):
+        # (4100 columns hold every slice count: there each allowance 1 .. 16 is also the number of slices taken)
+        for split in (1, 2, 3, 4, 8, 16, 99) if debias else tuple(range(1, 17)) + (99,):
+            assert debias or ref.slices(n, m, debias, split) == min(split, 16)
+            with _split(split):
                 got = _call(xd, yd, eps, debias)
             apart = max(float((np.abs(got[name].astype(np.float64) - product[name]) / want.U[:, None]).max()) for name in ('pot_x', 'pot_y'))
             print(f'sinkhorn {n} x {m} split {split}: {want.check(got, (n, m, split))}, {apart:.3f} U from the product')

@@ -12,6 +12,11 @@ import torch
 
 from pointcloudcounterfactual_amd.losses import sliced_wasserstein, torch_sliced_wasserstein  # noqa: F401  (no feature, no test)
 from tests import sliced_wasserstein_reference as ref
+from tests.which_ran import ran_only
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +65,11 @@ def _run(cuda, x, y, theta, want=ALL):
     return _call(_dev(x, cuda), _dev(y, cuda), _dev(theta, cuda), want)
 
 
+def _call_on(kernel, x, y, theta, want=ALL):
+    """``_call`` once the launch record shows that ``kernel``, and no other slice kernel, ran."""
+    return ran_only(lambda: _call(x, y, theta, want), kernel, 'sw_slice_kernel')
+
+
 @pytest.mark.parametrize('n', ref.N_GRID)
 def test_cost_word_for_word(cuda, n):
     """Every p of the grid; b in {1, 3} and the clouds' scale (unit, 1000 around 300, 1e-3) rotate.  The gradients ride along
@@ -70,7 +80,7 @@ def test_cost_word_for_word(cuda, n):
         x, y = ref.clouds(100 * n + p, b, n, scale, shift)
         theta = ref.unit_directions(n + p, p)
         want = ref.Forward(x, y, theta)
-        got = _run(cuda, x, y, theta)
+        got = _call_on(ref.kernel_of(n), _dev(x, cuda), _dev(y, cuda), _dev(theta, cuda))  # (n sits next to a switch point)
         assert _same_words(got['cost_p'], want.cost_p), (n, p)
         assert _same_words(got['cost'], want.cost), (n, p)
         ref.Grad(want, theta).check_bound(got['grad_x'], got['grad_y'])
@@ -79,18 +89,24 @@ def test_cost_word_for_word(cuda, n):
 @pytest.mark.parametrize('n', ref.N_GRID)
 def test_every_variant_returns_the_words_of_the_product(cuda, n):
     """Every (threads, elements per thread) variant that holds n, forced through the ``sw_path`` switch, over the p of the
-    forward grid: all four outputs word for word those of the product's choice, which the test above holds against the
-    reference."""
+    forward grid: all four outputs word for word those of the product's choice, which is held against the reference here
+    as in the test above.  The launch record proves each variant; one that cannot hold n is ignored (include/pcc_test_hooks.h), which
+    the first p of the grid shows: the product's kernel runs under it."""
     from pointcloudcounterfactual_amd import _lib
 
     for j, p in enumerate(ref.P_GRID):
         x, y = ref.clouds(100 * n + p, (1, 3)[j % 2], n)
-        xd, yd, td = _dev(x, cuda), _dev(y, cuda), _dev(ref.unit_directions(n + p, p), cuda)
-        product = _call(xd, yd, td)
+        theta = ref.unit_directions(n + p, p)
+        xd, yd, td = _dev(x, cuda), _dev(y, cuda), _dev(theta, cuda)
+        product = _call_on(ref.kernel_of(n), xd, yd, td)
+        want = ref.Forward(x, y, theta)  # (here too, so that every variant below is held to the reference inside this test)
+        assert _same_words(product['cost_p'], want.cost_p) and _same_words(product['cost'], want.cost), (n, p)
+        ref.Grad(want, theta).check_bound(product['grad_x'], product['grad_y'])
         for variant, capacity in enumerate(ref.VARIANT_CAPACITY, 1):
-            if capacity >= n:
+            if capacity >= n or j == 0:
+                assert ref.kernel_of(n, variant) == ('sw_slice_kernel<%d,%d>' % ref.VARIANT_SHAPE[variant - 1] if capacity >= n else ref.kernel_of(n))
                 with _lib.tuning('sw_path', variant):
-                    got = _call(xd, yd, td)
+                    got = _call_on(ref.kernel_of(n, variant), xd, yd, td)
                 for name in ALL:
                     assert _same_words(got[name], product[name]), (n, p, variant, name)
 

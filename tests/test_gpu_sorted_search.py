@@ -18,8 +18,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests import knn_reference as kr
 from tests.sorted_search_clouds import KINDS, channels_major, stress_cloud
 from tests.util import pair
+from tests.which_ran import assert_only
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +45,15 @@ def _launches(prefix):
 
 @contextlib.contextmanager
 def _profiled():
+    """``launches(prefix)`` over the body's launches; ``launches.exact()``: the exact launch record."""
     from pointcloudcounterfactual_amd import _lib
 
-    _lib.lib.pcc_profile_enable(1)  # (also clears what an earlier call recorded)
-    try:
-        yield _launches
-    finally:
-        _lib.lib.pcc_profile_enable(0)
+    with _lib.profile() as read:  # (cleared and enabled on entry, disabled behind the body)
+        def launches(prefix):
+            return _launches(prefix)
+
+        launches.exact = read.exact
+        yield launches
 
 
 def _sort_slots(*sizes):
@@ -96,6 +104,9 @@ def _check_knn(cuda, oracle_mod, x, k, key, stride, kernel=None):
         if kernel is not None:
             other = 'knn_small_kernel' if kernel == 'knn_sorted_kernel' else 'knn_sorted_kernel'
             assert launches(kernel) >= 1 and launches(other) == 0, (kernel, n)
+            exact = kr.kernel_of(x.shape[0], x.shape[1], n, k)  # ... in the instantiation of this list width
+            assert exact.startswith(kernel + '<'), (exact, kernel)
+            assert_only(launches.exact(), exact, *kr.FAMILIES)
             if kernel == 'knn_sorted_kernel':
                 assert _ran_only(launches, 'am_sort_kernel', f'am_sort_kernel<{_sort_slots(n)}>'), n
             else:
@@ -118,6 +129,15 @@ def test_knn_sorted_search_size_classes(cuda, oracle_mod, n, kind, k):
     x = channels_major(stress_cloud(kind, 100 + n, 1, n))
     _check_knn(cuda, oracle_mod, x, k, ('size', kind, n), 37,
                kernel='knn_sorted_kernel' if n <= 16384 else 'knn_small_kernel')
+
+
+@pytest.mark.parametrize('k', [4, 5, 8, 9, 16, 17, 21, 26])
+def test_knn_exhaustive_kernel_every_list_width(cuda, oracle_mod, k):
+    """The exhaustive kernel (16385 points) in every list-width instantiation, at both ends of the slot classes (k = 1, 20
+    and 32 are in the size classes above); the launch record names the instantiation."""
+    n = 16385
+    x = channels_major(stress_cloud('surface', 100 + n, 1, n))
+    _check_knn(cuda, oracle_mod, x, k, ('size', 'surface', n), 37, kernel='knn_small_kernel')
 
 
 def test_knn_sorted_search_two_channels_two_samples(cuda, oracle_mod):

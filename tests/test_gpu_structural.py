@@ -9,6 +9,10 @@ import pytest
 import torch
 
 from tests.util import pair
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -104,9 +108,15 @@ AM_SHAPES = [(1, 1, 1), (2, 3, 5), (2, 64, 64), (2, 257, 130), (2, 128, 256), (1
 @pytest.mark.parametrize('b,n,m', AM_SHAPES)
 @pytest.mark.parametrize('kind', ['recon', 'uniform'])
 def test_approxmatch_vs_oracle(cuda, oracle_mod, b, n, m, kind):
+    a, c = pair(300 + n + m, b, n, m, kind)
+    _approxmatch_inside_the_oracle_bars(cuda, oracle_mod, a, c)
+
+
+def _approxmatch_inside_the_oracle_bars(cuda, oracle_mod, a, c):
+    """``backend.ApproxMatch`` + ``MatchCost`` of the clouds ``a``, ``c`` against the float64 recurrence; -> (match, cost)."""
     from pointcloudcounterfactual_amd import backend
 
-    a, c = pair(300 + n + m, b, n, m, kind)
+    n, m = a.shape[1], c.shape[1]
     match, temp = backend.ApproxMatch(_dev(a, cuda), _dev(c, cuda))
     om64, ot64 = oracle_mod.approxmatch_f64(a, c)
     got = match.cpu().numpy()
@@ -139,6 +149,53 @@ def test_approxmatch_vs_oracle(cuda, oracle_mod, b, n, m, kind):
     cost = backend.MatchCost(_dev(a, cuda), _dev(c, cuda), match).cpu().numpy()
     oc64 = oracle_mod.matchcost_f64(a, c, om64)
     np.testing.assert_allclose(cost, oc64, rtol=1e-5, atol=1e-7)
+    return got, cost
+
+
+# the 19 passes of one approximate EMD under their launch-profile names, on the kernels without skip logic
+PLAIN_PASSES = ({'am_phase_kernel<A> L0 plain', 'am_phase_kernel<C> L8 plain'} | {f'am_phase_kernel<B> L{i} plain' for i in range(9)}
+                | {f'am_phase_kernel<CA> L{i} plain' for i in range(8)})
+
+
+@pytest.mark.parametrize('b,n,m', [(2, 64, 64), (2, 257, 130), (1, 513, 512), (2, 1024, 1024)])
+@pytest.mark.parametrize('kind', ['recon', 'uniform'])
+def test_plain_passes_vs_oracle(cuda, oracle_mod, b, n, m, kind, capsys):
+    """The am_nocull switch (include/pcc_test_hooks.h) runs all 19 passes on the plain am_phase_kernel variants -- the
+    arithmetic behind the no-skip roofline bench.py reports.  ApproxMatch + MatchCost, the implicit match_cost and
+    chamfer_emd under it are held to the bars of the product path (test_approxmatch_vs_oracle, tests.util.check_match_cost),
+    and the launch record proves what ran: each plain pass once, no fine-level, owner-compacted or list variant, no
+    resident launch -- and, with the switch at 0, at least one of those, so the switch acts.  Printed, not asserted: the
+    largest difference between the skipping and the no-skip result."""
+    from pointcloudcounterfactual_amd import _lib, backend
+    from tests.util import check_match_cost
+    from tests.which_ran import family, ran
+
+    def passes(names):
+        return set(family(names, 'am_phase_kernel', 'am_fine'))
+
+    a, c = pair(300 + n + m, b, n, m, kind)
+    t1, t2 = _dev(a, cuda), _dev(c, cuda)
+    (match0, _), names = ran(lambda: backend.ApproxMatch(t1, t2))
+    assert passes(names) - PLAIN_PASSES, names  # the product skips somewhere
+    cost0, g0, h0 = backend.MatchCostImplicit(t1, t2, True)
+    with _lib.tuning('am_nocull', 1):
+        (match, _cost), names = ran(lambda: _approxmatch_inside_the_oracle_bars(cuda, oracle_mod, a, c))
+        assert passes(names) == PLAIN_PASSES and all(names[p] == 1 for p in PLAIN_PASSES), names
+        (cost, g1, g2), names = ran(lambda: backend.MatchCostImplicit(t1, t2, True))
+        assert passes(names) == PLAIN_PASSES and all(names[p] == 1 for p in PLAIN_PASSES), names
+        check_match_cost(oracle_mod, a, c, cost.cpu().numpy(), g1.cpu().numpy(), g2.cpu().numpy())
+        (loss, j1, j2, emd, e1, e2, d1, d2), names = ran(lambda: backend.ChamferEMD(t1, t2, True, True, return_dist=True))
+        assert passes(names) == PLAIN_PASSES and all(names[p] == 1 for p in PLAIN_PASSES), names
+        check_match_cost(oracle_mod, a, c, emd.cpu().numpy(), e1.cpu().numpy(), e2.cpu().numpy())
+    ref_loss, r1, i1, r2, i2 = backend.ChamferLoss(t1, t2, True)  # the Chamfer half: the bits of the exhaustive search
+    assert torch.equal(loss, ref_loss) and torch.equal(j1, i1) and torch.equal(j2, i2) and torch.equal(d1, r1) and torch.equal(d2, r2)
+    # ... which are the oracle's, bit for bit (as in test_nndistance_bit_exact): the sorted search of chamfer_emd held to it directly
+    od1, oi1, od2, oi2 = oracle_mod.nndistance(a, c)
+    assert np.array_equal(j1.cpu().numpy(), oi1) and np.array_equal(j2.cpu().numpy(), oi2)
+    assert np.array_equal(d1.cpu().numpy(), od1) and np.array_equal(d2.cpu().numpy(), od2)
+    with capsys.disabled():
+        print(f'\n  no-skip against skipping, ({b}, {n}, {m}) {kind}: match {float((torch.from_numpy(match).to(cuda) - match0).abs().max()):.3e}'
+              f' cost {float((cost - cost0).abs().max()):.3e} grad {max(float((g1 - g0).abs().max()), float((g2 - h0).abs().max())):.3e}')
 
 
 @pytest.mark.parametrize('b,n,m', [(2, 3, 5), (2, 257, 130), (2, 1024, 1024), (1, 100, 2100)])
@@ -335,6 +392,9 @@ def test_implicit_match_cost_vs_oracle(cuda, oracle_mod, b, n, m):
     om64, _ = oracle_mod.approxmatch_f64(a, c)
     oc64 = oracle_mod.matchcost_f64(a, c, om64)
     np.testing.assert_allclose(cost.cpu().numpy(), oc64, rtol=1e-5, atol=1e-7)
+    # the cost-only call (am_pair_kernel<cost>: no gradient sums, sqrt taken directly) against the same float64 cost, same bar
+    only_cost, = backend.MatchCostImplicit(_dev(a, cuda), _dev(c, cuda), False)
+    np.testing.assert_allclose(only_cost.cpu().numpy(), oc64, rtol=1e-5, atol=1e-7)
     h1, h2 = oracle_mod.matchcostgrad_f64(a, c, om64)
     scale = max(np.abs(h1).max(), np.abs(h2).max())
     spread = 0.0
@@ -439,12 +499,20 @@ def test_chamfer_fused_equals_nn_distance_expression(cuda, b, n, m, reduction):
 def test_two_lane_schedule_equals_single_stream(cuda):
     """At the bench size (B=32, N=2048) the level passes run as two half-batch lanes on two streams.
     Per sample nothing changes, so the results carry the same bits as the single-stream schedule (measurement switch
-    `am_nosplit`, include/pcc_test_hooks.h), run to run."""
+    `am_nosplit`, include/pcc_test_hooks.h), run to run.  The launch record shows the schedule: every pass launched twice
+    per call, once per lane, and once under the switch."""
     from pointcloudcounterfactual_amd import _lib, backend
+    from tests.which_ran import family, ran
+
+    def launches_per_pass(names):
+        passes = family(names, 'am_phase_kernel')
+        assert len(passes) == 19, names  # (the 19 passes; 65536 owners x tiles: no resident launch at this size)
+        return set(passes.values())
 
     a, c = pair(91, 32, 2048, 2048)
     t1, t2 = _dev(a, cuda), _dev(c, cuda)
-    r1 = backend.MatchCostImplicit(t1, t2, True)
+    r1, names = ran(lambda: backend.MatchCostImplicit(t1, t2, True))
+    assert launches_per_pass(names) == {2}
     r2 = backend.MatchCostImplicit(t1, t2, True)
     assert all(torch.equal(x, y) for x, y in zip(r1, r2))
     m1 = backend.ApproxMatchCost(t1, t2)
@@ -452,7 +520,8 @@ def test_two_lane_schedule_equals_single_stream(cuda):
     temp1, mc1 = m1[1].clone(), m1[2].clone()
     del m1
     with _lib.tuning('am_nosplit', 1):
-        s1 = backend.MatchCostImplicit(t1, t2, True)
+        s1, names = ran(lambda: backend.MatchCostImplicit(t1, t2, True))
+        assert launches_per_pass(names) == {1}
         sm = backend.ApproxMatchCost(t1, t2)
         torch.cuda.synchronize()
     assert all(torch.equal(x, y) for x, y in zip(r1, s1))
@@ -466,22 +535,32 @@ def test_resident_fine_levels_equal_one_launch_per_pass(cuda):
     launch per pass (am_fine_kernel).  Same walk, same reduction order: every output carries the same bits -- cost,
     both gradients, the materialised path's cost, temp (remainL | remainR | ratioL | ratioR of the last level) and the
     row masses of match -- at the largest qualifying batch, at unequal clouds, at ragged sizes and at clouds smaller
-    than one tile."""
+    than one tile.  The launch record shows which ran: the resident launch and no fine-level pass of its own where the
+    rule above admits it, the seven fine-level passes and no resident launch under the switch."""
     from pointcloudcounterfactual_amd import _lib, backend
+    from tests.which_ran import family, ran
 
+    cus = torch.cuda.get_device_properties(cuda).multi_processor_count
+    fine = {'am_phase_kernel<A> L0 fine'} | {f'am_phase_kernel<{p}> L{i} fine' for p in ('B', 'CA') for i in range(3)}
     shapes = [(8, 2048, 2048, 'recon'), (3, 1000, 2048, 'recon'), (2, 2048, 700, 'uniform'), (5, 257, 130, 'recon'),
               (2, 40, 17, 'uniform'), (9, 1024, 1024, 'uniform'), (1, 1, 1, 'recon')]
 
     def run(k, b, n, m, kind):
         a, c = pair(300 + k, b, n, m, kind)
         t1, t2 = _dev(a, cuda), _dev(c, cuda)
-        cost, g1, g2 = backend.MatchCostImplicit(t1, t2, True)
-        mt, t, mc = backend.ApproxMatchCost(t1, t2)
+        (cost, g1, g2), names = ran(lambda: backend.MatchCostImplicit(t1, t2, True))
+        (mt, t, mc), more = ran(lambda: backend.ApproxMatchCost(t1, t2))
+        for record in (names, more):
+            assert set(family(record, 'am_fine_persist_kernel', *fine)) == expected, (b, n, m, record)
         return {'cost': cost, 'g1': g1, 'g2': g2, 'mc': mc, 'temp': t, 'rowmass': mt.sum(2)}
 
     for k, shape in enumerate(shapes):
+        b, n, m, _ = shape
+        assert max(n, m) <= 2048 and b * -(-max(n, m) // 64) <= cus  # (every shape qualifies for the resident launch)
+        expected = {'am_fine_persist_kernel'}
         resident = run(k, *shape)
         with _lib.tuning('am_noresident', 1):
+            expected = fine
             per_pass = run(k, *shape)
             torch.cuda.synchronize()
         for name in resident:

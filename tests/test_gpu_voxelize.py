@@ -9,6 +9,11 @@ import pytest
 import torch
 
 from tests import voxel_reference as ref
+from tests.which_ran import ran
+# autouse fixture: a test of this module that tests/kernel_census.py names runs with the launch profile on from start to end
+# (a pcc_profile_enable(0) inside it re-enables, so such a test cannot observe profiling off) and fails if a kernel mapped
+# to it did not launch
+from tests.which_ran import census_proof  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -52,14 +57,18 @@ def _index(xyz, res, lo, extent):
     b, n = xyz.shape[:2]
     dev = xyz.device
     cell, order, counts = _Out((b, n), torch.int32, dev), _Out((b, n), torch.int32, dev), _Out((b, res ** 3), torch.int32, dev)
-    _call('voxel_index', dev, b, n, xyz.data_ptr(), res, lo, extent, cell.ptr(), order.ptr(), counts.ptr())
+    _, names = ran(lambda: _call('voxel_index', dev, b, n, xyz.data_ptr(), res, lo, extent, cell.ptr(), order.ptr(), counts.ptr()))
+    assert names == ({ref.index_kernel(n): 1} if b else {}), (n, names)  # (the sort the size predicts, no sibling)
     return (cell, order, counts), (cell.numpy(), order.numpy(), counts.numpy())
 
 
 def _vox(x, index, res, shift=0):
     b, c, n = x.shape
     grid = _Out((b, c, res ** 3), torch.float32, x.device, shift)
-    _call('voxelize', x.device, b, c, n, res, x.data_ptr(), index[0].ptr(), index[1].ptr(), index[2].ptr(), grid.ptr())
+    _, names = ran(lambda: _call('voxelize', x.device, b, c, n, res, x.data_ptr(), index[0].ptr(), index[1].ptr(), index[2].ptr(),
+                                 grid.ptr()))
+    aligned = (index[2].ptr() | grid.ptr()) % 16 == 0
+    assert set(names) == (ref.voxelize_kernels(n, res, aligned) if b else set()), (n, res, aligned, names)
     return grid.numpy()
 
 
@@ -81,7 +90,8 @@ def _devox(grid, xyz, res, lo, extent):
 def _devox_bwd(xyz, go, res, lo, extent, shift=0):
     b, c, n = go.shape
     gg = _Out((b, c, res ** 3), torch.float32, xyz.device, shift)
-    _call('devoxelize_bwd', xyz.device, b, c, n, res, lo, extent, xyz.data_ptr(), go.data_ptr(), gg.ptr())
+    _, names = ran(lambda: _call('devoxelize_bwd', xyz.device, b, c, n, res, lo, extent, xyz.data_ptr(), go.data_ptr(), gg.ptr()))
+    assert names == ({ref.devox_bwd_kernel(res): 1} if b else {}), (res, names)  # (the rows per workgroup the resolution predicts)
     return gg.numpy()
 
 

@@ -31,7 +31,7 @@ FLOAT_FILL = 0x7fdead00    # a NaN whose payload no kernel produces
 INT_FILL = -7777
 SHIFTS = {F32: (1, 2, 3), I32: (1, 2, 3), I64: (1,)}  # elements: 4, 8 and 12 bytes; 8 bytes for an int64 list
 
-EXEMPT = {'pcc_version', 'pcc_last_error', 'pcc_last_status', 'pcc_profile_enable', 'pcc_profile_reset', 'pcc_profile_read',
+EXEMPT = {'pcc_version', 'pcc_last_error', 'pcc_last_status', 'pcc_profile_enable', 'pcc_profile_reset', 'pcc_profile_read', 'pcc_profile_names',
           'pcc_approxmatch_workspace_bytes', 'pcc_auction_status', 'pcc_test_inject_auction_failure',
           'pcc_test_inject_approxmatch_failure', 'pcc_test_set_tuning'}
 

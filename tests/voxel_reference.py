@@ -12,6 +12,34 @@ NAN_WORD = 0x7fc00000
 # LDS network padded to the next power of two above, MAX_POINTS at the most; CB channels per thread; a run of more than
 # LONG_RUN points of one cell goes to the kernel with the channels across lanes; LDS bins up to res = LDS_RES.
 WAVE_SORT, MAX_POINTS, CB, LONG_RUN, LDS_RES = 256, 16384, 8, 64, 32
+SORT_THREADS = 1024  # threads of the LDS sort at the most: 2 keys per thread up to 2048 keys, then 4, 8, 16
+
+
+# ---- which kernels a call runs, as exact launch-profile names (restated from DESIGN.md and the comments above) ----
+def index_kernel(n):
+    """``pcc_voxel_index``: the register sort of one wave up to WAVE_SORT points, the LDS sort above, instantiated by its keys
+    per thread: the points padded to a power of two (512 at the least) over at most SORT_THREADS threads."""
+    if n <= WAVE_SORT:
+        return 'vox_index_wave_kernel'
+    npad = 2 * WAVE_SORT
+    while npad < n:
+        npad *= 2
+    return f'vox_index_lds_kernel<{max(2, npad // SORT_THREADS)}>'
+
+
+def voxelize_kernels(n, res, aligned=True):
+    """``pcc_voxelize``: the cell starts, the forward four cells per thread where res^3 is a multiple of 4 and counts and
+    grid are 16-byte aligned (one otherwise), and the long-run kernel wherever a cell can hold more than LONG_RUN points."""
+    wide = res ** 3 % 4 == 0 and aligned
+    return {'vox_start_kernel', 'vox_fwd_kernel<4>' if wide else 'vox_fwd_kernel<1>'} | ({'vox_long_kernel'} if n > LONG_RUN else set())
+
+
+def devox_bwd_kernel(res):
+    """``pcc_devoxelize_bwd``: LDS bins up to LDS_RES -- rows of res^3 floats, 8 per workgroup while they fit 128 KB (res <=
+    16), 4 to 20, 2 to 25, 1 above -- and global atomics beyond."""
+    if res > LDS_RES:
+        return 'devox_bwd_global_kernel'
+    return 'devox_bwd_lds_kernel<%d>' % next((cb for cb in (8, 4, 2) if cb * res ** 3 * 4 <= 128 * 1024), 1)
 GRIDS = ((-0.5, 1.0), None)  # (lo, extent); None: lo = 0, extent = res - 1, so that inv = 1 and grid coordinates are exact
 
 
