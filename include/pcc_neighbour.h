@@ -530,6 +530,39 @@ int pcc_cell_neighbours(int b, int n, int m, int res, int ksize, int dilation, c
 int pcc_sparse_conv(int b, int c, int o, int n, int m, int t, const float *x, const int64_t *nbr, const float *weight,
                     const float *bias, float *out, pcc_stream_t stream);
 
+/* The kernel map of a submanifold sparse convolution over a RAGGED grid level: pcc_cell_neighbours for the slots of
+ * pcc_grid_cluster_ragged -- scenes of any size, up to 2^16 cells per axis, a packed batch of clouds of unequal size.  The
+ * result is an ordinary list with b = 1: pcc_sparse_conv, pcc_group_points, pcc_aggregate_points and pcc_local_geometry take
+ * it unchanged.  What a user writes in torch instead: int64 keys, one searchsorted of m * ksize^3 targets, a mask.
+ *   inputs      coord[m, 4] int32 and n_cells[1] int32 are those of pcc_grid_cluster_ragged at capacity m.  The real slots
+ *               are r < kept = min(max(n_cells[0], 0), m), ascending by (c, i, j, k).  Rows at or after kept are never read.
+ *               nbr[m, ksize^3] int64.
+ *   rule        Let h = (ksize - 1) / 2, offsets di, dj, dk in [-h, h], and t = ((di + h) * ksize + (dj + h)) * ksize + (dk + h).
+ *               nbr[r, t] is the rank s < kept of the slot whose row is (c, i + dilation * di, j + dilation * dj,
+ *               k + dilation * dk): the same cloud, with every target coordinate inside [0, 65536).  It is -1 if there is no
+ *               such slot.  It is -1 in every tap of a padded slot (r >= kept).
+ *               The offsets are added to the decomposed coordinates in 32-bit integers, and the range test comes before any
+ *               packing into a key.  Nothing wraps.  A carry from k into j must not turn (i, j, 65535) + 1 into
+ *               (i, j + 1, 0), and cloud c's cell must not become cloud c +- 1's.
+ *   so          The centre tap of a real slot is r.
+ *               The map is symmetric: nbr[r, t] = s >= 0 exactly when nbr[s, ksize^3 - 1 - t] = r.
+ *               The map at capacity m is the map at capacity n cut to m rows, with ranks >= m turned into -1.
+ *               Integers only.  Every word is written exactly once and is fixed by coord alone.
+ *   trust       coord is trusted to be the library's for the MEANING of the result, never for safety.  No value read from
+ *               coord or n_cells becomes an address.  Every position read lies in [0, kept).  Every loop is bounded (a
+ *               bisection by 32 steps, the taps by ksize).  On arbitrary int32 garbage every output word is in [-1, kept).
+ *               (A real slot with a component outside [0, 65536) has -1 in every tap.)
+ *   refusals    PCC_EINVAL under "cell_neighbours_ragged:" before anything is enqueued: m < 1, m * ksize^3 >= 2^31, ksize not
+ *               3 or 5, dilation < 1, a null pointer.  A dilation of 65536 or more reaches only the centre and is clamped to
+ *               65536, as pcc_cell_neighbours clamps to res.
+ *   launches    One launch.  No workspace, no host synchronisation, no atomics, no inter-workgroup communication; the grid
+ *               is a function of (m, ksize) alone.
+ *   capture     Graph capture is neither claimed nor tested for this entry point.
+ *   alignment   coord and n_cells may be any 4-byte-aligned address, nbr any 8-byte-aligned one (the alignment paragraph
+ *               above): a row of coord is one 16-byte load only where coord lies on a 16-byte boundary. */
+int pcc_cell_neighbours_ragged(int m, int ksize, int dilation, const int32_t *coord, const int32_t *n_cells, int64_t *nbr,
+                               pcc_stream_t stream);
+
 /* get_neighbours (neighbour_ops.py:85-94): out[b,c,n,j] = x[b,c,indices[b,n,j]]. */
 int pcc_gather_neighbours(int b, int c, int n, int k, const float *x, const int64_t *indices, float *out,
                           pcc_stream_t stream);

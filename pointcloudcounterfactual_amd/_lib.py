@@ -86,6 +86,7 @@ ABI: dict[str, tuple[object, list[object]]] = {
     'pcc_grid_cluster_ragged': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_cell_neighbours':(_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcc_sparse_conv': (_int, [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pcc_cell_neighbours_ragged': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_gather_neighbours_bwd': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'pcc_graph_features': (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp]),

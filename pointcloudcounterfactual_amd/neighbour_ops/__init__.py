@@ -45,6 +45,8 @@ from pointcloudcounterfactual_amd.neighbour_ops.ragged_grid import (  # noqa: F4
 from pointcloudcounterfactual_amd.neighbour_ops.sparse import (  # noqa: F401
     KERNEL_SIZES, SparseConvMap, SparseConvolved, SubmanifoldConv3d, cell_neighbours, sparse_conv, torch_cell_neighbours,
     torch_sparse_conv)
+from pointcloudcounterfactual_amd.neighbour_ops.ragged_sparse import (  # noqa: F401
+    cell_neighbours_ragged, hip_cell_neighbours_ragged, sparse_conv_ragged, torch_cell_neighbours_ragged)
 from pointcloudcounterfactual_amd.neighbour_ops.strided import (  # noqa: F401
     MAX_WGRAD_ROWS, STRIDE_TAPS, SparseConv3d, SparseConvTranspose3d, StrideMap, coarsen_level, sparse_conv_transpose,
     sparse_conv_wgrad, stride_map, strided_sparse_conv, torch_coarsen_cells, torch_sparse_conv_wgrad, torch_stride_map)
