@@ -7,7 +7,9 @@
  * replaces.  Tensors are contiguous row-major device arrays in the reference's layouts:
  *   x[b, c, n] float32 (channels-major), indices[b, n, k] int64.
  * All entries enqueue on `stream` (hipStream_t as void*), never synchronise, and return 0 or an error code
- * (message via pcc_last_error(), include/pcc_structural.h).
+ * (message via pcc_last_error(), include/pcc_structural.h).  ("Never synchronise" with the runtime's one exception that
+ * the head of include/pcc_structural.h describes: the second of two workspace-taking calls on a stream that has not yet
+ * executed the first; tests/test_gpu_stream_order.py.)
  *
  * Alignment: every tensor argument, input or output, may be any contiguous buffer aligned to its element size -- 4 bytes,
  * 8 for an int64 list (a chunk of a batch, a parameter inside a flat buffer, a slice of a gradient).  The kernels take

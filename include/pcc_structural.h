@@ -7,7 +7,13 @@
  * same argument order and meaning; the only change is `cudaStream_t` -> `hipStream_t` (passed as
  * `void *` so that the header needs no HIP include).  All pointers are device pointers to
  * contiguous row-major float32 / int32 arrays; inputs are borrowed and never written; outputs are
- * fully overwritten.  Calls enqueue work on `stream` and return without synchronising.
+ * fully overwritten.  Calls enqueue work on `stream` and return without synchronising -- with one exception that is the
+ * runtime's, not the library's: an entry that takes a workspace from the library's memory pool gives it back with
+ * hipFreeAsync on `stream`, and when an earlier call on the same stream, not yet executed, had freed the very block this call
+ * was handed, that hipFreeAsync waits on the host until the stream has reached the earlier free (ROCm 7.0).  A call on a
+ * stream that holds no unfinished call of the library returns at once, however busy the stream is with other work.
+ * tests/test_gpu_stream_order.py runs every entry point on a side stream behind late inputs and asserts both; the table
+ * WAITS of tests/stream_order.py names the entries that take such a workspace.
  *
  * Error behaviour: the reference's approxmatch/matchcost/matchcostgrad launchers throw
  * std::runtime_error("CUDA kernel failed : <code>") (approxmatch.cu:303-306) and its nndistance

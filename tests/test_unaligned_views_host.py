@@ -7,6 +7,8 @@ import pytest
 import torch
 
 from tests import unaligned_views as U
+from tests import unaligned_views_cell_ragged, unaligned_views_grid_ragged, unaligned_views_ragged  # noqa: F401  (they register their cases:
+# all 41 however this file is run)
 
 IDS = [case.name for case in U.CASES]
 

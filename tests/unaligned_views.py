@@ -141,9 +141,19 @@ def variants(call: Call, pool: dict[str, Any]) -> list[dict[str, int]]:
     return [{name: e} for name, dtype in names for e in SHIFTS[dtype]] + [{name: 1 for name, _ in names}]
 
 
-def run_call(call: Call, pool: dict[str, Any], dev: torch.device, shift: dict[str, int]) -> dict[str, np.ndarray]:
+class Pending(NamedTuple):
+    """A call that ``enqueue_call`` has made and nobody has waited for: its guarded outputs, and the argument tensors, which
+    must outlive the kernels that read them."""
+
+    outs: list[tuple[Out, guarded]]
+    alive: list[torch.Tensor]
+
+
+def enqueue_call(call: Call, pool: dict[str, Any], dev: torch.device, shift: dict[str, int],
+                 returned: Callable[[], None] | None = None) -> Pending:
     """The call on the device tensors of ``pool``, the arguments named in ``shift`` that many elements off a 16-byte boundary
-    (the others on one): its outputs as numpy, guards checked."""
+    (the others on one), built and enqueued on the current stream of ``dev`` without waiting for anything.  ``returned`` runs
+    the moment the library's function has returned (tests/stream_order.py asks there whether the stream is still busy)."""
     from pointcloudcounterfactual_amd import _lib
 
     args: list[Any] = []
@@ -172,18 +182,33 @@ def run_call(call: Call, pool: dict[str, Any], dev: torch.device, shift: dict[st
             args.append(a)
     fn = getattr(_lib.lib, call.symbol)
     with _lib.tuning(*call.tune) if call.tune else contextlib.nullcontext():
+        with torch.cuda.device(dev):
+            status = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
+        if returned is not None:
+            returned()
         if call.void:
-            with torch.cuda.device(dev):
-                assert fn(*args, torch.cuda.current_stream(dev).cuda_stream) is None
+            assert status is None
             assert _lib.lib.pcc_last_status() == 0, _lib.lib.pcc_last_error()
         else:
-            _lib.call(fn, call.symbol, dev, *args)
-    torch.cuda.synchronize(dev)
+            _lib.check(status, call.symbol)
+    return Pending(outs, alive)
+
+
+def collect_call(pending: Pending) -> dict[str, np.ndarray]:
+    """The outputs of a call of ``enqueue_call`` as numpy, guards checked.  The caller has waited for the call: the copies
+    to the host are made on the current stream, which need not be the call's."""
     got = {}
-    for a, g in outs:
+    for a, g in pending.outs:
         body = g.numpy(a.whole)
         got[a.name] = body if a.keep is None else a.keep(body)
     return got
+
+
+def run_call(call: Call, pool: dict[str, Any], dev: torch.device, shift: dict[str, int]) -> dict[str, np.ndarray]:
+    """``enqueue_call`` on the current stream, a wait for the device, and ``collect_call``."""
+    pending = enqueue_call(call, pool, dev, shift)
+    torch.cuda.synchronize(dev)
+    return collect_call(pending)
 
 
 # ---- inputs -------------------------------------------------------------------------------------------------------------------

@@ -2,9 +2,8 @@
 appends the case to ``unaligned_views.CASES`` (once), exactly as tests/unaligned_views_grid_ragged.py does for the ragged grid index,
 so that tests/test_unaligned_views_host.py and tests/test_gpu_unaligned_views.py, unchanged, take it like every other case.
 
-The new test files (tests/test_cell_ragged_host.py, tests/test_gpu_cell_ragged.py) import this module, and both sort before the two
-registry suites.  A run of one of the registry suites ALONE does not import it: its coverage check then reports the entry point as
-uncovered.  Run them together with one of the two new files, or with the whole directory.
+Every file that reads the registry (tests/test_unaligned_views_host.py, tests/test_gpu_unaligned_views.py,
+tests/stream_order.py) imports this module, so the case is there however a file is run.
 
 ``coord`` 4, 8 and 12 bytes off a 16-byte boundary takes the kernel's four dword loads per row, on the boundary its one 16-byte load;
 ``nbr`` 8 bytes off.  A scene of 280 cells in two clouds (more than one workgroup) at capacity 300 (padded slots) for K = 3, and at

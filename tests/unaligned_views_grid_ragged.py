@@ -2,9 +2,8 @@
 appends the case to ``unaligned_views.CASES`` (once), exactly as tests/unaligned_views_ragged.py does for the ragged searches, so
 that tests/test_unaligned_views_host.py and tests/test_gpu_unaligned_views.py, unchanged, take it like every other case.
 
-The new test files (tests/test_grid_ragged_host.py, tests/test_gpu_grid_ragged.py) import this module, and both sort before the
-two registry suites.  A run of one of the registry suites ALONE does not import it: its coverage check then reports the entry point
-as uncovered.  Run them together with one of the two new files, or with the whole directory.
+Every file that reads the registry (tests/test_unaligned_views_host.py, tests/test_gpu_unaligned_views.py,
+tests/stream_order.py) imports this module, so the case is there however a file is run.
 
 Lattice coordinates k/16 on a dyadic grid of 1/8 from the origin (every quotient exact); two clouds of unequal size; b = 2 and every
 dimension <= 512 as the registry asks; one call at a capacity below the number of occupied cells (ranks dropped) and one at

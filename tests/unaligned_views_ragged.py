@@ -4,11 +4,9 @@ tests/test_unaligned_views_host.py and tests/test_gpu_unaligned_views.py, unchan
 coverage check against ``_lib.ABI``, the shape check, the CPU paths on shifted views, and on the accelerator every tensor argument
 4, 8 and 12 bytes off a 16-byte boundary against the aligned call.
 
-The registry is a module-level list that those two files read when they are collected and when they run.  The new test files
-(tests/test_ragged_search_host.py, tests/test_gpu_ragged_search.py) import this module, and both sort before the two registry
-suites, so in a run of the suite the cases are registered before the registry is read.  A run of one of the registry suites ALONE
-does not import this module: its coverage check then reports the two entry points as uncovered.  Run them together with
-tests/test_ragged_search_host.py (CPU) or tests/test_gpu_ragged_search.py (accelerator), or with the whole directory.
+The registry is a module-level list that the registry suites read when they are collected.  Every file that reads it
+(tests/test_unaligned_views_host.py, tests/test_gpu_unaligned_views.py, tests/stream_order.py) imports this module, so the
+cases are there however a file is run.
 
 Lattice coordinates (exact distances, ties everywhere); two clouds of unequal size, the second longer than a query tile; b = 2 and
 every dimension <= 512 as the registry asks; each case's anchor is tests/ragged_reference.py."""
